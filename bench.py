@@ -11,7 +11,9 @@ Multi-GPU: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N 
 ranks (weak scaling: K fragments per rank); every rank keeps its WHOLE shard's records in HBM and the shards are
 all-gathered over RCCL once at the end of the timed region (the path's only data collective).
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps (one window), writes the last
+step's outputs when --dump-outputs DIR is given and prints the line: its extra objects below are null.  --full adds them
+(nine timed windows by default, the full object written to --detail-out):
   parity        the engine's output (same F, slots, graph path as the timed region) for the fragments the CPU leg pushes
                 through the oracle: points / level-0 neighbour indices bit-equal, descriptors / scores max |diff|;
                 the process exits non-zero (after printing the line) when a bound is exceeded;
@@ -109,10 +111,19 @@ def parse():
                          "0.03 m grid subsample = tests/golden/demo_bin{0,1}_sub003.npy), each cloud fed as a self-pair like "
                          "demo_registration.py:30-95 does; no stage-0 voxelisation inside the step (the script subsamples before the "
                          "dataset sees the cloud, demo_registration.py:24)")
-    ap.add_argument("--windows", type=int, default=9,
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: nine timed windows, single-fragment latency, PCIe-inclusive and mirrored "
+                         "secondary measurements, the instrumented per-kernel pass (rooflines, ms per KPConv layer), marginal costs, "
+                         "the CPU baseline with the parity check against the oracle, the detail file (each still subject to its --no-* "
+                         "switch)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the LAST timed step returned (its record block as a caller receives it) "
+                         "to DIR/points.npy, DIR/descriptors.npy, DIR/scores.npy (float32; rank 0's step)")
+    ap.add_argument("--windows", type=int, default=None,
                     help="the K-step job is timed this many times back to back (each window bracketed by barrier + synchronize); "
                          "`value` is the MEDIAN window (a 20-fragment window lasts 14 ms: single windows spread 1290..1430 fragments/s "
-                         "across boxes, profiles/r03_experiments.txt x30/x34), all samples, p10 / p90 are in the line")
+                         "across boxes, profiles/r03_experiments.txt x30/x34), all samples, p10 / p90 are in the line.  "
+                         "Default: 1 (exactly --steps timed steps), 9 with --full")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-fragment latency measurement (F = 1, one slot)")
     ap.add_argument("--gather-to", default="0", help="N > 1: the rank that receives the shards at the end (default 0: north_star's "
                     "\"gather of descriptors only at the end\"), or 'all' (all_gather: every rank receives every shard)")
@@ -126,9 +137,10 @@ def parse():
                     "process's own rank): a single process reproduces what rank r of an N-rank run computed (tests/test_gpu_multi.py)")
     ap.add_argument("--limits", default="", help="comma list: neighbourhood limits to use instead of calibrating (to repeat a multi-rank "
                     "run's limits, which are calibrated over all ranks' pools, in one process)")
-    ap.add_argument("--detail-out", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
+    ap.add_argument("--detail-out", default=None,
                     help="file that receives the FULL result object (every family's roofline, per-launch tables, marginal costs, "
-                         "secondary measurements); stdout carries the compact line only")
+                         "secondary measurements); stdout carries the compact line only.  Default: none on a plain run, "
+                         "bench_out/bench_detail.json with --full")
     ap.add_argument("--detail-stdout", action="store_true", help="also print the full object as an EARLIER stdout line")
     ap.add_argument("--raw-points", type=int, default=300000, help="raw points per synthetic fragment (config #2: 300k)")
     ap.add_argument("--kitti-points", type=int, default=120000, help="raw points per synthetic LiDAR sweep (config #4: 120k)")
@@ -290,6 +302,15 @@ def main():
     args = parse()
     if args.bf16_features:
         args.bf16 = True
+    if args.full:
+        args.windows = 9 if args.windows is None else args.windows
+        if args.detail_out is None:
+            args.detail_out = os.path.join(ROOT, "bench_out", "bench_detail.json")
+    else:
+        # a plain run measures the headline only: one window of exactly --steps steps, nothing after it
+        args.windows = 1 if args.windows is None else args.windows
+        args.no_cpu_baseline = args.no_instrument = args.no_mirror_extra = args.no_pcie_extra = args.no_latency = True
+        args.no_marginal = True
     from d3feat_amd import launch
     if launch.needs_launch(args.gpus):
         # `python bench.py --gpus N` without a launcher around it: start the N ranks (or refuse: fewer than N devices)
@@ -499,6 +520,8 @@ def main():
                     continue
                 parts = g[0] if isinstance(g[0], (list, tuple)) else [g[0]]       # overlapped mode: one view per fragment
                 checksums.append(float(sum(float(p.double().sum().item()) for p in parts)))
+            if args.dump_outputs and rank == 0:
+                dump_outputs(args.dump_outputs, last_step_records(gathered[0]))
         del gathered
         shard.reset()
     dt = float(np.median(windows))
@@ -679,7 +702,7 @@ def main():
         # the lab notebook (every family's roofline, per-launch tables, marginal costs, secondary measurements) goes to a FILE;
         # the driver-facing stdout line is the compact object only (r04: a 20 KB line was cut by the driver's 8 KB tail and
         # BENCH_r04.parsed came out null)
-        detail_path = write_detail(res, args.detail_out)
+        detail_path = write_detail(res, args.detail_out) if args.detail_out else None
         if args.detail_stdout:
             print(json.dumps(res))
         print(compact_line(res, detail_path))
@@ -804,6 +827,23 @@ def write_detail(res, path):
         return os.path.relpath(path, ROOT)
     except OSError:
         return None
+
+
+def last_step_records(shard):
+    """One rank's gathered shard (records, frag_rows) -> the [xyz | desc | score] block its LAST step contributed.  records is
+    one view per fragment (overlapped mode) or all fragments' rows back to back."""
+    records, frag_rows = shard
+    if isinstance(records, (list, tuple)):
+        return records[-1]
+    return records[sum(frag_rows[:-1]):sum(frag_rows)]
+
+
+def dump_outputs(out_dir, rec):
+    """--dump-outputs: the last step's records as the arrays a caller of the path receives, float32."""
+    rec = rec.float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("points", rec[:, :3]), ("descriptors", rec[:, 3:-1]), ("scores", rec[:, -1:])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

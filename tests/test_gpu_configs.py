@@ -189,8 +189,8 @@ def test_bench_lines_of_the_other_configurations(device, flag, frames):
     import subprocess
     import sys
     from conftest import ROOT
-    r = subprocess.run([sys.executable, "bench.py", flag, "--steps", "8", "--warmup", "2", "--windows", "3", "--cpu-fragments", "2",
-                        "--no-cpu-1thread"], capture_output=True, text=True, cwd=ROOT, timeout=850,
+    r = subprocess.run([sys.executable, "bench.py", flag, "--full", "--steps", "8", "--warmup", "2", "--windows", "3", "--cpu-fragments",
+                        "2", "--no-cpu-1thread"], capture_output=True, text=True, cwd=ROOT, timeout=850,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     assert len(r.stdout.encode()) < 4096, len(r.stdout)           # stdout = ONE compact line (the driver keeps an 8 KB tail)
@@ -205,3 +205,33 @@ def test_bench_lines_of_the_other_configurations(device, flag, frames):
     assert line["cpu_baseline"]["value"] > 0 and line["latency_ms"]["median"] > 0 and line["latency_ms"]["engine_fallbacks"] == 0
     assert len(line["timing"]["window_ms"]) == 3 and line["roofline"]["frac"] > 0
     assert abs(line["value"] - 8 * frames / (line["ms_per_step"] * 8 * 1e-3)) <= 1e-2 * line["value"]
+
+
+@pytest.mark.timeout(600)
+def test_plain_bench_run_times_its_steps_and_dumps_the_same_outputs(device, tmp_path):
+    """A plain bench.py run (no --full): one window of exactly --steps steps, no secondary objects; --dump-outputs writes the
+    last step's points / descriptors / scores, and a second run with the same arguments writes the same arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    lines, outs = [], []
+    for run in range(2):
+        out = tmp_path / ("out%d" % run)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "8", "--warmup", "2", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, cwd=ROOT, timeout=500, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+        outs.append({n: np.load(out / (n + ".npy")) for n in ("points", "descriptors", "scores")})
+    line = lines[0]
+    assert line["steps"] == 8 and line["dtype"] == "f32" and line["timing"]["windows"] == 1 and len(line["timing"]["window_ms"]) == 1
+    assert abs(line["ms_per_step"] - line["timing"]["window_ms"][0] / 8) <= 1e-3 * line["ms_per_step"] + 1e-4
+    assert line["config"]["engine_fallbacks"] == 0
+    assert all(line[k] is None for k in ("parity", "cpu_baseline", "latency_ms", "roofline")) and line["detail"] is None
+    a, b = outs
+    n = a["points"].shape[0]
+    assert n > 20000 and a["descriptors"].shape == (n, 32) and a["scores"].shape == (n, 1)
+    assert all(x.dtype == np.float32 for x in a.values())
+    assert np.array_equal(a["points"], b["points"])
+    assert np.abs(a["descriptors"] - b["descriptors"]).max() <= 1e-5 and np.abs(a["scores"] - b["scores"]).max() <= 1e-5

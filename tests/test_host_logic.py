@@ -281,3 +281,21 @@ def test_bench_roofline_selection_never_picks_a_multi_launch_group():
     assert bench.matrix_peak("kpconv_fused32_kernel") == 157.3
     # a run made of groups only has no headline kernel rather than a wrong one
     assert bench.select_dominant({k: v for k, v in fam.items() if v["multi"]})[1] is None
+
+
+def test_bench_dump_outputs_are_the_last_steps_records(tmp_path):
+    """bench.py --dump-outputs: the block of the LAST step of a gathered shard, in both shard forms (one view per fragment /
+    all rows back to back), split into the arrays a caller receives, float32."""
+    import torch
+    import bench
+    rng = np.random.default_rng(3)
+    frags = [torch.from_numpy(rng.standard_normal((n, 36)).astype(np.float32)) for n in (5, 7, 4)]
+    rows = [int(f.shape[0]) for f in frags]
+    assert torch.equal(bench.last_step_records((frags, rows)), frags[-1])
+    assert torch.equal(bench.last_step_records((torch.cat(frags), rows)), frags[-1])
+    bench.dump_outputs(str(tmp_path / "out"), bench.last_step_records((torch.cat(frags), rows)))
+    want = frags[-1].numpy()
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("points", "descriptors", "scores")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["points"], want[:, :3]) and np.array_equal(got["descriptors"], want[:, 3:35])
+    assert np.array_equal(got["scores"], want[:, 35:36])

@@ -3,7 +3,7 @@
 #   gpurun --timeout 900 -- 'bash tools/gpu_experiments.sh r02_x1 "<name>|<env assignments>|<bench flags>" ...'
 TAG=${1:-exp}; shift
 REPO=$(pwd); OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT
-LEAN="--no-cpu-baseline --no-instrument --no-mirror-extra --no-pcie-extra"
+LEAN="--full --no-cpu-baseline --no-instrument --no-mirror-extra --no-pcie-extra"
 : > $OUT/experiments.txt
 for SPEC in "$@"; do
   NAME="${SPEC%%|*}"; REST="${SPEC#*|}"; ENVS="${REST%%|*}"; FLAGS="${REST#*|}"

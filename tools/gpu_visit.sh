@@ -16,11 +16,11 @@ tests-all)   # no -x: every failure of a visit in one go
 smoke)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log;;
 benchk20)   # the driver's command
-  timeout ${BENCH_TIMEOUT:-400} python bench.py --steps 20 --warmup 5 --detail-out $OUT/bench_k20.json > $OUT/bench_k20_line.json 2> $OUT/bench_k20.err; echo "bench exit $?" >> $OUT/bench_k20.err
+  timeout ${BENCH_TIMEOUT:-400} python bench.py --full --steps 20 --warmup 5 --detail-out $OUT/bench_k20.json > $OUT/bench_k20_line.json 2> $OUT/bench_k20.err; echo "bench exit $?" >> $OUT/bench_k20.err
   wc -c $OUT/bench_k20_line.json; cut -c1-400 $OUT/bench_k20_line.json;;
 bench)
   # stdout = the compact driver-facing line (bench_line.json); the full object goes to bench.json (as in earlier rounds)
-  timeout ${BENCH_TIMEOUT:-400} python bench.py ${BENCH_FLAGS:-} --detail-out $OUT/bench.json > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench exit $?" >> $OUT/bench.err
+  timeout ${BENCH_TIMEOUT:-400} python bench.py --full ${BENCH_FLAGS:-} --detail-out $OUT/bench.json > $OUT/bench_line.json 2> $OUT/bench.err; echo "bench exit $?" >> $OUT/bench.err
   python - <<PY
 import json
 try:
