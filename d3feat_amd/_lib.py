@@ -49,8 +49,6 @@ SIGNATURES = {
     "d3f_kpconv_pack_weights": (_i, [_vp, _i, _i, _vp, _vp]),
     "d3f_kpconv_fused": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _f, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i,
                               _f, _vp, _i, _vp, _vp, _vp, _i, _vp]),
-    "d3f_kpconv_fused32_mfma": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp,
-                                _i, _vp, _vp, _vp, _vp]),
     "d3f_kpconv_fused32_x3": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp,
                                    _i, _vp, _vp, _vp, _i, _vp]),
     "d3f_kpconv_packed_x3_bytes": (_sz, [_i, _i]),
@@ -82,6 +80,7 @@ SIGNATURES = {
     "d3f_gemm_pack_x3": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_x3_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "d3f_gemm_x3_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    "d3f_gemm_x3_resident": (_i, [_i, _i, _i, _i]),
     "d3f_gemm_x3": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _sz,
                          _vp, _vp, _i, _vp]),
     "d3f_gemm_bf16": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _sz,

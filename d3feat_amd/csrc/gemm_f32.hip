@@ -995,6 +995,18 @@ extern "C" size_t d3f_gemm_x3_workspace_bytes(int M, int N, int K, int M_hint) {
     return p.S > 1 ? d3f_align((size_t)p.S * M * N * sizeof(float)) + 256 : 256;
 }
 
+// LDS of the resident-W persistent form (gemm_x3.h): the whole pre-split W, the A patches and the epilogue vectors
+static size_t gemm_x3r_lds_bytes(int nkt, int NG) {
+    return (size_t)nkt * NG * GX_CHUNK * sizeof(unsigned short) + GXR_PATCH_BYTES + GXR_EPI_BYTES;
+}
+
+// d3f_gemm_x3 takes the resident-W persistent form for tall contractions whose whole pre-split W fits the LDS of a CU
+extern "C" int d3f_gemm_x3_resident(int M, int N, int K, int M_hint) {
+    if (N < 1 || K < GX_BK || (K % GX_BK)) return 0;
+    const int NG = d3f_cdiv(N, 32), m_eff = (M_hint > 0 && M_hint < M) ? M_hint : M;
+    return (NG == 1 || NG == 2 || NG == 4) && gemm_x3r_lds_bytes(K / GX_BK, NG) <= 160 * 1024 && m_eff >= 65536;
+}
+
 // Same operator and argument meaning as d3f_gemm_f32t; Wx = d3f_gemm_pack_x3(W [K,N]).  On top of d3f_gemm_f32t's addressing rules:
 // K = C1 + C2 a multiple of 32 and, for a concatenated operand, C1 a multiple of 32 too (else D3F_ERR_ARG: use d3f_gemm_f32t).
 // workspace >= d3f_gemm_x3_workspace_bytes(M, N, K, M_hint).
@@ -1015,34 +1027,29 @@ extern "C" int d3f_gemm_x3(const float* A, int N1, int lda, int C1, const int* i
     GemmEpi E{row_scale, col_scale, col_shift, residual, ldr, leaky, alpha};
     GemmGather G{idx, ld_idx, N1, N1_dev, C2 > 0 ? skip : nullptr, lds, C1};
     const int nkt = K / GX_BK, NG = d3f_cdiv(N, 32);
-    {   // ---- the resident-W persistent form: tall contractions whose whole pre-split W fits the LDS of a CU (gemm_x3.h) ----
-        static const bool on = []() { const char* e = getenv("D3F_GEMM_X3R"); return !(e && e[0] == '0'); }();
-        const int m_eff = (M_hint > 0 && M_hint < M) ? M_hint : M;
-        const size_t wbytes = (size_t)nkt * NG * GX_CHUNK * sizeof(unsigned short);
-        if (on && (NG == 1 || NG == 2 || NG == 4) && wbytes + GXR_PATCH_BYTES + GXR_EPI_BYTES <= 160 * 1024 && m_eff >= 65536) {
-            // CU count of the CURRENT device (cached per device ordinal: a process may drive several)
-            static std::atomic<int> cus_of[64];
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess) return D3F_ERR_HIP;
-            int cus = cus_of[dev & 63].load(std::memory_order_relaxed);
-            if (!cus) {
-                hipDeviceProp_t pr;
-                if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return D3F_ERR_HIP;
-                cus = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-                cus_of[dev & 63].store(cus, std::memory_order_relaxed);
-            }
-            static std::atomic<unsigned long long> lds_done{0};
-            const void* const fns[3] = {(const void*)gemm_x3r_kernel<1>, (const void*)gemm_x3r_kernel<2>, (const void*)gemm_x3r_kernel<4>};
-            if (d3f_opt_in_lds(lds_done, fns, 160 * 1024) != D3F_OK) return D3F_ERR_HIP;
-            const int grid = std::min(cus, d3f_cdiv(d3f_cdiv(M, 32), 8));
-#define D3F_GXR(TN_) gemm_x3r_kernel<TN_><<<grid, 512, wbytes + GXR_PATCH_BYTES + GXR_EPI_BYTES, stream>>>(A, lda, (const unsigned short*)Wx, nkt, C, ldc, M, N, E, M_dev, G)
-            if (NG == 4) D3F_GXR(4);
-            else if (NG == 2) D3F_GXR(2);
-            else D3F_GXR(1);
-#undef D3F_GXR
-            D3F_LAUNCH_CHECK();
-            return D3F_OK;
+    if (d3f_gemm_x3_resident(M, N, K, M_hint)) {   // ---- the resident-W persistent form (gemm_x3.h) ----
+        // CU count of the CURRENT device (cached per device ordinal: a process may drive several)
+        static std::atomic<int> cus_of[64];
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return D3F_ERR_HIP;
+        int cus = cus_of[dev & 63].load(std::memory_order_relaxed);
+        if (!cus) {
+            hipDeviceProp_t pr;
+            if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return D3F_ERR_HIP;
+            cus = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
+            cus_of[dev & 63].store(cus, std::memory_order_relaxed);
         }
+        static std::atomic<unsigned long long> lds_done{0};
+        const void* const fns[3] = {(const void*)gemm_x3r_kernel<1>, (const void*)gemm_x3r_kernel<2>, (const void*)gemm_x3r_kernel<4>};
+        if (d3f_opt_in_lds(lds_done, fns, 160 * 1024) != D3F_OK) return D3F_ERR_HIP;
+        const int grid = std::min(cus, d3f_cdiv(d3f_cdiv(M, 32), 8));
+#define D3F_GXR(TN_) gemm_x3r_kernel<TN_><<<grid, 512, gemm_x3r_lds_bytes(nkt, NG), stream>>>(A, lda, (const unsigned short*)Wx, nkt, C, ldc, M, N, E, M_dev, G)
+        if (NG == 4) D3F_GXR(4);
+        else if (NG == 2) D3F_GXR(2);
+        else D3F_GXR(1);
+#undef D3F_GXR
+        D3F_LAUNCH_CHECK();
+        return D3F_OK;
     }
     const GemmX3Plan pl = gemm_x3_plan(M, N, K, M_hint);
     const int S = pl.S, tps = pl.tps, bm = 32 * pl.waves;

@@ -54,12 +54,16 @@ def trace_marker(ident, device):
 def _order(t):
     """Spatially coherent visiting order attached to a point / index tensor (attribute `order`, int32), or None."""
     o = getattr(t, "order", None) if t is not None else None
-    return o.data_ptr() if o is not None else None
+    return _ptr(o)
 
 
 def _nd(t):
-    d = getattr(t, "n_dev", None) if t is not None else None
-    return d.data_ptr() if d is not None else None
+    return _ptr(getattr(t, "n_dev", None) if t is not None else None)
+
+
+def _ptr(t):
+    """Device address of an optional tensor (None -> NULL)."""
+    return t.data_ptr() if t is not None else None
 
 
 def _tag(out, src):
@@ -259,7 +263,7 @@ def pack_status(dst, blocks, clear=None):
         args += [blocks[i].data_ptr(), blocks[i].numel()] if i < len(blocks) else [None, 0]
     if clear is not None:
         assert clear.dtype == torch.int32 and clear.is_contiguous() and clear.dim() == 2 and clear.shape[1] == 2
-    _lib.check(lib.d3f_pack_status(dst.data_ptr(), *args, clear.data_ptr() if clear is not None else None,
+    _lib.check(lib.d3f_pack_status(dst.data_ptr(), *args, _ptr(clear),
                                    clear.shape[0] if clear is not None else 0, 1, 2, _stream(dst.device)), "pack_status")
     return dst
 
@@ -470,12 +474,13 @@ def _h(t):
 
 
 def _out_dtype():
-    return torch.bfloat16 if (BF16_FEATURES and not F32_OUTPUT) else torch.float32
+    """dtype of a contraction's output."""
+    return torch.bfloat16 if (BF16_CONTRACTION and BF16_FEATURES and not F32_OUTPUT) else torch.float32
 
 
 def _packed_on_tensor(W, slot, make):
-    """A packed copy of a weight matrix that LIVES AND DIES WITH THE WEIGHT TENSOR: the copy rides on the tensor object that owns
-    the storage (the view's base), keyed by the view's offset / shape / stride and the tensor's version.  (A global cache with
+    """A packed copy of a weight tensor that LIVES AND DIES WITH THE WEIGHT TENSOR: the copy rides on the tensor object that owns
+    the storage (the view's base), keyed by the view's offset / shape / strides and the tensor's version.  (A global cache with
     eviction would free copies that captured graphs still read: round 4 found exactly that -- an engine's replays computed with
     another model's packed weights once 512 entries had gone through the cache.)"""
     base = W._base if W._base is not None else W
@@ -483,7 +488,7 @@ def _packed_on_tensor(W, slot, make):
     if store is None:
         store = {}
         setattr(base, slot, store)
-    key = (W.storage_offset(), tuple(W.shape), W.stride(0))
+    key = (W.storage_offset(), tuple(W.shape), tuple(W.stride()))
     hit = store.get(key)
     if hit is None:
         hit = store[key] = [base._version, make(None)]
@@ -505,52 +510,37 @@ def refresh_packed_weights(tensors):
         if not isinstance(t, torch.Tensor):
             continue
         base = t._base if t._base is not None else t
-        for slot, fn in (("_d3f_bf16t", packed_bf16_weights), ("_d3f_f32t", packed_f32t_weights), ("_d3f_x3", packed_x3_weights)):
-            store = getattr(base, slot, None)
-            for key, hit in list((store or {}).items()):
+        for slot, fn in _PACKERS:
+            for (off, shape, strides), hit in list((getattr(base, slot, None) or {}).items()):
                 if hit[0] != base._version:
-                    off, shape, st0 = key
-                    fn(base.as_strided(shape, (st0, 1), off))
+                    fn(base.as_strided(shape, strides, off))
                     n += 1
-        for slot, fn in (("_d3f_packed", packed_kpconv_weights), ("_d3f_packed_x3", packed_kpconv_weights_x3),
-                         ("_d3f_packed_x3m", packed_kpconv_weights_x3m)):
-            hit = getattr(t, slot, None)
-            if hit is not None and hit[0] != t._version:
-                fn(t)
-                n += 1
     return n
+
+
+def _packed_weights(W, slot, alloc, pack, what):
+    """W f32[K,N] (contiguous rows) -> its packed copy: alloc(K, N) makes the buffer, pack(W, ldb, K, N, buffer, stream) fills it."""
+    def make(t):
+        K, N = W.shape
+        if t is None:
+            t = alloc(K, N)
+        _lib.check(pack(W.data_ptr(), int(W.stride(0)), K, N, t.data_ptr(), _stream(W.device)), what)
+        return t
+    return _packed_on_tensor(W, slot, make)
 
 
 def packed_bf16_weights(W):
     """W f32[K,N] (contiguous rows) -> the bf16 [N][Kp] copy d3f_gemm_bf16 reads; made once per (weight tensor, view, version)."""
-    def make(t):
-        lib = _lib.load()
-        K, N = W.shape
-        Kp = (K + 31) // 32 * 32
-        if t is None:
-            t = torch.empty((N, Kp), dtype=torch.int16, device=W.device)
-        _lib.check(lib.d3f_gemm_pack_bf16(W.data_ptr(), int(W.stride(0)), K, N, t.data_ptr(), _stream(W.device)), "gemm_pack_bf16")
-        return t
-    return _packed_on_tensor(W, "_d3f_bf16t", make)
-
-
-# the LDS-DMA form of the fp32 contraction (d3f_gemm_f32t) is the default; D3F_GEMM_DMA=0 selects round 3's register-staged kernel
-GEMM_DMA = os.environ.get("D3F_GEMM_DMA", "1") != "0"
+    return _packed_weights(W, "_d3f_bf16t", lambda K, N: torch.empty((N, (K + 31) // 32 * 32), dtype=torch.int16, device=W.device),
+                           _lib.load().d3f_gemm_pack_bf16, "gemm_pack_bf16")
 
 
 def packed_f32t_weights(W):
     """W f32[K,N] (contiguous rows) -> the transposed, K-padded f32 [N][Kp] copy d3f_gemm_f32t reads (LDS-DMA copies 16
     contiguous bytes per lane: it cannot transpose); made once per (weight tensor, view, version) -- at a model's first eager
     use, i.e. the engine's warm-up, never inside a captured graph."""
-    def make(t):
-        lib = _lib.load()
-        K, N = W.shape
-        Kp = (K + 31) // 32 * 32
-        if t is None:
-            t = torch.empty((N, Kp), dtype=torch.float32, device=W.device)
-        _lib.check(lib.d3f_gemm_pack_f32t(W.data_ptr(), int(W.stride(0)), K, N, t.data_ptr(), _stream(W.device)), "gemm_pack_f32t")
-        return t
-    return _packed_on_tensor(W, "_d3f_f32t", make)
+    return _packed_weights(W, "_d3f_f32t", lambda K, N: torch.empty((N, (K + 31) // 32 * 32), dtype=torch.float32, device=W.device),
+                           _lib.load().d3f_gemm_pack_f32t, "gemm_pack_f32t")
 
 
 # The operand-split form (d3f_gemm_x3: exact 3 x bf16 split of both fp32 operands, six bf16 MFMA products per fp32 product, fp32
@@ -562,35 +552,46 @@ GEMM_X3 = os.environ.get("D3F_GEMM_X3", "1") != "0"
 def packed_x3_weights(W):
     """W f32[K,N] (contiguous rows) -> the pre-split bf16 planes d3f_gemm_x3 stages ([column group][k-tile][plane][32][40]); made
     once per (weight tensor, view, version), like the transposed fp32 copy."""
-    def make(t):
-        lib = _lib.load()
-        K, N = W.shape
-        if t is None:
-            t = torch.empty((int(lib.d3f_gemm_x3_packed_bytes(K, N)) // 2,), dtype=torch.int16, device=W.device)
-        _lib.check(lib.d3f_gemm_pack_x3(W.data_ptr(), int(W.stride(0)), K, N, t.data_ptr(), _stream(W.device)), "gemm_pack_x3")
-        return t
-    return _packed_on_tensor(W, "_d3f_x3", make)
-
-
-X3R_MIN_ROWS = 65536     # d3f_gemm_x3 takes its resident-W persistent form from this many (expected) rows on (csrc/gemm_f32.hip)
-X3_N32 = os.environ.get("D3F_X3_N32", "1") != "0"      # the 32-column layers on that form too (D3F_X3_N32=0: the fp32 MFMA kernel)
-
-
-def _x3_ok(C1, C2, N, rows=0):
-    """d3f_gemm_x3 can address the call (K and a concatenation's first part multiples of 32) and is the faster kernel for it.  The
-    32-column layers (level-0 unary blocks, memory bound) are slower on its tile form than on the fp32 MFMA kernel (70.9 against
-    83.6 us at M = 707592, K = 64: r04 x6) but faster on the resident-W persistent form of round 5, which the library takes for
-    `rows` >= X3R_MIN_ROWS (70.6 / 105.8 us against 72-82 / 118.6 at M = 707592, 23 / 31 against 28 / 39 at M = 235864: r05 g3)."""
-    wide = N > 32 or (X3_N32 and rows >= X3R_MIN_ROWS and os.environ.get("D3F_GEMM_X3R", "1") != "0")
-    return GEMM_X3 and wide and (C1 + C2) % 32 == 0 and (C2 == 0 or C1 % 32 == 0)
+    lib = _lib.load()
+    return _packed_weights(W, "_d3f_x3", lambda K, N: torch.empty((int(lib.d3f_gemm_x3_packed_bytes(K, N)) // 2,), dtype=torch.int16,
+                                                                  device=W.device), lib.d3f_gemm_pack_x3, "gemm_pack_x3")
 
 
 X3_MAX_ROWS = 65535 * 128      # d3f_gemm_x3's grid holds 65535 row tiles of (at least) 128 rows; beyond: the fp32 kernel
 
 
+def _x3_resident(M, N, K, hint):
+    """Does d3f_gemm_x3 take its resident-W persistent form for this call?  (The library's own predicate.)"""
+    return bool(_lib.load().d3f_gemm_x3_resident(M, N, K, hint))
+
+
+def _x3_ok(C1, C2, N, rows=0):
+    """d3f_gemm_x3 can address the call (K and a concatenation's first part multiples of 32) and is the faster kernel for it.  The
+    32-column layers (level-0 unary blocks, memory bound) are slower on its tile form than on the fp32 MFMA kernel (70.9 against
+    83.6 us at M = 707592, K = 64: r04 x6) but faster on the resident-W persistent form of round 5, which the library takes when
+    d3f_gemm_x3_resident says so for `rows` (70.6 / 105.8 us against 72-82 / 118.6 at M = 707592, 23 / 31 against 28 / 39 at
+    M = 235864: r05 g3)."""
+    fits = GEMM_X3 and (C1 + C2) % 32 == 0 and (C2 == 0 or C1 % 32 == 0)
+    return fits and (N > 32 or _x3_resident(rows, N, C1 + C2, 0))
+
+
+def _route(M, plain, bf16, bf16_ok, f32t_ok, x3, resident):
+    """-> (entry point, record name) of a contraction of M rows.  plain: no gathered or concatenated operand; bf16: BF16_CONTRACTION;
+    bf16_ok / f32t_ok: d3f_gemm_bf16 / d3f_gemm_f32t can address the operands (alignment, leading dimensions); x3: _x3_ok of the
+    call; resident: d3f_gemm_x3_resident of the call.  The record name tells bench.py's per-family tables which form of d3f_gemm_x3
+    runs: the resident form is a streaming kernel, bound by HBM, not by the matrix pipe."""
+    if bf16 and bf16_ok:
+        return "d3f_gemm_bf16", "gemm_bf16"
+    if not f32t_ok:
+        return ("d3f_gemm_f32" if plain else "d3f_gemm_upsample_cat_f32"), "gemm_f32"
+    if x3 and M <= X3_MAX_ROWS:
+        return "d3f_gemm_x3", "gemm_x3r" if resident else "gemm_x3"
+    return "d3f_gemm_f32t", "gemm_f32"
+
+
 def _f32t_ok(N, ldc, out, residual, ldr, vectors, *operands):
     """Can d3f_gemm_f32t address this call?  (every shape of the network can)"""
-    if not GEMM_DMA or N % 4 or ldc % 4 or out.data_ptr() % 16:
+    if N % 4 or ldc % 4 or out.data_ptr() % 16:
         return False
     if residual is not None and (ldr % 4 or residual.data_ptr() % 16):
         return False
@@ -600,40 +601,6 @@ def _f32t_ok(N, ldc, out, residual, ldr, vectors, *operands):
         if t is not None and (cols % 4 or ld % 4 or t.data_ptr() % 16 or cols < 4):
             return False
     return True
-
-
-def _gemm_f32t(A, N1, lda, C1, idx, ld_idx, skip, lds, C2, W, out, ldc, M, N, row_scale, col_scale, col_shift, residual, ldr, leaky,
-               alpha, m_dev, n1_dev, hint, dev):
-    lib = _lib.load()
-    if _x3_ok(C1, C2, N, hint if 0 < hint < M else M) and M <= X3_MAX_ROWS:
-        Wx = packed_x3_weights(W)
-        ws = workspace(lib.d3f_gemm_x3_workspace_bytes(M, N, C1 + C2, hint), dev)
-        # (record name only: which form the library takes -- the predicate of csrc/gemm_f32.hip d3f_gemm_x3, mirrored for the
-        # per-family tables of bench.py: the resident-W persistent form is a streaming kernel, bound by HBM, not by the matrix pipe)
-        ng, rows = (N + 31) // 32, (hint if 0 < hint < M else M)
-        resident = (os.environ.get("D3F_GEMM_X3R", "1") != "0" and ng in (1, 2, 4) and rows >= X3R_MIN_ROWS and
-                    ((C1 + C2) // 32) * ng * 7680 + 36864 + 1024 <= 160 * 1024)
-        with _timed("gemm_x3r" if resident else "gemm_x3", dict(M=M, N=N, K=C1 + C2), dev):
-            rc = lib.d3f_gemm_x3(A.data_ptr(), N1, lda, C1, idx.data_ptr() if idx is not None else None, ld_idx,
-                                 skip.data_ptr() if skip is not None else None, lds, C2, Wx.data_ptr(), out.data_ptr(), ldc, M, N,
-                                 row_scale.data_ptr() if row_scale is not None else None,
-                                 col_scale.data_ptr() if col_scale is not None else None,
-                                 col_shift.data_ptr() if col_shift is not None else None,
-                                 residual.data_ptr() if residual is not None else None, ldr, 1 if leaky else 0, float(alpha),
-                                 ws.data_ptr(), ws.numel(), m_dev, n1_dev, hint, _stream(dev))
-        _lib.check(rc, "gemm_x3")
-        return
-    Wt = packed_f32t_weights(W)
-    ws = workspace(lib.d3f_gemm_workspace_bytes(M, N, C1 + C2, hint), dev)
-    with _timed("gemm_f32", dict(M=M, N=N, K=C1 + C2), dev):
-        rc = lib.d3f_gemm_f32t(A.data_ptr(), N1, lda, C1, idx.data_ptr() if idx is not None else None, ld_idx,
-                               skip.data_ptr() if skip is not None else None, lds, C2, Wt.data_ptr(), out.data_ptr(), ldc, M, N,
-                               row_scale.data_ptr() if row_scale is not None else None,
-                               col_scale.data_ptr() if col_scale is not None else None,
-                               col_shift.data_ptr() if col_shift is not None else None,
-                               residual.data_ptr() if residual is not None else None, ldr, 1 if leaky else 0, float(alpha),
-                               ws.data_ptr(), ws.numel(), m_dev, n1_dev, hint, _stream(dev))
-    _lib.check(rc, "gemm_f32t")
 
 
 def _bf16_ok(*operands):
@@ -646,37 +613,58 @@ def _bf16_ok(*operands):
     return True
 
 
-def _gemm_bf16(A, N1, lda, C1, idx, ld_idx, skip, lds, C2, W, out, M, N, row_scale, col_scale, col_shift, residual, ldr, leaky,
-               alpha, m_dev, n1_dev, hint, dev):
+def _contract(what, A, N1, lda, C1, idx, ld_idx, skip, lds, C2, W, ldb, out, ldc, m_dev, n1_dev, hint, row_scale=None, col_scale=None,
+              col_shift=None, residual=None, ldr=0, leaky=False, alpha=0.2):
+    """out = act(([ A[idx[:,0]] (A itself when idx is None) | skip ] @ W) * row_scale[:,None] * col_scale + col_shift + residual):
+    picks the kernel (_route) and launches it.  W f32[C1 + C2, N] with contiguous rows (ldb)."""
     lib = _lib.load()
-    Wp = packed_bf16_weights(W)
-    # (the bf16 launcher plans its K split for a 64-column tile even when N <= 32: ask for the same plan's slab)
-    ws = workspace(lib.d3f_gemm_bf16_workspace_bytes(M, N, C1 + C2, hint), dev)
-    if out.data_ptr() % 16 or (residual is not None and (residual.data_ptr() % 8 or ldr % 4)):
-        raise ValueError("gemm (bf16): output / residual must be 16 / 8-byte aligned with a leading dimension of 4 k")
-    with _timed("gemm_bf16", dict(M=M, N=N, K=C1 + C2), dev):
-        rc = lib.d3f_gemm_bf16(A.data_ptr(), N1, lda, C1, idx.data_ptr() if idx is not None else None, ld_idx,
-                               skip.data_ptr() if skip is not None else None, lds, C2, Wp.data_ptr(), out.data_ptr(), N, M, N,
-                               row_scale.data_ptr() if row_scale is not None else None,
-                               col_scale.data_ptr() if col_scale is not None else None,
-                               col_shift.data_ptr() if col_shift is not None else None,
-                               residual.data_ptr() if residual is not None else None, ldr, 1 if leaky else 0, float(alpha),
-                               ws.data_ptr(), ws.numel(), m_dev, n1_dev, hint, _h(A), _h(out), _stream(dev))
-    _lib.check(rc, "gemm_bf16")
+    (M, N), K, dev = out.shape, C1 + C2, out.device
+    operands = ((A, lda, C1), (skip, lds, C2))
+    entry, name = _route(M, idx is None and skip is None, BF16_CONTRACTION,
+                         K >= 4 and ldc == N and W.is_contiguous() and _bf16_ok(*operands),
+                         W.is_contiguous() and _f32t_ok(N, ldc, out, residual, ldr, (col_scale, col_shift), *operands),
+                         _x3_ok(C1, C2, N, hint if 0 < hint < M else M), _x3_resident(M, N, K, hint))
+    if entry != "d3f_gemm_bf16" and (_h(A) or _h(skip) or _h(out)):
+        raise TypeError("%s: bfloat16 operands that the bf16 contraction cannot address (K %d, lda %d)" % (what, K, lda))
+    flags = [1 if leaky else 0, float(alpha)]
+    if entry == "d3f_gemm_f32":
+        ws = workspace(lib.d3f_gemm_workspace_bytes(M, N, K, hint), dev)
+        args = [A.data_ptr(), lda, W.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K, _ptr(row_scale), _ptr(col_scale), _ptr(col_shift),
+                _ptr(residual), ldr] + flags + [ws.data_ptr(), ws.numel(), m_dev, hint]
+    else:
+        head = [A.data_ptr(), N1, lda, C1, _ptr(idx), ld_idx, _ptr(skip), lds, C2]
+        if entry == "d3f_gemm_upsample_cat_f32":
+            ws = workspace(lib.d3f_gemm_workspace_bytes(M, N, K, hint), dev)
+            args = head + [W.data_ptr(), ldb, out.data_ptr(), ldc, M, N, _ptr(col_scale), _ptr(col_shift)] + flags
+        else:
+            pack, ws_bytes = {"d3f_gemm_bf16": (packed_bf16_weights, lib.d3f_gemm_bf16_workspace_bytes),
+                              "d3f_gemm_f32t": (packed_f32t_weights, lib.d3f_gemm_workspace_bytes),
+                              "d3f_gemm_x3": (packed_x3_weights, lib.d3f_gemm_x3_workspace_bytes)}[entry]
+            Wp = pack(W)
+            # (the bf16 launcher plans its K split for a 64-column tile even when N <= 32: its own function sizes the slab)
+            ws = workspace(ws_bytes(M, N, K, hint), dev)
+            args = head + [Wp.data_ptr(), out.data_ptr(), ldc, M, N, _ptr(row_scale), _ptr(col_scale), _ptr(col_shift), _ptr(residual),
+                           ldr] + flags
+        args += [ws.data_ptr(), ws.numel(), m_dev, n1_dev, hint]
+    if entry == "d3f_gemm_bf16":
+        if out.data_ptr() % 16 or (residual is not None and (residual.data_ptr() % 8 or ldr % 4)):
+            raise ValueError("gemm (bf16): output / residual must be 16 / 8-byte aligned with a leading dimension of 4 k")
+        args += [_h(A), _h(out)]
+    with _timed(name, dict(M=M, N=N, K=K), dev):
+        rc = getattr(lib, entry)(*args, _stream(dev))
+    _lib.check(rc, entry[4:])
 
 
 def gemm(A, Bm, row_scale=None, col_scale=None, col_shift=None, residual=None, leaky=False, alpha=0.2, out=None):
     """out = act((A @ Bm) * row_scale[:,None] * col_scale + col_shift + residual) on the matrix cores."""
-    lib = _lib.load()
     A, lda = _rows(_feat(A, "A"), "A")
     Bm, ldb = _rows(_req(Bm, torch.float32, "B"), "B")
     M, K = A.shape
     if Bm.shape[0] != K:
         raise ValueError("gemm: A is %s, B is %s" % (tuple(A.shape), tuple(Bm.shape)))
     N = Bm.shape[1]
-    dev = A.device
     if out is None:
-        out = torch.empty((M, N), dtype=_out_dtype() if BF16_CONTRACTION else torch.float32, device=dev)
+        out = torch.empty((M, N), dtype=_out_dtype(), device=A.device)
     out, ldc = _rows(out, "out")
     ldr = 0
     if residual is not None:
@@ -688,27 +676,8 @@ def gemm(A, Bm, row_scale=None, col_scale=None, col_shift=None, residual=None, l
             _req(v, torch.float32, name)
             if v.numel() != n or not v.is_contiguous():
                 raise ValueError("%s must be a contiguous vector of %d" % (name, n))
-    hint = int(getattr(A, "n_hint", 0) or 0)
-    if BF16_CONTRACTION and K >= 4 and ldc == N and Bm.is_contiguous() and _bf16_ok((A, lda, K)):
-        _gemm_bf16(A, M, lda, K, None, 0, None, 0, 0, Bm, out, M, N, row_scale, col_scale, col_shift, residual, ldr, leaky, alpha,
-                   _nd(A), None, hint, dev)
-        return _tag(out, A)
-    if _h(A) or _h(out):
-        raise TypeError("gemm: bfloat16 operands that the bf16 contraction cannot address (K %d, lda %d)" % (K, lda))
-    if Bm.is_contiguous() and _f32t_ok(N, ldc, out, residual, ldr, (col_scale, col_shift), (A, lda, K)):
-        _gemm_f32t(A, M, lda, K, None, 0, None, 0, 0, Bm, out, ldc, M, N, row_scale, col_scale, col_shift, residual, ldr, leaky, alpha,
-                   _nd(A), None, hint, dev)
-        return _tag(out, A)
-    nbytes = lib.d3f_gemm_workspace_bytes(M, N, K, hint)
-    ws = workspace(nbytes, dev)
-    with _timed("gemm_f32", dict(M=M, N=N, K=K), dev):
-        rc = lib.d3f_gemm_f32(A.data_ptr(), lda, Bm.data_ptr(), ldb, out.data_ptr(), ldc, M, N, K,
-                              row_scale.data_ptr() if row_scale is not None else None,
-                              col_scale.data_ptr() if col_scale is not None else None,
-                              col_shift.data_ptr() if col_shift is not None else None,
-                              residual.data_ptr() if residual is not None else None, ldr,
-                              1 if leaky else 0, float(alpha), ws.data_ptr(), ws.numel(), _nd(A), hint, _stream(dev))
-    _lib.check(rc, "gemm_f32")
+    _contract("gemm", A, M, lda, K, None, 0, None, 0, 0, Bm, ldb, out, ldc, _nd(A), None, int(getattr(A, "n_hint", 0) or 0),
+              row_scale, col_scale, col_shift, residual, ldr, leaky, alpha)
     return _tag(out, A)
 
 
@@ -729,7 +698,6 @@ class UpsampleCat:
 
 def gemm_upsample_cat(u, W, col_scale=None, col_shift=None, leaky=False, alpha=0.2):
     """out = act(([ x'[inds[:,0]] | skip ] @ W) * col_scale + col_shift) without building the concatenation."""
-    lib = _lib.load()
     x, ldx = _rows(_feat(u.x, "x"), "x")
     inds, ldi = _rows(_req(u.inds, torch.int32, "inds"), "inds")
     W, ldb = _rows(_req(W, torch.float32, "W"), "W")
@@ -742,34 +710,14 @@ def gemm_upsample_cat(u, W, col_scale=None, col_shift=None, leaky=False, alpha=0
         raise ValueError("gemm_upsample_cat: W has %d rows, operands %d + %d columns" % (W.shape[0], C1, C2))
     if C2 and (C1 % 4 or lds % 4 or skip.data_ptr() % 16) and not _h(x):
         return gemm(u.materialize(), W, col_scale=col_scale, col_shift=col_shift, leaky=leaky, alpha=alpha)
-    dev = x.device
-    out = torch.empty((M, N), dtype=_out_dtype() if BF16_CONTRACTION else torch.float32, device=dev)
-    hint = int(getattr(inds, "n_hint", 0) or 0)
-    if BF16_CONTRACTION and W.is_contiguous() and _bf16_ok((x, ldx, C1), (skip, lds, C2)):
-        _gemm_bf16(x, x.shape[0], ldx, C1, inds, ldi, skip, lds, C2, W, out, M, N, None, col_scale, col_shift, None, 0, leaky, alpha,
-                   _nd(inds), _nd(x), hint, dev)
-        return _tag(out, inds)
-    if _h(x) or _h(out):
-        raise TypeError("gemm_upsample_cat: bfloat16 operands that the bf16 contraction cannot address")
-    if W.is_contiguous() and _f32t_ok(N, N, out, None, 0, (col_scale, col_shift), (x, ldx, C1), (skip, lds, C2) if C2 else (None, 0, 0)):
-        _gemm_f32t(x, x.shape[0], ldx, C1, inds, ldi, skip, lds, C2, W, out, N, M, N, None, col_scale, col_shift, None, 0, leaky, alpha,
-                   _nd(inds), _nd(x), hint, dev)
-        return _tag(out, inds)
-    nbytes = lib.d3f_gemm_workspace_bytes(M, N, C1 + C2, hint)
-    ws = workspace(nbytes, dev)
-    with _timed("gemm_f32", dict(M=M, N=N, K=C1 + C2), dev):
-        rc = lib.d3f_gemm_upsample_cat_f32(x.data_ptr(), x.shape[0], ldx, C1, inds.data_ptr(), ldi,
-                                           skip.data_ptr() if C2 else None, lds, C2, W.data_ptr(), ldb, out.data_ptr(), N, M, N,
-                                           col_scale.data_ptr() if col_scale is not None else None,
-                                           col_shift.data_ptr() if col_shift is not None else None, 1 if leaky else 0,
-                                           float(alpha), ws.data_ptr(), ws.numel(), _nd(inds), _nd(x), hint, _stream(dev))
-    _lib.check(rc, "gemm_upsample_cat_f32")
+    out = torch.empty((M, N), dtype=_out_dtype(), device=x.device)
+    _contract("gemm_upsample_cat", x, x.shape[0], ldx, C1, inds, ldi, skip, lds, C2, W, ldb, out, N, _nd(inds), _nd(x),
+              int(getattr(inds, "n_hint", 0) or 0), col_scale=col_scale, col_shift=col_shift, leaky=leaky, alpha=alpha)
     return _tag(out, inds)
 
 
 def gemm_cat2(A1, A2, W, col_scale=None, col_shift=None, leaky=False, alpha=0.2):
     """out = act(([A1 | A2] @ W) * col_scale + col_shift) without building the concatenation (same rows in A1 and A2)."""
-    lib = _lib.load()
     A1, ld1 = _rows(_feat(A1, "A1"), "A1")
     A2, ld2 = _rows(_feat(A2, "A2"), "A2")
     W, ldb = _rows(_req(W, torch.float32, "W"), "W")
@@ -778,121 +726,71 @@ def gemm_cat2(A1, A2, W, col_scale=None, col_shift=None, leaky=False, alpha=0.2)
         raise ValueError("gemm_cat2: operands %s | %s, W %s" % (tuple(A1.shape), tuple(A2.shape), tuple(W.shape)))
     if (C1 % 4 or ld2 % 4 or A2.data_ptr() % 16) and not _h(A1):
         return gemm(torch.cat([A1, A2], 1), W, col_scale=col_scale, col_shift=col_shift, leaky=leaky, alpha=alpha)
-    dev = A1.device
-    out = torch.empty((M, N), dtype=_out_dtype() if BF16_CONTRACTION else torch.float32, device=dev)
-    hint = int(getattr(A1, "n_hint", 0) or 0)
-    if BF16_CONTRACTION and W.is_contiguous() and _bf16_ok((A1, ld1, C1), (A2, ld2, C2)):
-        _gemm_bf16(A1, M, ld1, C1, None, 0, A2, ld2, C2, W, out, M, N, None, col_scale, col_shift, None, 0, leaky, alpha,
-                   _nd(A1), _nd(A1), hint, dev)
-        return _tag(out, A1)
-    if _h(A1) or _h(A2) or _h(out):
-        raise TypeError("gemm_cat2: bfloat16 operands that the bf16 contraction cannot address")
-    if W.is_contiguous() and _f32t_ok(N, N, out, None, 0, (col_scale, col_shift), (A1, ld1, C1), (A2, ld2, C2)):
-        _gemm_f32t(A1, M, ld1, C1, None, 0, A2, ld2, C2, W, out, N, M, N, None, col_scale, col_shift, None, 0, leaky, alpha,
-                   _nd(A1), _nd(A1), hint, dev)
-        return _tag(out, A1)
-    nbytes = lib.d3f_gemm_workspace_bytes(M, N, C1 + C2, hint)
-    ws = workspace(nbytes, dev)
-    with _timed("gemm_f32", dict(M=M, N=N, K=C1 + C2), dev):
-        rc = lib.d3f_gemm_upsample_cat_f32(A1.data_ptr(), M, ld1, C1, None, 0, A2.data_ptr(), ld2, C2, W.data_ptr(), ldb,
-                                           out.data_ptr(), N, M, N,
-                                           col_scale.data_ptr() if col_scale is not None else None,
-                                           col_shift.data_ptr() if col_shift is not None else None, 1 if leaky else 0,
-                                           float(alpha), ws.data_ptr(), ws.numel(), _nd(A1), _nd(A1), hint, _stream(dev))
-    _lib.check(rc, "gemm_cat2")
+    out = torch.empty((M, N), dtype=_out_dtype(), device=A1.device)
+    _contract("gemm_cat2", A1, M, ld1, C1, None, 0, A2, ld2, C2, W, ldb, out, N, _nd(A1), _nd(A1), int(getattr(A1, "n_hint", 0) or 0),
+              col_scale=col_scale, col_shift=col_shift, leaky=leaky, alpha=alpha)
     return _tag(out, A1)
+
+
+def _kp_front(what, query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent, KP_influence,
+              aggregation_mode, col_scale=None, col_shift=None, residual=None, leaky=False, alpha=0.2, row_pos=True, feat=_feat):
+    """The operand preparation every KPConv wrapper shares -> (gather, kpar, row_pos, epi, tail, f): the argument groups of the
+    entry points of csrc/kpconv.hip, tensors and host arrays as objects (they must outlive the launch: pass them through _arg) --
+      gather = q, Nq, s, Ns, idx, ld_idx, K, f, ldf     kpar = kernel points (host), num_kp, extent, influence, aggregation
+      epi = col_scale, col_shift, residual, ldr, leaky, alpha     tail = Nq_dev, Ns_dev, q_order
+    row_pos: the row-positive flags of the features (d3f_row_positive, launched here), or None when the form does not read them."""
+    lib = _lib.load()
+    q = _req(query_points, torch.float32, "query_points", 2).contiguous()
+    s = _req(support_points, torch.float32, "support_points", 2).contiguous()
+    idx, ld_idx = _rows(_req(neighbors_indices, torch.int32, "neighbors_indices"), "neighbors_indices")
+    f, ldf = _rows(feat(features, "features"), "features")
+    if KP_influence not in _INFLUENCE:
+        raise ValueError("Unknown influence function type (config.KP_influence)")
+    if aggregation_mode not in _AGGREGATION:
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    if K_values is not None and f.shape[1] != K_values.shape[1]:
+        raise ValueError("%s: features have %d channels, K_values expects %d" % (what, f.shape[1], K_values.shape[1]))
+    kp = _kp_host(K_points)
+    Nq, Ns = q.shape[0], s.shape[0]
+    nq_dev, ns_dev = _nd(query_points), _nd(support_points)
+    if ns_dev is None:
+        ns_dev = _nd(features)
+    rpos = None
+    if row_pos:
+        rpos = torch.empty((max(Ns, 1),), dtype=torch.uint8, device=q.device)
+        _lib.check(lib.d3f_row_positive(f.data_ptr(), Ns, ldf, f.shape[1], rpos.data_ptr(), ns_dev, _h(f), _stream(q.device)),
+                   "row_positive")
+    ldr = 0
+    if residual is not None:
+        residual, ldr = _rows(_req(residual, torch.float32, "residual"), "residual")
+    return ((q, Nq, s, Ns, idx, ld_idx, idx.shape[1], f, ldf),
+            (kp, kp.shape[0], float(KP_extent), _INFLUENCE[KP_influence], _AGGREGATION[aggregation_mode]), rpos,
+            (col_scale, col_shift, residual, ldr, 1 if leaky else 0, float(alpha)), (nq_dev, ns_dev, _order(query_points)), f)
+
+
+def _arg(v):
+    """A kernel argument: a tensor's device address, a host array's address, anything else as it is."""
+    if isinstance(v, torch.Tensor):
+        return v.data_ptr()
+    return v.ctypes.data if isinstance(v, np.ndarray) else v
 
 
 def kpconv_aggregate(query_points, support_points, neighbors_indices, features, K_points, KP_extent,
                      KP_influence="linear", aggregation_mode="sum"):
     """-> (wf f32[Nq, num_kp*Cin], inv_cnt f32[Nq])   (phase 1 of KPConv_ops)."""
     lib = _lib.load()
-    q = _req(query_points, torch.float32, "query_points", 2).contiguous()
-    s = _req(support_points, torch.float32, "support_points", 2).contiguous()
-    idx, ld_idx = _rows(_req(neighbors_indices, torch.int32, "neighbors_indices"), "neighbors_indices")
-    f, ldf = _rows(_feat(features, "features"), "features")
-    if KP_influence not in _INFLUENCE:
-        raise ValueError("Unknown influence function type (config.KP_influence)")
-    if aggregation_mode not in _AGGREGATION:
-        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
-    kp = _kp_host(K_points)
-    num_kp = kp.shape[0]
-    Nq, Ns, K, Cin = q.shape[0], s.shape[0], idx.shape[1], f.shape[1]
-    if idx.shape[0] != Nq or f.shape[0] != Ns:
+    if neighbors_indices.shape[0] != query_points.shape[0] or features.shape[0] != support_points.shape[0]:
         raise ValueError("KPConv: %d queries / %d index rows, %d supports / %d feature rows" %
-                         (Nq, idx.shape[0], Ns, f.shape[0]))
-    dev = q.device
-    wf = torch.empty((Nq, num_kp * Cin), dtype=torch.float32, device=dev)
-    inv_cnt = torch.empty((Nq,), dtype=torch.float32, device=dev)
-    row_pos = torch.empty((max(Ns, 1),), dtype=torch.uint8, device=dev)
-    st = _stream(dev)
-    nq_dev, ns_dev = _nd(query_points), _nd(support_points)
-    if ns_dev is None:
-        ns_dev = _nd(features)
-    _lib.check(lib.d3f_row_positive(f.data_ptr(), Ns, ldf, Cin, row_pos.data_ptr(), ns_dev, _h(f), st), "row_positive")
-    with _timed("kpconv_aggregate", dict(Nq=Nq, Ns=Ns, K=K, Cin=Cin), dev):
-        rc = lib.d3f_kpconv_aggregate(q.data_ptr(), Nq, s.data_ptr(), Ns, idx.data_ptr(), ld_idx, K, f.data_ptr(), ldf,
-                                      Cin, row_pos.data_ptr(), kp.ctypes.data, num_kp, float(KP_extent),
-                                      _INFLUENCE[KP_influence], _AGGREGATION[aggregation_mode], wf.data_ptr(),
-                                      inv_cnt.data_ptr(), nq_dev, ns_dev, _order(query_points), _h(f), st)
+                         (query_points.shape[0], neighbors_indices.shape[0], support_points.shape[0], features.shape[0]))
+    gather, kpar, row_pos, _, tail, f = _kp_front("KPConv", query_points, support_points, neighbors_indices, features, K_points, None,
+                                                  KP_extent, KP_influence, aggregation_mode)
+    Nq, Ns, K, Cin = gather[1], gather[3], gather[6], f.shape[1]
+    wf = torch.empty((Nq, kpar[1] * Cin), dtype=torch.float32, device=f.device)
+    inv_cnt = torch.empty((Nq,), dtype=torch.float32, device=f.device)
+    with _timed("kpconv_aggregate", dict(Nq=Nq, Ns=Ns, K=K, Cin=Cin), f.device):
+        rc = lib.d3f_kpconv_aggregate(*map(_arg, (*gather, Cin, row_pos, *kpar, wf, inv_cnt, *tail, _h(f), _stream(f.device))))
     _lib.check(rc, "kpconv_aggregate")
     return _tag(wf, query_points), _tag(inv_cnt, query_points)
-
-
-def kpconv_fused32(query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent,
-                   KP_influence="linear", aggregation_mode="sum", col_scale=None, col_shift=None, residual=None,
-                   leaky=False, alpha=0.2):
-    """Whole KPConv (+ epilogue) for Cin = Cout = 32 in one kernel (the aggregation tile is contracted from LDS)."""
-    lib = _lib.load()
-    q = _req(query_points, torch.float32, "query_points", 2).contiguous()
-    s = _req(support_points, torch.float32, "support_points", 2).contiguous()
-    idx, ld_idx = _rows(_req(neighbors_indices, torch.int32, "neighbors_indices"), "neighbors_indices")
-    f, ldf = _rows(_feat(features, "features"), "features")
-    kp = _kp_host(K_points)
-    num_kp, cin, cout = K_values.shape
-    if cin != 32 or cout != 32 or f.shape[1] != 32:
-        raise ValueError("kpconv_fused32 needs Cin == Cout == 32")
-    x3 = KP_X3 and (num_kp * cin) % 32 == 0
-    # the aggregation on the matrix cores as well (d3f_kpconv_fused32_mfma): the shipped configuration, fp32 features
-    mfma = (KP_MFMA and x3 and num_kp == 15 and KP_influence == "linear" and aggregation_mode == "sum" and f.dtype == torch.float32
-            and idx.shape[1] <= 64)
-    if mfma:
-        W = packed_kpconv_weights_x3m(K_values)
-    else:
-        W = packed_kpconv_weights_x3(K_values) if x3 else _req(K_values, torch.float32, "K_values").reshape(num_kp * cin, cout).contiguous()
-    Nq, Ns, K = q.shape[0], s.shape[0], idx.shape[1]
-    dev = q.device
-    out = torch.empty((Nq, cout), dtype=f.dtype, device=dev)
-    row_pos = torch.empty((max(Ns, 1),), dtype=torch.uint8, device=dev)
-    ldr = 0
-    if residual is not None:
-        residual, ldr = _rows(_req(residual, torch.float32, "residual"), "residual")
-    st = _stream(dev)
-    nq_dev, ns_dev = _nd(query_points), _nd(support_points)
-    if ns_dev is None:
-        ns_dev = _nd(features)
-    _lib.check(lib.d3f_row_positive(f.data_ptr(), Ns, ldf, 32, row_pos.data_ptr(), ns_dev, _h(f), st), "row_positive")
-    if mfma:
-        with _timed("kpconv_fused32", dict(Nq=Nq, Ns=Ns, K=K, Cin=32, Cout=32), dev):
-            rc = lib.d3f_kpconv_fused32_mfma(q.data_ptr(), Nq, s.data_ptr(), Ns, idx.data_ptr(), ld_idx, K, f.data_ptr(), ldf,
-                                             row_pos.data_ptr(), kp.ctypes.data, num_kp, float(KP_extent), _INFLUENCE[KP_influence],
-                                             _AGGREGATION[aggregation_mode], W.data_ptr(),
-                                             col_scale.data_ptr() if col_scale is not None else None,
-                                             col_shift.data_ptr() if col_shift is not None else None,
-                                             residual.data_ptr() if residual is not None else None, ldr, 1 if leaky else 0,
-                                             float(alpha), out.data_ptr(), cout, nq_dev, ns_dev, _order(query_points), st)
-        _lib.check(rc, "kpconv_fused32_mfma")
-        return _tag(out, query_points)
-    with _timed("kpconv_fused32", dict(Nq=Nq, Ns=Ns, K=K, Cin=32, Cout=32), dev):
-        rc = (lib.d3f_kpconv_fused32_x3 if x3 else lib.d3f_kpconv_fused32)(q.data_ptr(), Nq, s.data_ptr(), Ns, idx.data_ptr(), ld_idx, K, f.data_ptr(), ldf,
-                                    row_pos.data_ptr(), kp.ctypes.data, num_kp, float(KP_extent), _INFLUENCE[KP_influence],
-                                    _AGGREGATION[aggregation_mode], W.data_ptr(),
-                                    col_scale.data_ptr() if col_scale is not None else None,
-                                    col_shift.data_ptr() if col_shift is not None else None,
-                                    residual.data_ptr() if residual is not None else None, ldr, 1 if leaky else 0,
-                                    float(alpha), out.data_ptr(), cout, nq_dev, ns_dev, _order(query_points), _h(f), st)
-    _lib.check(rc, "kpconv_fused32")
-    return _tag(out, query_points)
 
 
 def kpconv_fused_supported(cin, cout, num_kp, KP_influence, aggregation_mode, available=False):
@@ -903,111 +801,86 @@ def kpconv_fused_supported(cin, cout, num_kp, KP_influence, aggregation_mode, av
     return r >= 1 if available else r == 1
 
 
+def _packed_kpconv(K_values, slot, alloc, pack, what):
+    """K_values f32[num_kp, Cin, Cout] -> a packed copy of the [num_kp*Cin, Cout] matrix, riding on the tensor like the contraction
+    weights' copies (made at a model's first eager use -- the engine's warm-up -- never inside a captured graph)."""
+    def make(t):
+        num_kp, cin, cout = K_values.shape
+        W = _req(K_values, torch.float32, "K_values").reshape(num_kp * cin, cout).contiguous()
+        if t is None:
+            t = alloc(W)
+        _lib.check(pack(W.data_ptr(), num_kp * cin, cout, t.data_ptr(), _stream(W.device)), what)
+        return t
+    return _packed_on_tensor(K_values, slot, make)
+
+
 def packed_kpconv_weights(K_values):
-    """K_values f32[num_kp, Cin, Cout] -> the k-block-packed copy d3f_kpconv_fused reads (made once per weight tensor and
-    version: the result rides on the tensor object, so a model's cached device weights are packed at their first use --
-    the engine's eager warm-up -- and never inside a captured graph)."""
-    cached = getattr(K_values, "_d3f_packed", None)
-    if cached is not None and cached[0] == K_values._version:
-        return cached[1]
-    lib = _lib.load()
-    num_kp, cin, cout = K_values.shape
-    W = _req(K_values, torch.float32, "K_values").reshape(num_kp * cin, cout).contiguous()
-    # an in-place update of the weights re-packs into the SAME buffer (captured graphs hold its address: _packed_on_tensor)
-    Wp = cached[1] if cached is not None else torch.empty_like(W)
-    _lib.check(lib.d3f_kpconv_pack_weights(W.data_ptr(), num_kp * cin, cout, Wp.data_ptr(), _stream(W.device)), "kpconv_pack_weights")
-    K_values._d3f_packed = (K_values._version, Wp)
-    return Wp
-
-
-# The fused KPConv kernels of levels 1 and 2 contract their LDS tile in the operand-split form (csrc/kpconv.hip, round 5: three exact
-# bf16 planes per operand, six exact products per fp32 product, fp32 accumulate -- fp32 in, fp32 out); D3F_KP_X3=0 keeps the
-# v_mfma_f32_16x16x4_f32 form.
-KP_X3 = os.environ.get("D3F_KP_X3", "1") != "0"
-
-
-# the level-0 KPConv with its aggregation on the matrix cores too (csrc/kpconv.hip: kpconv_fused32m_kernel): OFF by default -- built,
-# verified (tests/test_gpu_kpconv_x3.py) and measured SLOWER than the vector form (profiles/r06_experiments.txt k1-k6: 247-298 against
-# 220-235 us per level-0 launch at F = 4): these kernels are bound by the latency of a workgroup's dependent chain at three workgroups
-# per CU, not by the vector pipe.  D3F_KP_MFMA=1 selects it.
-KP_MFMA = os.environ.get("D3F_KP_MFMA", "0") == "1"
-
-
-def packed_kpconv_weights_x3m(K_values):
-    """K_values f32[15, Cin, Cout] -> the pre-split bf16 planes of W'[16 s + p][n] = K_values[p][c(s)][n] (p < 15; 0 for the 16th slot;
-    c(s) = the even channels, then the odd ones):
-    the channel-major k order in which the matrix-core aggregation leaves its weighted features.  Rides on the tensor like the other
-    packed copies (re-packed in place when the tensor's version changes)."""
-    cached = getattr(K_values, "_d3f_packed_x3m", None)
-    if cached is not None and cached[0] == K_values._version:
-        return cached[1]
-    lib = _lib.load()
-    num_kp, cin, cout = K_values.shape
-    Wp = torch.zeros((cin, 16, cout), dtype=torch.float32, device=K_values.device)
-    order = list(range(0, cin, 2)) + list(range(1, cin, 2))             # the even channels (chain 0 of the kernel), then the odd ones
-    Wp[:, :num_kp] = _req(K_values, torch.float32, "K_values").permute(1, 0, 2)[order]
-    Wp = Wp.reshape(cin * 16, cout).contiguous()
-    Wx = cached[1] if cached is not None else \
-        torch.empty((int(lib.d3f_kpconv_packed_x3_bytes(cin * 16, cout)) // 2,), dtype=torch.int16, device=Wp.device)
-    _lib.check(lib.d3f_kpconv_pack_weights_x3(Wp.data_ptr(), cin * 16, cout, Wx.data_ptr(), _stream(Wp.device)), "kpconv_pack_weights_x3")
-    K_values._d3f_packed_x3m = (K_values._version, Wx)
-    return Wx
+    """-> the k-block-packed copy d3f_kpconv_fused reads."""
+    return _packed_kpconv(K_values, "_d3f_packed", torch.empty_like, _lib.load().d3f_kpconv_pack_weights, "kpconv_pack_weights")
 
 
 def packed_kpconv_weights_x3(K_values):
-    """K_values f32[num_kp, Cin, Cout] -> the pre-split bf16 planes d3f_kpconv_fused_x3 reads; made once per weight tensor and
-    version (rides on the tensor object like packed_kpconv_weights: never inside a captured graph)."""
-    cached = getattr(K_values, "_d3f_packed_x3", None)
-    if cached is not None and cached[0] == K_values._version:
-        return cached[1]
+    """-> the pre-split bf16 planes d3f_kpconv_fused_x3 / d3f_kpconv_fused32_x3 read."""
+    lib = _lib.load()
+    return _packed_kpconv(K_values, "_d3f_packed_x3",
+                          lambda W: torch.empty((int(lib.d3f_kpconv_packed_x3_bytes(*W.shape)) // 2,), dtype=torch.int16, device=W.device),
+                          lib.d3f_kpconv_pack_weights_x3, "kpconv_pack_weights_x3")
+
+
+# every packed copy that can ride on a weight tensor: its slot and the packer that (re-)makes it
+_PACKERS = (("_d3f_bf16t", packed_bf16_weights), ("_d3f_f32t", packed_f32t_weights), ("_d3f_x3", packed_x3_weights),
+            ("_d3f_packed", packed_kpconv_weights), ("_d3f_packed_x3", packed_kpconv_weights_x3))
+
+
+# The fused KPConv kernels of levels 0 to 2 contract their LDS tile in the operand-split form (csrc/kpconv.hip, round 5: three exact
+# bf16 planes per operand, six exact products per fp32 product, fp32 accumulate -- fp32 in, fp32 out); D3F_KP_X3=0 keeps the
+# fp32 MFMA form.
+KP_X3 = os.environ.get("D3F_KP_X3", "1") != "0"
+
+
+def _kpconv_fused(what, query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent, KP_influence,
+                  aggregation_mode, col_scale, col_shift, residual, leaky, alpha):
     lib = _lib.load()
     num_kp, cin, cout = K_values.shape
-    W = _req(K_values, torch.float32, "K_values").reshape(num_kp * cin, cout).contiguous()
-    Wx = cached[1] if cached is not None else \
-        torch.empty((int(lib.d3f_kpconv_packed_x3_bytes(num_kp * cin, cout)) // 2,), dtype=torch.int16, device=W.device)
-    _lib.check(lib.d3f_kpconv_pack_weights_x3(W.data_ptr(), num_kp * cin, cout, Wx.data_ptr(), _stream(W.device)), "kpconv_pack_weights_x3")
-    K_values._d3f_packed_x3 = (K_values._version, Wx)
-    return Wx
+    gather, kpar, row_pos, epi, tail, f = _kp_front(what, query_points, support_points, neighbors_indices, features, K_points, K_values,
+                                                    KP_extent, KP_influence, aggregation_mode, col_scale, col_shift, residual, leaky,
+                                                    alpha)
+    level0 = what == "kpconv_fused32"
+    x3 = KP_X3 and (num_kp * cin) % 32 == 0 and (level0 or cout % 16 == 0)
+    if x3:
+        W = packed_kpconv_weights_x3(K_values)
+    elif level0:
+        W = _req(K_values, torch.float32, "K_values").reshape(num_kp * cin, cout).contiguous()
+    else:
+        W = packed_kpconv_weights(K_values)
+    out = torch.empty((gather[1], cout), dtype=f.dtype, device=f.device)
+    with _timed(what, dict(Nq=gather[1], Ns=gather[3], K=gather[6], Cin=cin, Cout=cout), f.device):
+        if level0:
+            rc = (lib.d3f_kpconv_fused32_x3 if x3 else lib.d3f_kpconv_fused32)(
+                *map(_arg, (*gather, row_pos, *kpar, W, *epi, out, cout, *tail, _h(f), _stream(f.device))))
+        else:
+            rc = (lib.d3f_kpconv_fused_x3 if x3 else lib.d3f_kpconv_fused)(
+                *map(_arg, (*gather, cin, row_pos, *kpar, W, cout, *epi, out, cout, *tail, _h(f), _stream(f.device))))
+    _lib.check(rc, what)
+    return _tag(out, query_points)
+
+
+def kpconv_fused32(query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent,
+                   KP_influence="linear", aggregation_mode="sum", col_scale=None, col_shift=None, residual=None,
+                   leaky=False, alpha=0.2):
+    """Whole KPConv (+ epilogue) for Cin = Cout = 32 in one kernel (the aggregation tile is contracted from LDS)."""
+    if tuple(K_values.shape[1:]) != (32, 32):
+        raise ValueError("kpconv_fused32 needs Cin == Cout == 32")
+    return _kpconv_fused("kpconv_fused32", query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent,
+                         KP_influence, aggregation_mode, col_scale, col_shift, residual, leaky, alpha)
 
 
 def kpconv_fused(query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent,
                  KP_influence="linear", aggregation_mode="sum", col_scale=None, col_shift=None, residual=None,
                  leaky=False, alpha=0.2):
     """Whole KPConv (+ epilogue) for Cin == Cout in {64, 128} in one kernel (kpconv_fused_supported says when)."""
-    lib = _lib.load()
-    q = _req(query_points, torch.float32, "query_points", 2).contiguous()
-    s = _req(support_points, torch.float32, "support_points", 2).contiguous()
-    idx, ld_idx = _rows(_req(neighbors_indices, torch.int32, "neighbors_indices"), "neighbors_indices")
-    f, ldf = _rows(_feat(features, "features"), "features")
-    kp = _kp_host(K_points)
-    num_kp, cin, cout = K_values.shape
-    if f.shape[1] != cin:
-        raise ValueError("kpconv_fused: features have %d channels, K_values expects %d" % (f.shape[1], cin))
-    x3 = KP_X3 and (num_kp * cin) % 32 == 0 and cout % 16 == 0
-    Wp = packed_kpconv_weights_x3(K_values) if x3 else packed_kpconv_weights(K_values)
-    Nq, Ns, K = q.shape[0], s.shape[0], idx.shape[1]
-    dev = q.device
-    out = torch.empty((Nq, cout), dtype=f.dtype, device=dev)
-    row_pos = torch.empty((max(Ns, 1),), dtype=torch.uint8, device=dev)
-    ldr = 0
-    if residual is not None:
-        residual, ldr = _rows(_req(residual, torch.float32, "residual"), "residual")
-    st = _stream(dev)
-    nq_dev, ns_dev = _nd(query_points), _nd(support_points)
-    if ns_dev is None:
-        ns_dev = _nd(features)
-    _lib.check(lib.d3f_row_positive(f.data_ptr(), Ns, ldf, cin, row_pos.data_ptr(), ns_dev, _h(f), st), "row_positive")
-    with _timed("kpconv_fused", dict(Nq=Nq, Ns=Ns, K=K, Cin=cin, Cout=cout), dev):
-        rc = (lib.d3f_kpconv_fused_x3 if x3 else lib.d3f_kpconv_fused)(
-                                  q.data_ptr(), Nq, s.data_ptr(), Ns, idx.data_ptr(), ld_idx, K, f.data_ptr(), ldf, cin,
-                                  row_pos.data_ptr(), kp.ctypes.data, num_kp, float(KP_extent), _INFLUENCE[KP_influence],
-                                  _AGGREGATION[aggregation_mode], Wp.data_ptr(), cout,
-                                  col_scale.data_ptr() if col_scale is not None else None,
-                                  col_shift.data_ptr() if col_shift is not None else None,
-                                  residual.data_ptr() if residual is not None else None, ldr, 1 if leaky else 0,
-                                  float(alpha), out.data_ptr(), cout, nq_dev, ns_dev, _order(query_points), _h(f), st)
-    _lib.check(rc, "kpconv_fused")
-    return _tag(out, query_points)
+    return _kpconv_fused("kpconv_fused", query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent,
+                         KP_influence, aggregation_mode, col_scale, col_shift, residual, leaky, alpha)
 
 
 def kpconv_fused_c1(query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent,
@@ -1015,30 +888,16 @@ def kpconv_fused_c1(query_points, support_points, neighbors_indices, features, K
                     leaky=False, alpha=0.2):
     """Whole KPConv (+ epilogue) for Cin = 1 in one kernel.  K_values f32[num_kp, 1, Cout]."""
     lib = _lib.load()
-    q = _req(query_points, torch.float32, "query_points", 2).contiguous()
-    s = _req(support_points, torch.float32, "support_points", 2).contiguous()
-    idx, ld_idx = _rows(_req(neighbors_indices, torch.int32, "neighbors_indices"), "neighbors_indices")
-    f, ldf = _rows(_req(features, torch.float32, "features"), "features")
-    kp = _kp_host(K_points)
     num_kp, cin, cout = K_values.shape
-    if cin != 1 or f.shape[1] != 1:
+    if cin != 1:
         raise ValueError("kpconv_fused_c1 needs Cin == 1")
+    gather, kpar, _, epi, tail, f = _kp_front("kpconv_fused_c1", query_points, support_points, neighbors_indices, features, K_points,
+                                              K_values, KP_extent, KP_influence, aggregation_mode, col_scale, col_shift, residual,
+                                              leaky, alpha, row_pos=False, feat=lambda t, name: _req(t, torch.float32, name))
     W = _req(K_values, torch.float32, "K_values").reshape(num_kp, cout).contiguous()
-    Nq, Ns, K = q.shape[0], s.shape[0], idx.shape[1]
-    dev = q.device
-    out = torch.empty((Nq, cout), dtype=torch.bfloat16 if BF16_FEATURES else torch.float32, device=dev)
-    ldr = 0
-    if residual is not None:
-        residual, ldr = _rows(_req(residual, torch.float32, "residual"), "residual")
-    with _timed("kpconv_fused_c1", dict(Nq=Nq, Ns=Ns, K=K, Cin=1, Cout=cout), dev):
-        rc = lib.d3f_kpconv_fused_c1(q.data_ptr(), Nq, s.data_ptr(), Ns, idx.data_ptr(), ld_idx, K, f.data_ptr(), ldf,
-                                     kp.ctypes.data, num_kp, float(KP_extent), _INFLUENCE[KP_influence],
-                                     _AGGREGATION[aggregation_mode], W.data_ptr(), cout,
-                                     col_scale.data_ptr() if col_scale is not None else None,
-                                     col_shift.data_ptr() if col_shift is not None else None,
-                                     residual.data_ptr() if residual is not None else None, ldr, 1 if leaky else 0,
-                                     float(alpha), out.data_ptr(), cout, _nd(query_points), _nd(support_points),
-                                     _order(query_points), _h(out), _stream(dev))
+    out = torch.empty((gather[1], cout), dtype=torch.bfloat16 if BF16_FEATURES else torch.float32, device=f.device)
+    with _timed("kpconv_fused_c1", dict(Nq=gather[1], Ns=gather[3], K=gather[6], Cin=1, Cout=cout), f.device):
+        rc = lib.d3f_kpconv_fused_c1(*map(_arg, (*gather, *kpar, W, cout, *epi, out, cout, *tail, _h(out), _stream(f.device))))
     _lib.check(rc, "kpconv_fused_c1")
     return _tag(out, query_points)
 
@@ -1071,7 +930,7 @@ def closest_pool_cat(x, inds, skip=None):
             raise ValueError("closest_pool_cat: %d index rows, %d skip rows" % (inds.shape[0], skip.shape[0]))
     out = torch.empty((inds.shape[0], C1 + C2), dtype=torch.float32, device=dev)
     rc = lib.d3f_closest_pool_cat(x.data_ptr(), x.shape[0], ldx, C1, inds.data_ptr(), inds.shape[0], ldi,
-                                  skip.data_ptr() if skip is not None else None, lds, C2, out.data_ptr(), C1 + C2,
+                                  _ptr(skip), lds, C2, out.data_ptr(), C1 + C2,
                                   _nd(x), _nd(inds), _stream(dev))
     _lib.check(rc, "closest_pool_cat")
     return _tag(out, inds)
@@ -1092,7 +951,7 @@ def detect_head(x, neighbors, stack_lengths_dev, include_zero_dev, stack_group=0
     with _timed("detect_head", dict(N=N, K=nb.shape[1], C=Cc), dev):
         rc = lib.d3f_detect_head(x.data_ptr(), N, ldx, Cc, nb.data_ptr(), ldi, nb.shape[1],
                                  stack_lengths_dev.data_ptr(),
-                                 include_zero_dev.data_ptr() if include_zero_dev is not None else None,
+                                 _ptr(include_zero_dev),
                                  int(stack_group), B, desc.data_ptr(), Cc, score.data_ptr(), scratch.data_ptr(), _order(nb),
                                  _stream(dev))
     _lib.check(rc, "detect_head")
@@ -1163,10 +1022,10 @@ def pack_descriptors(xyz, desc, score, lens=None, group=1, keep=0, dst=None, row
         if row_map is not None:
             assert row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() >= N
         rc = lib.d3f_pack_descriptors_to(xyz.data_ptr(), desc.data_ptr(), ldd, Cc, score.data_ptr(), N, out.data_ptr(), Cc + 4,
-                                         _nd(xyz) or _nd(desc), lens.data_ptr() if lens is not None else None,
+                                         _nd(xyz) or _nd(desc), _ptr(lens),
                                          lens.numel() if lens is not None else 0, int(group), int(keep),
-                                         dst.data_ptr() if dst is not None else None,
-                                         row_map.data_ptr() if row_map is not None else None, _stream(desc.device))
+                                         _ptr(dst),
+                                         _ptr(row_map), _stream(desc.device))
     else:
         rc = lib.d3f_pack_descriptors(xyz.data_ptr(), desc.data_ptr(), ldd, Cc, score.data_ptr(), N, out.data_ptr(), Cc + 4,
                                       _nd(xyz) or _nd(desc), _stream(desc.device))
@@ -1183,9 +1042,9 @@ def affine_act(x, col_scale=None, col_shift=None, residual=None, leaky=False, al
     if residual is not None:
         residual, ldr = _rows(_req(residual, torch.float32, "residual"), "residual")
     out = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    rc = lib.d3f_affine_act(x.data_ptr(), ldx, M, N, col_scale.data_ptr() if col_scale is not None else None,
-                            col_shift.data_ptr() if col_shift is not None else None,
-                            residual.data_ptr() if residual is not None else None, ldr, 1 if leaky else 0, float(alpha),
+    rc = lib.d3f_affine_act(x.data_ptr(), ldx, M, N, _ptr(col_scale),
+                            _ptr(col_shift),
+                            _ptr(residual), ldr, 1 if leaky else 0, float(alpha),
                             out.data_ptr(), N, _nd(x), _stream(x.device))
     _lib.check(rc, "affine_act")
     return _tag(out, x)

@@ -299,3 +299,77 @@ def test_bench_dump_outputs_are_the_last_steps_records(tmp_path):
     assert all(a.dtype == np.float32 for a in got.values())
     assert np.array_equal(got["points"], want[:, :3]) and np.array_equal(got["descriptors"], want[:, 3:35])
     assert np.array_equal(got["scores"], want[:, 35:36])
+
+
+# Level row counts of the order of a 3DMatch benchmark step and of a KITTI two-sweep stack (the routes depend on them only through
+# the 65536-row threshold of the resident-W form and the X3_MAX_ROWS limit).
+_L3DM = (234956, 58320, 14528, 3620, 900)
+_LKITTI = (40000, 11000, 3000, 800, 200)
+
+
+def _model_contractions(L):
+    """Every contraction of the shipped architecture (3DMatch and KITTI models alike): (what, rows, N, C1, C2, plain).
+    plain: A @ W; else gathered (decoder: nearest upsampling | skip) or concatenated (conv3 | shortcut) operands."""
+    out = []
+    for l, fdim in enumerate((64, 128, 256, 512, 1024)):
+        cin = 64 if l == 0 else fdim
+        out += [("L%d resnetb conv1" % l, L[l], fdim // 2, cin, 0, True),
+                ("L%d resnetb conv3 | shortcut" % l, L[l], 2 * fdim, fdim // 2, cin, False)]
+        if l == 3:
+            out.append(("L3 KPConv Cin 256 contraction", L[3], 256, 15 * 256, 0, True))
+        if l < 4:
+            out += [("L%d strided conv1" % l, L[l], fdim // 2, 2 * fdim, 0, True),
+                    ("L%d strided conv3 (+ residual)" % l, L[l + 1], 2 * fdim, fdim // 2, 0, True)]
+        if l == 3:
+            out.append(("L3 strided KPConv Cin 256 contraction", L[4], 256, 15 * 256, 0, True))
+    out.append(("L4 KPConv Cin 512 contraction", L[4], 512, 15 * 512, 0, True))
+    for l, (c1, c2, n) in enumerate(((128, 128, 64), (256, 256, 128), (512, 512, 256), (2048, 1024, 512))):
+        out.append(("uplayer %d upsample | skip" % l, L[l], n, c1, c2, False))
+    out.append(("last_unary", L[0], 32, 64, 0, True))
+    return out
+
+
+# expected (entry point, record name) of the fp32 network, as the parent of the router commit routed them
+_X3, _X3R, _F32T = ("d3f_gemm_x3", "gemm_x3"), ("d3f_gemm_x3", "gemm_x3r"), ("d3f_gemm_f32t", "gemm_f32")
+_WANT_3DM = {"L0 resnetb conv1": _X3R, "L0 resnetb conv3 | shortcut": _X3R, "L0 strided conv1": _X3R, "uplayer 0 upsample | skip": _X3R,
+             "last_unary": _X3R}
+_WANT_KITTI = {"L0 resnetb conv1": _F32T, "L0 strided conv1": _F32T, "last_unary": _F32T}
+
+
+def _decide(ops, rows, N, C1, C2, plain, bf16, bf16_ok, f32t_ok):
+    """The decision ops._contract makes for a call of `rows` rows (no row hint)."""
+    return ops._route(rows, plain, bf16, bf16_ok, f32t_ok, ops._x3_ok(C1, C2, N, rows), ops._x3_resident(rows, N, C1 + C2, 0))
+
+
+@pytest.mark.parametrize("model,L,want", [("3DMatch", _L3DM, _WANT_3DM), ("KITTI", _LKITTI, _WANT_KITTI)])
+def test_contraction_routes_of_the_shipped_models(model, L, want):
+    """The router's decision on every contraction of the network: fp32 (d3f_gemm_x3, its resident-W form from 65536 rows on, the fp32 MFMA
+    kernel for the 32-column layers below that) and bf16 (configs[4]: d3f_gemm_bf16 throughout)."""
+    from d3feat_amd import ops
+    for what, rows, N, C1, C2, plain in _model_contractions(L):
+        assert ops.GEMM_X3
+        assert _decide(ops, rows, N, C1, C2, plain, False, True, True) == want.get(what, _X3), (model, what)
+        assert _decide(ops, rows, N, C1, C2, plain, True, True, True) == ("d3f_gemm_bf16", "gemm_bf16"), (model, what)
+        # no shipped contraction is a 32-column one of >= 65536 rows whose pre-split W misses the LDS budget (K > 512)
+        assert not (N <= 32 and rows >= 65536 and C1 + C2 > 512)
+
+
+@pytest.mark.parametrize("rows,N,C1,C2,plain,bf16,bf16_ok,f32t_ok,x3,want", [
+    (5000, 64, 64, 0, True, False, False, False, True, ("d3f_gemm_f32", "gemm_f32")),             # A not addressable by LDS-DMA
+    (5000, 64, 64, 62, False, False, False, False, True, ("d3f_gemm_upsample_cat_f32", "gemm_f32")),  # misaligned second operand
+    (5000, 64, 64, 62, False, True, False, False, True, ("d3f_gemm_upsample_cat_f32", "gemm_f32")),   # ... under bf16 as well
+    (5000, 64, 48, 0, True, False, False, True, True, _F32T),                                        # K not a multiple of 32
+    (5000, 64, 16, 48, False, False, False, True, True, _F32T),                                      # first part not one either
+    (50000, 32, 64, 0, True, False, True, True, True, _F32T),                                        # N = 32 below 65536 rows
+    (100000, 32, 64, 0, True, False, True, True, True, _X3R),                                        # ... and above
+    (100000, 32, 544, 0, True, False, True, True, True, _F32T),                                      # ... W beyond the LDS budget
+    (65535 * 128 + 1, 64, 64, 0, True, False, True, True, True, _F32T),                              # more than X3_MAX_ROWS
+    (5000, 64, 64, 0, True, False, True, True, False, _F32T),                                        # D3F_GEMM_X3=0
+    (5000, 64, 64, 0, True, True, True, True, True, ("d3f_gemm_bf16", "gemm_bf16")),                 # bf16 on
+    (5000, 64, 64, 0, True, True, False, True, True, _X3),                                           # bf16 on, not addressable
+    (5000, 64, 64, 0, True, False, True, True, True, _X3),                                           # bf16 off
+])
+def test_contraction_route_fallbacks(monkeypatch, rows, N, C1, C2, plain, bf16, bf16_ok, f32t_ok, x3, want):
+    from d3feat_amd import ops
+    monkeypatch.setattr(ops, "GEMM_X3", x3)
+    assert _decide(ops, rows, N, C1, C2, plain, bf16, bf16_ok, f32t_ok) == want
