@@ -249,28 +249,44 @@ class FragmentEngine:
         return sl
 
     # ---- per-fragment API -------------------------------------------------------------------------------------------
+    def kept_rows_cap(self):
+        """The most rows a submit(out=...) destination can receive from one fragment under this engine's capacities: the fragment's
+        `keep_clouds` kept clouds hold at most n0_cap voxels each (stage 0 reports an EMPTY result for a cloud beyond it; without
+        stage 0 a cloud beyond n0_cap never reaches a replay), and the stack of a replay F * n0_cap voxels in all -- which is what
+        bounds the pair of a two_clouds engine at batch 1."""
+        return self.n0_cap * min(self.keep_clouds, self.F)
+
     def submit(self, slot, raw, out=None):
         """Start a replay on slot `slot`; returns immediately.  `raw`: one fragment (float32 [n,3] on the device or the host;
         a pair (raw_a, raw_b) with two_clouds), or -- batch > 1 -- a list of up to `batch` fragments.
-        out (with fetch(packed=True)): one destination per fragment, a contiguous f32[rows >= its kept rows, 36] device tensor -- the
+        out (with fetch(packed=True)): one destination per fragment, a contiguous f32[rows >= kept_rows_cap(), 36] device tensor (fewer
+        rows: ValueError, nothing is launched and the slot stays free) -- the
         [xyz | desc | score] records of the fragment's kept clouds (the first cloud of a stacked self-pair; both of two different
         clouds) are written THERE by the replay's last kernel and fetch returns a view of it: no copy into the caller's shard."""
         sl = self.slots[slot]
         assert not sl.busy, "slot %d still holds an unfetched fragment" % slot
-        if sl.cap != self.neighbor_cap:
-            # the ordering budget was raised after repeated overflows: re-capture this slot once, on its own stream
-            sl = self.slots[slot] = self._build_slot(sl.stream)
         single = not isinstance(raw, list)
         frags = [raw] if single else list(raw)
         if not 1 <= len(frags) <= self.F:
             raise ValueError("submit: %d fragments for a batch-%d engine" % (len(frags), self.F))
-        sl.single, sl.raw_src, sl.nfrag = single, frags, len(frags)
-        sl.busy = True
         outs = None
         if out is not None and not self.mirror:
             outs = [out] if (single and isinstance(out, torch.Tensor)) else list(out)
             assert len(outs) == len(frags) and all(o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() and o.dim() == 2
                                                    and o.shape[1] == 36 for o in outs)
+            # The replay's last kernel writes a fragment's kept rows to the raw address, so a destination must hold the MOST rows
+            # the capacities allow, whatever this fragment turns out to need.  Checked before the slot is touched or any GPU work
+            # is issued: the slot stays free.
+            need = self.kept_rows_cap()
+            short = [int(o.shape[0]) for o in outs if int(o.shape[0]) < need]
+            if short:
+                raise ValueError("submit: a destination of %d rows, but a fragment of this engine can keep up to %d rows "
+                                 "(n0_cap %d)" % (min(short), need, self.n0_cap))
+        if sl.cap != self.neighbor_cap:
+            # the ordering budget was raised after repeated overflows: re-capture this slot once, on its own stream
+            sl = self.slots[slot] = self._build_slot(sl.stream)
+        sl.single, sl.raw_src, sl.nfrag = single, frags, len(frags)
+        sl.busy = True
         sl.out_dst = outs
         sl.out_given = outs is not None
         parts = []

@@ -281,6 +281,48 @@ def detection_head(features, neighbor, in_batches, stack_lengths):
     return score[:-1]                                                                    # :115
 
 
+def include_zero_rule(stack_lengths, group=0):
+    """datasets/common.py:453-496 per cloud: does the cloud's row of in_batches hold the shadow index?  Yes iff the cloud is shorter
+    than the longest one of its stack, or all clouds of the stack are equally long (the extra pad column).  group > 0: the B clouds
+    are a concatenation of independent stacks of `group` consecutive clouds each; 0: one stack."""
+    lens = [int(l) for l in stack_lengths]
+    g = int(group) if int(group) > 0 else len(lens)
+    inc = []
+    for b, l in enumerate(lens):
+        grp = lens[b // g * g: b // g * g + g]
+        inc.append(1 if (l < max(grp) or all(v == max(grp) for v in grp)) else 0)
+    return inc
+
+
+def detection_head_f64(features, neighbor, stack_lengths, group=0, include_zero=None):
+    """models/D3Feat.py:65-115 in plain float64 numpy, generalised from the reference's two clouds to B clouds, stacks of `group`
+    clouds and an explicit include-zero vector (None: include_zero_rule).  Rows beyond sum(stack_lengths) are ignored; a neighbour
+    index outside [0, sum(stack_lengths)) is the shadow (zero) row.  -> (desc [n, C], score [n], y [n, C]): y is the normalised
+    feature matrix of :90, whose row sums decide which neighbours are counted (:94-96)."""
+    lens = [int(l) for l in stack_lengths]
+    n = sum(lens)
+    x = np.asarray(features, np.float64)[:n]
+    C = x.shape[1]
+    inc = include_zero_rule(lens, group) if include_zero is None else [int(v) for v in include_zero]
+    y = np.empty_like(x)
+    a = 0
+    for l, z in zip(lens, inc):
+        if l:
+            m = x[a:a + l].max()                                  # :84-85 (the zero row takes part iff in_batches holds the shadow)
+            y[a:a + l] = x[a:a + l] / ((max(m, 0.0) if z else m) + 1e-6)   # :90
+        a += l
+    nb = np.asarray(neighbor, np.int64)[:n]
+    nb = np.where((nb < 0) | (nb >= n), n, nb)
+    nf = np.concatenate([y, np.zeros((1, C))], 0)[nb]            # :77-78, :93   [n, K, C]
+    num = np.maximum((nf.sum(-1) != 0).sum(-1), 1)                # :94-96
+    mean = nf.sum(1) / num[:, None]                               # :97
+    alpha = np.logaddexp(0.0, y - mean)                           # :98  softplus
+    beta = y / (1e-6 + y.max(1, keepdims=True))                   # :101-102
+    score = (alpha * beta).max(1)                                 # :104-106
+    desc = x / np.sqrt(np.maximum((x * x).sum(1, keepdims=True), 1e-10))   # :65
+    return desc, score, y
+
+
 # --------------------------------------------------------------------------------------------------
 # datasets/common.py
 # --------------------------------------------------------------------------------------------------

@@ -431,3 +431,32 @@ def test_records_written_in_place_equal_the_copied_ones(device, setup):
     ep, ed, es = eng.run_eager(big)
     rec = ops.pack_descriptors(ep, ed, es)
     assert torch.equal(got[1], rec[: rec.shape[0] // 2])
+
+
+def test_submit_rejects_a_destination_that_is_too_small(device, setup):
+    """FragmentEngine.submit(out=...): the replay's last kernel writes a fragment's kept rows to the raw address, so a destination
+    with fewer rows than the engine's capacities allow a fragment to keep (kept_rows_cap(): n0_cap for the first cloud of a stacked
+    self-pair) is refused with ValueError BEFORE any GPU work -- one row short is enough, whatever the fragment would need.  The
+    slot stays free, the destinations untouched, and the same slot then runs the same fragments into full-size destinations."""
+    from d3feat_amd.engine import FragmentEngine
+    cfg, W, limits = setup
+    raws = [torch.from_numpy(_frag(s, n)).to(device) for s, n in ((31, 30000), (32, 26000))]
+    eng = FragmentEngine(cfg, W, limits, raw_cap=40000, n0_cap=10000, slots=1, device=device, batch=2)
+    need = eng.kept_rows_cap()
+    assert need == 10000
+    good = [torch.full((need, 36), -7.0, device=device) for _ in range(2)]
+    short = torch.full((need - 1, 36), -7.0, device=device)
+    for frags, outs in ((raws, [good[0], short]), (raws, [short, good[1]]), (raws[0], short)):
+        with pytest.raises(ValueError):
+            eng.submit(0, frags, out=outs)
+        assert not eng.slots[0].busy
+    torch.cuda.synchronize(device)
+    assert all(bool((t == -7.0).all()) for t in good + [short])
+    eng.submit(0, raws)
+    want = [r.clone() for r in eng.fetch(0, packed=True)]
+    eng.submit(0, raws, out=good)
+    got = eng.fetch(0, packed=True)
+    assert eng.fallbacks == 0
+    for w, g, d in zip(want, got, good):
+        half = w.shape[0] // 2
+        assert g.data_ptr() == d.data_ptr() and torch.equal(g, w[:half]) and bool((d[half:] == -7.0).all())

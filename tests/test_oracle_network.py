@@ -81,6 +81,44 @@ def test_detection_head_restatement_vs_scalar_loops(coracle):
     assert np.abs(got - want).max() <= 1e-5 * max(1.0, np.abs(want).max())
 
 
+# two-cloud stacks for the float64 head reference: (C, K, lens, all-negative clouds, include-zero vector or None = length rule)
+HEAD_F64_CASES = [(32, 33, (60, 60), (), None), (32, 35, (70, 45), (), None), (20, 7, (45, 70), (), None),
+                  (64, 40, (50, 50), (), None), (128, 33, (40, 64), (), None), (1, 16, (30, 50), (), None),
+                  (32, 30, (60, 60), (0, 1), None), (32, 30, (70, 45), (1,), None), (32, 30, (70, 45), (0,), None),
+                  (33, 17, (70, 45), (0,), (1, 0)), (32, 0, (20, 30), (), None)]
+HEAD_F64_MEASURED = 2.79e-7     # largest difference over the cases above on the CPU (scores 7.6e-8 .. 2.8e-7 per case; the descriptors differ by less)
+HEAD_F64_BOUND = 2 * HEAD_F64_MEASURED
+
+
+def test_detection_head_f64_generalisation_vs_oracle():
+    """onp.detection_head_f64 (B clouds, stack groups, explicit include-zero: the reference of tests/test_gpu_pool_head.py) restates
+    the same lines as onp.detection_head, which is pinned to the reference's Python: on two-cloud stacks (equal / unequal lengths,
+    all-negative clouds whose padded maximum is the zero row, shadow slots, all-zero and cancelling rows, K = 0) they differ by the
+    float32 rounding of the oracle only.  The bound is twice the largest difference measured here on these inputs, relative to
+    max(1, |want|) (a padded all-negative cloud has scores of order 1e7); it stays far below the 1e-5 descriptor bar."""
+    from oracle import head_cases as hc
+    from oracle import network_np as onp
+    worst = 0.0
+    for i, (C, K, lens, neg, inc) in enumerate(HEAD_F64_CASES):
+        x, nb = hc.head_case(100 + i, C, K, lens, negative=neg)
+        assert hc.neighbours_stay_in_cloud(nb, lens)
+        n = sum(lens)
+        inc_v = onp.include_zero_rule(lens) if inc is None else list(inc)
+        in_b = onp.stack_batch_inds(lens) if inc is None else hc.in_batches(lens, inc_v)
+        nb_t = np.where((nb < 0) | (nb >= n), n, nb)
+        got = onp.detection_head(torch.from_numpy(x), nb_t, in_b, np.asarray(lens)).numpy()[:, 0].astype(np.float64)
+        desc, want, _ = onp.detection_head_f64(x, nb, lens, 0, inc)
+        assert [int(n in set(in_b[b].tolist())) for b in range(2)] == inc_v
+        rel = np.abs(got - want).max() / max(1.0, np.abs(want).max())
+        print("head f64 vs oracle: C %d K %d lens %s neg %s inc %s: %.3e (|want| max %.3g)" % (C, K, lens, neg, inc, rel, np.abs(want).max()))
+        worst = max(worst, rel)
+        sq = (torch.from_numpy(x) ** 2).sum(1, keepdim=True)
+        d32 = (torch.from_numpy(x) * torch.rsqrt(torch.clamp(sq, min=1e-10))).numpy()     # onp.forward's descriptor line
+        worst = max(worst, np.abs(d32 - desc).max())
+    print("largest: %.3e" % worst)
+    assert worst <= HEAD_F64_BOUND < 1e-5
+
+
 def test_pools_restatement():
     from oracle import network_np as onp
     x = torch.tensor([[1., -5.], [3., 2.], [-2., 7.]])
