@@ -17,35 +17,27 @@
 //     has finished reading tile t - 1) -> issue tile t + STAGES - 1 into the slot tile t - 1 occupied -> fragments + MFMAs of
 //     tile t.
 // Same k-permuted fragments (lane (r, h) owns k = 16 h .. 16 h + 15 of its row: four ds_read_b128 per operand and k-tile), same
-// transposed accumulators / epilogue as gemm_fast_kernel.
+// transposed accumulators / epilogue as gemm_fast_kernel (the k-tile step is gemm_common.h's gemm_tile_mfma).
 #pragma once
+#include "gemm_common.h"
 
 #define GD_BK 32
+#define GD_STAGES 3
 __device__ __attribute__((aligned(128))) float gd_zero_line[32];     // zero-initialised device global
 
 typedef const __attribute__((address_space(1))) void* gd_gptr;
 typedef __attribute__((address_space(3))) void* gd_lptr;
 
+// hand-counted wait: at most N_ of this wavefront's vector memory operations outstanding (0, or the P = 4 / 5 pieces of one tile)
 template <int N_> __device__ __forceinline__ void gd_wait_vm() {
     if constexpr (N_ == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N_ == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if constexpr (N_ == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
     else if constexpr (N_ == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     else if constexpr (N_ == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (N_ == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (N_ == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N_ == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-    else if constexpr (N_ == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    else if constexpr (N_ == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if constexpr (N_ == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N_ == 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-    else if constexpr (N_ == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if constexpr (N_ == 15) asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
     else static_assert(N_ < 0, "add the count");
 }
 
-// WM x WN wavefronts, TM x TN 32 x 32 accumulator tiles each (independent MFMA chains; an A / B fragment feeds TN / TM MFMAs),
-// STAGES k-tiles of LDS; EPI bit 0: per-row scale, bit 1: residual operand.
+// WM x WN wavefronts (WM * WN == 4), one 32 x 32 accumulator tile each, GD_STAGES k-tiles of LDS; EPI bit 0: per-row scale,
+// bit 1: residual operand.
 //
 // PERSISTENT over work items.  An item = (row block, K slice, column tile); the grid holds G workgroups (G a multiple of 8, at most
 // what is resident at once), workgroup w takes the items w, w + G, w + 2 G, ... of the XCD-aware item order (common.h:
@@ -55,12 +47,13 @@ template <int N_> __device__ __forceinline__ void gd_wait_vm() {
 // first load (one full memory round trip with nothing to overlap it) and a store tail each time: ~30 % of its life at the
 // network's shapes (the bare LDS + MFMA loop runs at 0.90 of the matrix peak in isolation, tools/ubench/mfma_rate.hip, and reached
 // 0.70 inside such workgroups: profiles/r03_experiments.txt x9).
-template <int WM, int WN, int TM, int TN, int STAGES, int EPI>
+template <int WM, int WN, int EPI>
 __global__ void __launch_bounds__(256)
 gemm_dma_kernel(const float* __restrict__ A, int lda, const float* __restrict__ Wt, int Kp, float* __restrict__ C, int ldc,
                 int M, int N, int K, int tiles_per_split, int S, float* __restrict__ slab, GemmEpi E,
                 const int* __restrict__ M_dev, GemmGather G) {
-    constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN, ROWS_T = BM + BN;
+    constexpr int STAGES = GD_STAGES;
+    constexpr int BM = 32 * WM, BN = 32 * WN, ROWS_T = BM + BN;
     constexpr int P = ROWS_T / 32;                 // DMA pieces per thread and stage (256 threads x 16 B = 32 rows per piece)
     constexpr int PA = BM / 32;                    // the first PA pieces are A rows, the rest weight rows
     constexpr int SF = ROWS_T * GD_BK;             // floats per stage
@@ -162,7 +155,7 @@ gemm_dma_kernel(const float* __restrict__ A, int lda, const float* __restrict__ 
 
     // fragment read offsets (floats, inside a stage): row R, chunk (4 h + q) ^ ((R >> 1) & 7)
     const int fr = lane & 31, fh = lane >> 5, fsw = (fr >> 1) & 7;
-    const int arow_off = (wm * TM * 32 + fr) * GD_BK, brow_off = (BM + wn * TN * 32 + fr) * GD_BK;
+    const int arow_off = (wm * 32 + fr) * GD_BK, brow_off = (BM + wn * 32 + fr) * GD_BK;
     int coff[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) coff[q] = (((4 * fh + q) ^ fsw) << 2);
@@ -178,13 +171,9 @@ gemm_dma_kernel(const float* __restrict__ A, int lda, const float* __restrict__ 
         const int t_begin = by * tiles_per_split;
         const int nt = min(nt_all, t_begin + tiles_per_split) - t_begin;
 
-        f32x16 acc[TM][TN];
+        f32x16 acc;
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+        for (int q = 0; q < 16; ++q) acc[q] = 0.f;
 
         for (int i = 0; i < nt; ++i) {
             // `ahead` tiles are in flight and the oldest is the one multiplied now; the newer ones may stay outstanding --
@@ -195,37 +184,11 @@ gemm_dma_kernel(const float* __restrict__ A, int lda, const float* __restrict__ 
             __builtin_amdgcn_s_barrier();
             --ahead;
             issue_next();
-            const float* as = gd_smem + slot * SF + arow_off;
-            const float* bs = gd_smem + slot * SF + brow_off;
-            float4 fa[TM][4], fb[TN][4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-#pragma unroll
-                for (int ii = 0; ii < TM; ++ii) fa[ii][q] = *(const float4*)&as[ii * 32 * GD_BK + coff[q]];
-#pragma unroll
-                for (int j = 0; j < TN; ++j) fb[j][q] = *(const float4*)&bs[j * 32 * GD_BK + coff[q]];
-            }
-            __builtin_amdgcn_sched_barrier(0);        // every fragment read is issued before the first MFMA waits on one
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int ii = 0; ii < TM; ++ii) {
-                        const float a = e == 0 ? fa[ii][q].x : e == 1 ? fa[ii][q].y : e == 2 ? fa[ii][q].z : fa[ii][q].w;
-#pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            const float b = e == 0 ? fb[j][q].x : e == 1 ? fb[j][q].y : e == 2 ? fb[j][q].z : fb[j][q].w;
-                            // operands swapped: the accumulator holds the TRANSPOSED tile (a lane owns one output row, four
-                            // consecutive columns per register quad -> 16-byte stores)
-                            acc[ii][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b, a, acc[ii][j], 0, 0, 0);
-                        }
-                    }
-                }
-            }
+            gemm_tile_mfma(acc, gd_smem + slot * SF + arow_off, gd_smem + slot * SF + brow_off, coff[0], coff[1], coff[2], coff[3]);
             slot = slot + 1 == STAGES ? 0 : slot + 1;
         }
 
+        constexpr int TM = 1, TN = 1;              // one-trip loops: see gemm_fast_kernel's epilogue
         // ---- epilogue of the item: as gemm_fast_kernel's (per-column terms up front, no load between two stores).  Its ordinary
         // loads make hipcc wait for vmcnt(0), i.e. also for the next item's first tiles, which are needed one step later anyway.
         float4 cs4[TN][4], ch4[TN][4];
@@ -258,7 +221,7 @@ gemm_dma_kernel(const float* __restrict__ A, int lda, const float* __restrict__ 
                 for (int q = 0; q < 4; ++q) {
                     float v[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e];
+                    for (int e = 0; e < 4; ++e) v[e] = acc[4 * q + e];
                     if (!slab) {
                         const float c[4] = {cs4[j][q].x, cs4[j][q].y, cs4[j][q].z, cs4[j][q].w};
                         const float h4[4] = {ch4[j][q].x, ch4[j][q].y, ch4[j][q].z, ch4[j][q].w};

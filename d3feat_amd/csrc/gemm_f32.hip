@@ -6,65 +6,36 @@
 // the resnet blocks (:368, :612):
 //   C[m,n] = act( acc[m,n] * row_scale[m] * col_scale[n] + col_shift[n] + residual[m,n] ),  acc = A @ B
 //
-// v_mfma_f32_32x32x2_f32 (f32 in / f32 accumulate, 64 cycles per SIMD, exact fp32 products and sums) -- the 1e-4 parity bar
-// is an fp32 bar, so the contraction stays in fp32 on the MFMA pipe (157 TF peak).
-// Two kernels, one launcher (gemm_run):
-//   gemm_fast_kernel    the production tile kernel for float4-addressable operands (every shape of the network): 256-thread
-//                       workgroup = 4 wavefronts x (TM x TN) 32x32 accumulator tiles, BK = 32, double-buffered LDS, k-permuted
-//                       fragments read with ds_read_b128, transposed accumulators -> 16-byte stores, straight-line staging;
-//                       workgroup tile 64x64 (default) or 128x32 (Cout <= 32).  Measured and removed again: 128x64 / 128x128 register
-//                       tiles (slower on every shape of the network: tails), a streaming form for many rows x shallow K (B slab
-//                       resident in LDS, A global -> registers: equal end to end), a second prefetch register set (round 3);
-//   gemm_f32_kernel     generic fallback (odd K / N / leading dimensions, unaligned bases): scalar tail handling.
-// Skinny problems (few output tiles, long K: the deep KPConv layers) are split along K into slabs that a second kernel
-// reduces in a fixed order (deterministic).
-#include "common.h"
+// kernel (file)                  entry point                       picked when
+// gemm_x3_kernel (gemm_x3.h)     d3f_gemm_x3                       ops._route: float4-addressable operands, K (and C1 of a
+//                                                                  concatenation) multiples of 32, N > 32: most of the network
+// gemm_x3r_kernel (gemm_x3.h)    d3f_gemm_x3                       inside it, when d3f_gemm_x3_resident: tall, W fits the LDS
+// gemm_dma_kernel (gemm_dma.h)   d3f_gemm_f32t                     ops._route: float4-addressable operands that x3 does not
+//                                                                  take (D3F_GEMM_X3=0, K % 32, 32-column layers, row cap)
+// gemm_fast_kernel (here)        d3f_gemm_f32,                     gemm_run: float4-addressable operands.  ops._route calls these
+//                                d3f_gemm_upsample_cat_f32         entries only when d3f_gemm_f32t cannot address the call, so
+//                                                                  from Python this is a weight view with ldb != N; it is what
+//                                                                  a direct caller of the C ABI gets for aligned operands
+// gemm_f32_kernel (here)         the same two                      gemm_run: anything else (odd K / N / leading dimensions,
+//                                                                  unaligned bases): scalar tail handling
+// gemm_bf16_kernel (here)        d3f_gemm_bf16                     ops._route: ops.bf16_contraction() is on (not fp32 arithmetic)
+// gemm_splitk_reduce_kernel      all of them                       the launcher split K (skinny problems: few output tiles,
+//   (gemm_common.h)                                                long K): slabs reduced in a fixed order (deterministic)
+//
+// The fp32 kernels multiply with v_mfma_f32_32x32x2_f32 (f32 in / f32 accumulate, 64 cycles per SIMD, exact fp32 products and
+// sums): the 1e-4 parity bar is an fp32 bar.  The x3 form reaches the same bar on the bf16 pipe by exact operand splitting.
+#include "gemm_common.h"
 #include <cstdio>
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define GM_BK 32
 #define GM_SA (GM_BK + 1)
 
-// Optional composite A operand (decoder of models/D3Feat.py:55-63): A = [ x'[gidx[m, 0]] | A2[m] ] -- the nearest-upsample
-// gather (closest_pool, models/network_blocks.py:69-83: x' = x + zero row) and the skip concatenation feed the unary
-// contraction directly, so the concatenated [N, C1 + C2] tensor is never written to / re-read from HBM.
-struct GemmGather {
-    const int* gidx;      // NULL: A rows are used in place
-    int ld_gidx;
-    int N1;               // rows of A (the gather source); indices outside [0, N1) read the zero row
-    const int* N1_dev;
-    const float* A2;      // NULL: no second operand
-    int lda2;
-    int K1;               // columns taken from A (multiple of 4 when A2 != NULL)
-};
-
-struct GemmEpi {
-    const float* row_scale;
-    const float* col_scale;
-    const float* col_shift;
-    const float* residual;
-    int ldr;
-    int leaky;
-    float alpha;
-};
-
-__device__ __forceinline__ float gemm_epilogue(float v, int m, int n, const GemmEpi& E) {
-    if (E.row_scale) v *= E.row_scale[m];
-    if (E.col_scale) v *= E.col_scale[n];
-    if (E.col_shift) v += E.col_shift[n];
-    if (E.residual) v += E.residual[(size_t)m * E.ldr + n];
-    if (E.leaky) v = v > 0.f ? v : v * E.alpha;
-    return v;
-}
-
-template <int WM, int WN, int TM, int TN>  // waves along M / N (WM*WN == 4); 32x32 MFMA tiles per wave along M / N
+template <int WM, int WN>  // waves along M / N (WM*WN == 4), one 32x32 MFMA tile each
 __global__ void __launch_bounds__(256)
 gemm_f32_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, float* __restrict__ C, int ldc,
                 int M, int N, int K, int vecA, int vecB, int tiles_per_split, float* __restrict__ slab, GemmEpi E,
                 const int* __restrict__ M_dev, GemmGather G) {
-    constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
+    constexpr int BM = 32 * WM, BN = 32 * WN;
     constexpr int A_F4 = BM * GM_BK / 4 / 256;  // float4 loads per thread for the A tile
     constexpr int B_F4 = GM_BK * BN / 4 / 256;  // ... for the B tile (>= 1)
     static_assert(WM * WN == 4 && A_F4 >= 1 && B_F4 >= 1, "tile shape");
@@ -168,13 +139,9 @@ gemm_f32_kernel(const float* __restrict__ A, int lda, const float* __restrict__ 
         }
     };
 
-    f32x16 acc[TM][TN];
+    f32x16 acc;
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
     if (t_begin < t_end) {
         load_tile(t_begin);
@@ -182,22 +149,15 @@ gemm_f32_kernel(const float* __restrict__ A, int lda, const float* __restrict__ 
     }
     __syncthreads();
     // A fragment: lane reads column (k + lane/32) of row (lane%32) of its 32-row tile; B fragment: row (k + lane/32), col lane%32
-    const int arow = (wm * TM * 32 + (lane & 31)) * GM_SA + (lane >> 5);
-    const int bcol = (lane >> 5) * BN + wn * TN * 32 + (lane & 31);
+    const int arow = (wm * 32 + (lane & 31)) * GM_SA + (lane >> 5);
+    const int bcol = (lane >> 5) * BN + wn * 32 + (lane & 31);
     int cur = 0;
     for (int t = t_begin; t < t_end; ++t) {
         if (t + 1 < t_end) load_tile(t + 1);   // global -> registers, in flight while this tile is multiplied
 #pragma unroll
         for (int kk = 0; kk < GM_BK / 2; ++kk) {
-            float a[TM], b[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a[i] = As[cur][arow + i * 32 * GM_SA + kk * 2];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b[j] = Bs[cur][bcol + j * 32 + kk * 2 * BN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+            const float a = As[cur][arow + kk * 2], b = Bs[cur][bcol + kk * 2 * BN];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
         }
         if (t + 1 < t_end) store_tile(cur ^ 1);
         __syncthreads();
@@ -205,43 +165,38 @@ gemm_f32_kernel(const float* __restrict__ A, int lda, const float* __restrict__ 
     }
 
     // C/D layout of 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+    const int gn = n0 + wn * 32 + (lane & 31);
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int gn = n0 + (wn * TN + j) * 32 + (lane & 31);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int gm = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (gm < M && gn < N) {
-                    if (slab) slab[((size_t)blockIdx.y * Mcap + gm) * N + gn] = acc[i][j][r];
-                    else C[(size_t)gm * ldc + gn] = gemm_epilogue(acc[i][j][r], gm, gn, E);
-                }
-            }
+    for (int r = 0; r < 16; ++r) {
+        const int gm = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (gm < M && gn < N) {
+            if (slab) slab[((size_t)blockIdx.y * Mcap + gm) * N + gn] = acc[r];
+            else C[(size_t)gm * ldc + gn] = gemm_epilogue(acc[r], gm, gn, E);
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// The production tile kernel: same tiling as gemm_f32_kernel above, written so that the compiler has nothing to serialise.
+// The register-staged tile kernel: same tiling as gemm_f32_kernel above, written so that the compiler has nothing to serialise.
 //  * operands are float4-addressable (K, N, leading dimensions multiples of 4, 16-byte aligned bases: every shape of the
 //    network), so a tile load is straight-line code: clamped address, one global_load_dwordx4, a select to zero -- no
 //    branch between the loads and therefore no s_waitcnt before the multiply they are meant to overlap with;
 //  * the contraction may visit k in any order as long as A and B agree: within a 32-deep tile lane (r, h) owns
 //    k = 16h .. 16h+15, which are CONSECUTIVE in an LDS row, so a wavefront fetches its A and B fragments for the whole
 //    tile with four ds_read_b128 each (B is stored transposed, [n][k]) instead of 32 ds_read_b32 followed by a wait apiece;
-//    the second half of the fragments lands while the first eight MFMAs run.
+//    the second half of the fragments lands while the first eight MFMAs run (gemm_common.h: gemm_tile_mfma, shared with
+//    gemm_dma_kernel).
 // Row stride 36 floats: 16-byte aligned rows, and 36r mod 64 spreads eight consecutive rows over all banks for b128 reads.
 // ------------------------------------------------------------------------------------------------
 #define GF_S 36
 
-// NACC: accumulator chains per MFMA tile; EPI bit 0: per-row scale, bit 1: residual operand
-template <int WM, int WN, int TM, int TN, int NACC, int EPI>
+// WM x WN wavefronts (WM * WN == 4), one 32 x 32 accumulator tile each; EPI bit 0: per-row scale, bit 1: residual operand
+template <int WM, int WN, int EPI>
 __global__ void __launch_bounds__(256)
 gemm_fast_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb, float* __restrict__ C, int ldc,
                  int M, int N, int K, int tiles_per_split, float* __restrict__ slab, GemmEpi E,
                  const int* __restrict__ M_dev, GemmGather G) {
-    constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
+    constexpr int BM = 32 * WM, BN = 32 * WN;
     constexpr int A_F4 = BM * GM_BK / 4 / 256, B_F4 = GM_BK * BN / 4 / 256;
     static_assert(WM * WN == 4 && A_F4 >= 1 && B_F4 >= 1, "tile shape");
     const int Mcap = M;
@@ -332,60 +287,30 @@ gemm_fast_kernel(const float* __restrict__ A, int lda, const float* __restrict__
         }
     };
 
-    f32x16 acc[TM][TN][NACC];
+    f32x16 acc;
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int c = 0; c < NACC; ++c)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][c][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 
     if (t_begin < t_end) {
         load_tile(t_begin);
         store_tile(0);
     }
     __syncthreads();
-    const int afrag = (wm * TM * 32 + (lane & 31)) * GF_S + (lane >> 5) * 16;
-    const int bfrag = (wn * TN * 32 + (lane & 31)) * GF_S + (lane >> 5) * 16;
+    const int afrag = (wm * 32 + (lane & 31)) * GF_S + (lane >> 5) * 16;
+    const int bfrag = (wn * 32 + (lane & 31)) * GF_S + (lane >> 5) * 16;
     int cur = 0;
     for (int t = t_begin; t < t_end; ++t) {
         const bool more = t + 1 < t_end;
         if (more) load_tile(t + 1);               // global -> registers, in flight while this tile is multiplied
-        const float* as = As + cur * BM * GF_S + afrag;
-        const float* bt = Bt + cur * BN * GF_S + bfrag;
-        float4 fa[TM][4], fb[TN][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i][q] = *(const float4*)&as[i * 32 * GF_S + 4 * q];
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j][q] = *(const float4*)&bt[j * 32 * GF_S + 4 * q];
-        }
-        __builtin_amdgcn_sched_barrier(0);        // every fragment read is issued before the first MFMA waits on one
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    const float a = e == 0 ? fa[i][q].x : e == 1 ? fa[i][q].y : e == 2 ? fa[i][q].z : fa[i][q].w;
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const float b = e == 0 ? fb[j][q].x : e == 1 ? fb[j][q].y : e == 2 ? fb[j][q].z : fb[j][q].w;
-                        // operands swapped: the accumulator holds the TRANSPOSED tile, i.e. a lane owns one output row
-                        // and four consecutive columns per register quad -> 16-byte stores in the epilogue
-                        acc[i][j][e % NACC] = __builtin_amdgcn_mfma_f32_32x32x2f32(b, a, acc[i][j][e % NACC], 0, 0, 0);
-                    }
-                }
-            }
-        }
+        gemm_tile_mfma(acc, As + cur * BM * GF_S + afrag, Bt + cur * BN * GF_S + bfrag, 0, 4, 8, 12);
         if (more) store_tile(cur ^ 1);
         __syncthreads();
         cur ^= 1;
     }
-
+    // ---- epilogue.  A wavefront owns TM x TN = 1 x 1 tiles; the one-trip loops over them stay, here and in gemm_dma_kernel's
+    // copy: without them (written out, or as one shared function) the compiler emits different code for all 16 instances,
+    // which measured 1-3 % slower on the 64 x 64 tile.
+    constexpr int TM = 1, TN = 1;
     // Accumulator layout (operands swapped, so D = tile^T): lane l owns output row (l & 31) of its 32-row tile and, in
     // register quad q, the four consecutive columns 8q + 4(l >> 5) .. +3 of the 32-column tile: one global_store_dwordx4 per
     // quad (the store path is issue bound: 4 wide stores per tile instead of 16 dword stores).
@@ -425,8 +350,7 @@ gemm_fast_kernel(const float* __restrict__ A, int lda, const float* __restrict__
                 float v[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    v[e] = acc[i][j][0][4 * q + e];
-                    if (NACC == 2) v[e] += acc[i][j][NACC - 1][4 * q + e];
+                    v[e] = acc[4 * q + e];
                 }
                 if (!slab) {
                     const float c[4] = {cs4[j][q].x, cs4[j][q].y, cs4[j][q].z, cs4[j][q].w};
@@ -455,63 +379,11 @@ gemm_fast_kernel(const float* __restrict__ A, int lda, const float* __restrict__
 
 #include "gemm_dma.h"
 
-// res_bf16 / c_bf16: the residual operand / the output hold bfloat16 values (bf16 feature storage, d3f_gemm_bf16)
-__global__ void __launch_bounds__(256)
-gemm_splitk_reduce_kernel(const float* __restrict__ slab, int S, int M, int N, float* __restrict__ C, int ldc, GemmEpi E,
-                          const int* __restrict__ M_dev, int res_bf16 = 0, int c_bf16 = 0) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)d3f_dyn(M, M_dev) * N) return;
-    const int m = (int)(i / N), n = (int)(i % N);
-    float v = 0.f;
-    for (int s = 0; s < S; ++s) v += slab[((size_t)s * M + m) * N + n];
-    if (res_bf16 && E.residual) {
-        const float r = d3f_bf16_f32(((const unsigned short*)E.residual)[(size_t)m * E.ldr + n]);
-        GemmEpi E2 = E;
-        E2.residual = nullptr;
-        E2.leaky = 0;
-        v = gemm_epilogue(v, m, n, E2) + r;
-        if (E.leaky) v = v > 0.f ? v : v * E.alpha;
-    } else {
-        v = gemm_epilogue(v, m, n, E);
-    }
-    if (c_bf16) ((unsigned short*)C)[(size_t)m * ldc + n] = (unsigned short)d3f_bf16_rne(v);
-    else C[(size_t)m * ldc + n] = v;
-}
-
-// Tile selection.  Large tiles (each wave owns 2x2 / 2x1 MFMA tiles: half the LDS traffic per flop, 4 independent
-// accumulator chains) when the problem still fills the chip with them; smaller tiles / split K for the skinny deep layers.
-static void gemm_plan(int M, int N, int K, int M_hint, int& bm, int& bn, int& S, int& tps) {
-    // capacity mode: M is only an upper bound; split K for the row count the caller EXPECTS (skinny deep layers would
-    // otherwise be planned as if they filled the chip and run their whole K loop in a handful of workgroups)
-    if (M_hint > 0 && M_hint < M) M = M_hint;
-    // Measured on MI355X over the network's 37 shapes (round 1 / 2 sweeps): these GEMMs are small (<= 7 GFLOP) and latency /
-    // bandwidth bound, so the 64x64 tile -- 37 KB of LDS, 4 workgroups resident per CU -- beat the register-tiled 128x128 /
-    // 128x64 variants everywhere.
-    auto blocks_of = [&](int m, int n) { return (long long)d3f_cdiv(M, m) * d3f_cdiv(N, n); };
-    if (N <= 32) { bm = 128; bn = 32; }
-    else { bm = 64; bn = 64; }
-    const long long blocks = blocks_of(bm, bn);
-    const int nt = d3f_cdiv(K, GM_BK);
-    // Skinny problems with a long K are latency bound per k-tile (global -> LDS -> MFMA): give every CU ~6 co-resident
-    // workgroups by splitting K, as long as each split keeps >= 8 k-tiles.  Up to 16 k-tiles (K <= 512) a split never paid
-    // for its slab traffic and reduce launch (tools/gemm_bench.py sweep).
-    S = 1;
-    if (blocks < 768 && nt > 16) {
-        long long want = (1536 + blocks - 1) / blocks;
-        long long maxs = nt / 8;
-        S = (int)(want < maxs ? want : maxs);
-        if (S > 64) S = 64;
-        if (S < 1) S = 1;
-    }
-    tps = d3f_cdiv(nt, S);
-    S = d3f_cdiv(nt, tps);
-}
-
 extern "C" size_t d3f_gemm_workspace_bytes(int M, int N, int K, int M_hint) {
     if (M <= 0 || N <= 0 || K <= 0) return 256;
     int bm, bn, S, tps;
     gemm_plan(M, N, K, M_hint, bm, bn, S, tps);
-    return S > 1 ? d3f_align((size_t)S * M * N * sizeof(float)) + 256 : 256;
+    return gemm_slab_bytes(S, M, N);
 }
 
 static int gemm_run(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K, GemmEpi E,
@@ -554,16 +426,12 @@ static int gemm_run(const float* A, int lda, const float* B, int ldb, float* C, 
                     GemmGather G, void* workspace, size_t workspace_bytes, const int* M_dev, int M_hint, hipStream_t stream) {
     int bm, bn, S, tps;
     gemm_plan(M, N, K > 0 ? K : 1, M_hint, bm, bn, S, tps);
-    float* slab = nullptr;
-    if (S > 1) {
-        const size_t need = (size_t)S * M * N * sizeof(float);
-        if (!workspace || workspace_bytes < need) return D3F_ERR_WORKSPACE;
-        slab = (float*)workspace;
-    }
+    float* slab;
+    if (int rc = gemm_slab(S, M, N, workspace, workspace_bytes, slab)) return rc;
     const int vecA = (lda % 4 == 0) && (((uintptr_t)A & 15) == 0);
     const int vecB = (ldb % 4 == 0) && (((uintptr_t)B & 15) == 0);
     if (d3f_cdiv(M, bm) > 65535) return D3F_ERR_ARG;
-    dim3 grid(d3f_cdiv(N, bn), S, d3f_cdiv(M, bm));
+    const dim3 grid(d3f_cdiv(N, bn), S, d3f_cdiv(M, bm));      // bm x bn = 128 x 32 or 64 x 64 for both kernels
     // float4-addressable operands (every shape of the network): the straight-line kernel; anything else: the generic one
     const bool fast = (!E.residual || (E.ldr % 4 == 0 && ((uintptr_t)E.residual & 15) == 0)) && vecA && vecB &&
                       K % 4 == 0 && N % 4 == 0 && ldc % 4 == 0 &&
@@ -571,37 +439,22 @@ static int gemm_run(const float* A, int lda, const float* B, int ldb, float* C, 
                       (!G.A2 || (G.K1 % 4 == 0 && G.lda2 % 4 == 0 && ((uintptr_t)G.A2 & 15) == 0));
     if (fast) {
         const size_t lds = (size_t)2 * (bm + bn) * GF_S * sizeof(float);
-#define D3F_GEMM_E(WM_, WN_, TM_, TN_, NA_, EPI_)                                                                     \
-    gemm_fast_kernel<WM_, WN_, TM_, TN_, NA_, EPI_><<<grid, 256, lds, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, tps, slab, E, \
-                                                                                M_dev, G)
-#define D3F_GEMM(WM_, WN_, TM_, TN_, NA_)                                                                              \
-    do {                                                                                                               \
-        const int epi = (E.row_scale ? 1 : 0) | (E.residual ? 2 : 0);                                                  \
-        if (epi == 0) D3F_GEMM_E(WM_, WN_, TM_, TN_, NA_, 0);                                                          \
-        else if (epi == 1) D3F_GEMM_E(WM_, WN_, TM_, TN_, NA_, 1);                                                     \
-        else if (epi == 2) D3F_GEMM_E(WM_, WN_, TM_, TN_, NA_, 2);                                                     \
-        else D3F_GEMM_E(WM_, WN_, TM_, TN_, NA_, 3);                                                                   \
-    } while (0)
-        if (bn == 32) D3F_GEMM(4, 1, 1, 1, 1);
-        else D3F_GEMM(2, 2, 1, 1, 1);
-#undef D3F_GEMM
-#undef D3F_GEMM_E
+        gemm_with_epi(E, [&](auto epi) {
+            constexpr int EPI = decltype(epi)::value;
+            if (bn == 32) gemm_fast_kernel<4, 1, EPI><<<grid, 256, lds, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, tps, slab, E, M_dev, G);
+            else gemm_fast_kernel<2, 2, EPI><<<grid, 256, lds, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, tps, slab, E, M_dev, G);
+        });
+    } else if (bn == 32) {
+        gemm_f32_kernel<4, 1><<<grid, 256, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, vecA, vecB, tps, slab, E, M_dev, G);
     } else {
-        if (bn != 32) { bm = 64; bn = 64; grid = dim3(d3f_cdiv(N, bn), S, d3f_cdiv(M, bm)); }
-#define D3F_GEMM(WM_, WN_, TM_, TN_)                                                                                   \
-    gemm_f32_kernel<WM_, WN_, TM_, TN_><<<grid, 256, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, vecA, vecB, tps, slab, E, \
-                                                                  M_dev, G)
-        if (bn == 32) D3F_GEMM(4, 1, 1, 1);
-        else D3F_GEMM(2, 2, 1, 1);
-#undef D3F_GEMM
+        gemm_f32_kernel<2, 2><<<grid, 256, 0, stream>>>(A, lda, B, ldb, C, ldc, M, N, K, vecA, vecB, tps, slab, E, M_dev, G);
     }
-    if (S > 1)
-        gemm_splitk_reduce_kernel<<<d3f_cdiv((long long)M * N, 256), 256, 0, stream>>>(slab, S, M, N, C, ldc, E, M_dev);
+    gemm_reduce(slab, S, M, N, C, ldc, E, M_dev, stream);
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }
 
-// ---- LDS-DMA form (gemm_dma.h): weights pre-transposed once, k-tiles in a STAGES-deep LDS ring ------------------------
+// ---- LDS-DMA form (gemm_dma.h): weights pre-transposed once, k-tiles in a GD_STAGES-deep LDS ring -----------------------
 extern "C" int d3f_gemm_pack_f32t(const float* B, int ldb, int K, int N, float* Wt, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (K < 1 || N < 1 || ldb < N || !B || !Wt) return D3F_ERR_ARG;
@@ -615,8 +468,7 @@ extern "C" int d3f_gemm_pack_f32t(const float* B, int ldb, int K, int N, float* 
 // ring runs across tile boundaries, a loader wavefront) are recorded in profiles/r04_experiments.txt g1-g6 with their numbers; the
 // persistent walk is still in the kernel (grid = items is its degenerate case), the others live in git history /
 // tools/ubench/gemm_dma_loader_wave.patch.  What ships: 3 stages, 64 x 64 tiles (128 x 32 when N <= 32), one item per workgroup.
-#define GD_STAGES 3
-
+//
 // Same operator and argument meaning as d3f_gemm_bf16 (the union of d3f_gemm_f32 and d3f_gemm_upsample_cat_f32), in fp32:
 //   C = act( ([ A'[idx[m,0]] | skip[m] ] @ W) * row_scale * col_scale + col_shift + residual ),  Wt = d3f_gemm_pack_f32t(W).
 // Operands must be float4-addressable (C1, C2, lda, lds, ldc, ldr multiples of 4; 16-byte aligned bases) -- D3F_ERR_ARG otherwise:
@@ -627,56 +479,30 @@ extern "C" int d3f_gemm_f32t(const float* A, int N1, int lda, int C1, const int*
                              size_t workspace_bytes, const int* M_dev, const int* N1_dev, int M_hint, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int K = C1 + C2;
-    if (M < 0 || N < 1 || N1 < 0 || C1 < 4 || C2 < 0 || (C1 % 4) || (C2 % 4) || (N % 4) || lda < C1 || (lda % 4) || ldc < N || (ldc % 4) ||
-        (C2 > 0 && (lds < C2 || (lds % 4))) || (residual && (ldr < N || (ldr % 4))) || (idx && ld_idx < 1) || (!idx && N1 < M))
-        return D3F_ERR_ARG;
-    if (M == 0) return D3F_OK;
-    if (!A || !Wt || !C || (C2 > 0 && !skip) ||
-        (((uintptr_t)A | (uintptr_t)Wt | (uintptr_t)C | (uintptr_t)skip | (uintptr_t)residual | (uintptr_t)col_scale | (uintptr_t)col_shift) & 15))
-        return D3F_ERR_ARG;
+    bool empty;
+    if (int rc = gemm_check_composite(true, 4, 15, M, N, N1, C1, C2, lda, ldc, lds, ldr, ld_idx, A, Wt, C, idx, skip, residual,
+                                      col_scale, col_shift, empty))
+        return rc;
+    if (empty) return D3F_OK;
     const int Kp = (K + GD_BK - 1) / GD_BK * GD_BK;
     int bm, bn, S, tps;
     gemm_plan(M, N, K, M_hint, bm, bn, S, tps);
-    float* slab = nullptr;
-    if (S > 1) {
-        if (!workspace || workspace_bytes < (size_t)S * M * N * sizeof(float)) return D3F_ERR_WORKSPACE;
-        slab = (float*)workspace;
-    }
+    float* slab;
+    if (int rc = gemm_slab(S, M, N, workspace, workspace_bytes, slab)) return rc;
     GemmEpi E{row_scale, col_scale, col_shift, residual, ldr, leaky, alpha};
     GemmGather G{idx, ld_idx, N1, N1_dev, C2 > 0 ? skip : nullptr, lds, C1};
+    static_assert((size_t)GD_STAGES * (128 + 32) * GD_BK * sizeof(float) <= 65536, "the ring needs an LDS opt-in (d3f_opt_in_lds)");
     const size_t lds_bytes = (size_t)GD_STAGES * (bm + bn) * GD_BK * sizeof(float);
     const long long items_cap = (long long)d3f_cdiv(N, bn) * S * d3f_cdiv(M, bm);
     const long long gsz = (items_cap + 7) / 8 * 8;        // one item per workgroup; a multiple of 8 keeps the XCD item order whole
     if (gsz > 0x7fffffffll) return D3F_ERR_ARG;
-    dim3 grid((unsigned)gsz, 1, 1);
-#define D3F_GD_E(WM_, WN_, TM_, TN_, ST_, EPI_)                                                                                 \
-    do {                                                                                                                       \
-        if (lds_bytes > 65536) {                                                                                               \
-            static std::atomic<int> done{0};                                                                                   \
-            if (!done.load(std::memory_order_acquire)) {                                                                       \
-                if (hipFuncSetAttribute((const void*)gemm_dma_kernel<WM_, WN_, TM_, TN_, ST_, EPI_>,                           \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return D3F_ERR_HIP; \
-                done.store(1, std::memory_order_release);                                                                      \
-            }                                                                                                                  \
-        }                                                                                                                      \
-        gemm_dma_kernel<WM_, WN_, TM_, TN_, ST_, EPI_><<<grid, 256, lds_bytes, stream>>>(A, lda, Wt, Kp, C, ldc, M, N, K, tps, S, slab, \
-                                                                                          E, M_dev, G);                        \
-    } while (0)
-#define D3F_GD_S(WM_, WN_, TM_, TN_, ST_)                                                                                       \
-    do {                                                                                                                       \
-        const int epi = (E.row_scale ? 1 : 0) | (E.residual ? 2 : 0);                                                          \
-        if (epi == 0) D3F_GD_E(WM_, WN_, TM_, TN_, ST_, 0);                                                                    \
-        else if (epi == 1) D3F_GD_E(WM_, WN_, TM_, TN_, ST_, 1);                                                               \
-        else if (epi == 2) D3F_GD_E(WM_, WN_, TM_, TN_, ST_, 2);                                                               \
-        else D3F_GD_E(WM_, WN_, TM_, TN_, ST_, 3);                                                                             \
-    } while (0)
-    if (bn == 32) D3F_GD_S(4, 1, 1, 1, GD_STAGES);
-    else D3F_GD_S(2, 2, 1, 1, GD_STAGES);
-#undef D3F_GD
-#undef D3F_GD_S
-#undef D3F_GD_E
-    if (S > 1)
-        gemm_splitk_reduce_kernel<<<d3f_cdiv((long long)M * N, 256), 256, 0, stream>>>(slab, S, M, N, C, ldc, E, M_dev);
+    const dim3 grid((unsigned)gsz, 1, 1);
+    gemm_with_epi(E, [&](auto epi) {
+        constexpr int EPI = decltype(epi)::value;
+        if (bn == 32) gemm_dma_kernel<4, 1, EPI><<<grid, 256, lds_bytes, stream>>>(A, lda, Wt, Kp, C, ldc, M, N, K, tps, S, slab, E, M_dev, G);
+        else gemm_dma_kernel<2, 2, EPI><<<grid, 256, lds_bytes, stream>>>(A, lda, Wt, Kp, C, ldc, M, N, K, tps, S, slab, E, M_dev, G);
+    });
+    gemm_reduce(slab, S, M, N, C, ldc, E, M_dev, stream);
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }
@@ -701,20 +527,14 @@ typedef __bf16 gb_bf16x8 __attribute__((ext_vector_type(8)));
 #define GB_BK 32
 #define GB_LS 40          // LDS row stride in bf16 elements (80 bytes)
 
-__device__ __forceinline__ unsigned gb_rne(float f) {          // fp32 -> bf16 bits, round to nearest even (NaN stays NaN)
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ unsigned gb_pack2(float a, float b) { return gb_rne(a) | (gb_rne(b) << 16); }
+__device__ __forceinline__ unsigned gb_pack2(float a, float b) { return d3f_bf16_rne(a) | (d3f_bf16_rne(b) << 16); }
 
 __global__ void __launch_bounds__(256) gemm_pack_bf16_kernel(const float* __restrict__ B, int ldb, int K, int N, int Kp,
                                                              unsigned short* __restrict__ Wt) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long long)N * Kp) return;
     const int n = (int)(t / Kp), k = (int)(t % Kp);
-    Wt[t] = (unsigned short)(k < K ? gb_rne(B[(size_t)k * ldb + n]) : 0u);
+    Wt[t] = (unsigned short)(k < K ? d3f_bf16_rne(B[(size_t)k * ldb + n]) : 0u);
 }
 
 extern "C" int d3f_gemm_pack_bf16(const float* B, int ldb, int K, int N, void* Wt, void* stream_) {
@@ -860,7 +680,7 @@ extern "C" size_t d3f_gemm_bf16_workspace_bytes(int M, int N, int K, int M_hint)
     if (M <= 0 || N <= 0 || K <= 0) return 256;
     int S, tps;
     gemm_bf16_split(M, N, K, M_hint, S, tps);
-    return S > 1 ? d3f_align((size_t)S * M * N * sizeof(float)) + 256 : 256;
+    return gemm_slab_bytes(S, M, N);
 }
 
 // A f32[M,K] (lda) or the composite [ x'[idx[m,0]] | skip[m] ] (idx != NULL / skip != NULL, as d3f_gemm_upsample_cat_f32);
@@ -877,20 +697,16 @@ extern "C" int d3f_gemm_bf16(const void* A_, int N1, int lda, int C1, const int*
     const float* residual = (const float*)residual_;
     float* C = (float*)C_;
     const int K = C1 + C2;
-    if (M < 0 || N < 1 || N1 < 0 || C1 < 4 || C2 < 0 || (K % 4) || (C1 % 4) || lda < C1 || (lda % 4) || ldc < N ||
-        (C2 > 0 && (lds < C2 || (lds % 4))) || (residual && ldr < N) || (idx && ld_idx < 1) || (!idx && N1 < M))
-        return D3F_ERR_ARG;
-    if (M == 0) return D3F_OK;
-    if (!A || !Wt || !C || (C2 > 0 && !skip) || ((uintptr_t)Wt & 15) || (((uintptr_t)A | (uintptr_t)skip) & (a_bf16 ? 7 : 15)))
-        return D3F_ERR_ARG;
+    bool empty;
+    if (int rc = gemm_check_composite(false, 4, a_bf16 ? 7 : 15, M, N, N1, C1, C2, lda, ldc, lds, ldr, ld_idx, A, Wt, C, idx, skip,
+                                      residual, col_scale, col_shift, empty))
+        return rc;
+    if (empty) return D3F_OK;
     const int Kp = (K + GB_BK - 1) / GB_BK * GB_BK;
     int S, tps;
     gemm_bf16_split(M, N, K, M_hint, S, tps);
-    float* slab = nullptr;
-    if (S > 1) {
-        if (!workspace || workspace_bytes < (size_t)S * M * N * sizeof(float)) return D3F_ERR_WORKSPACE;
-        slab = (float*)workspace;
-    }
+    float* slab;
+    if (int rc = gemm_slab(S, M, N, workspace, workspace_bytes, slab)) return rc;
     if (d3f_cdiv(M, 64) > 65535) return D3F_ERR_ARG;
     GemmEpi E{row_scale, col_scale, col_shift, residual, ldr, leaky, alpha};
     GemmGather G{idx, ld_idx, N1, N1_dev, C2 > 0 ? skip : nullptr, lds, C1};
@@ -899,8 +715,7 @@ extern "C" int d3f_gemm_bf16(const void* A_, int N1, int lda, int C1, const int*
     if (a_bf16) { if (c_bf16) D3F_GB(true, true); else D3F_GB(true, false); }
     else { if (c_bf16) D3F_GB(false, true); else D3F_GB(false, false); }
 #undef D3F_GB
-    if (S > 1)
-        gemm_splitk_reduce_kernel<<<d3f_cdiv((long long)M * N, 256), 256, 0, stream>>>(slab, S, M, N, C, ldc, E, M_dev, a_bf16, c_bf16);
+    gemm_reduce(slab, S, M, N, C, ldc, E, M_dev, stream, a_bf16, c_bf16);
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }
@@ -992,7 +807,7 @@ extern "C" int d3f_gemm_x3_plan(int M, int N, int K, int M_hint, int* rows, int*
 extern "C" size_t d3f_gemm_x3_workspace_bytes(int M, int N, int K, int M_hint) {
     if (M <= 0 || N <= 0 || K < GX_BK) return 256;
     const GemmX3Plan p = gemm_x3_plan(M, N, K, M_hint);
-    return p.S > 1 ? d3f_align((size_t)p.S * M * N * sizeof(float)) + 256 : 256;
+    return gemm_slab_bytes(p.S, M, N);
 }
 
 // LDS of the resident-W persistent form (gemm_x3.h): the whole pre-split W, the A patches and the epilogue vectors
@@ -1016,14 +831,11 @@ extern "C" int d3f_gemm_x3(const float* A, int N1, int lda, int C1, const int* i
                            size_t workspace_bytes, const int* M_dev, const int* N1_dev, int M_hint, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int K = C1 + C2;
-    if (M < 0 || N < 1 || N1 < 0 || C1 < 4 || C2 < 0 || (C1 % 4) || (C2 % 4) || (N % 4) || lda < C1 || (lda % 4) || ldc < N || (ldc % 4) ||
-        (C2 > 0 && (lds < C2 || (lds % 4))) || (residual && (ldr < N || (ldr % 4))) || (idx && ld_idx < 1) || (!idx && N1 < M))
-        return D3F_ERR_ARG;
-    if ((K % GX_BK) || (C2 > 0 && (C1 % GX_BK))) return D3F_ERR_ARG;
-    if (M == 0) return D3F_OK;
-    if (!A || !Wx || !C || (C2 > 0 && !skip) ||
-        (((uintptr_t)A | (uintptr_t)Wx | (uintptr_t)C | (uintptr_t)skip | (uintptr_t)residual | (uintptr_t)col_scale | (uintptr_t)col_shift) & 15))
-        return D3F_ERR_ARG;
+    bool empty;
+    if (int rc = gemm_check_composite(true, GX_BK, 15, M, N, N1, C1, C2, lda, ldc, lds, ldr, ld_idx, A, Wx, C, idx, skip, residual,
+                                      col_scale, col_shift, empty))
+        return rc;
+    if (empty) return D3F_OK;
     GemmEpi E{row_scale, col_scale, col_shift, residual, ldr, leaky, alpha};
     GemmGather G{idx, ld_idx, N1, N1_dev, C2 > 0 ? skip : nullptr, lds, C1};
     const int nkt = K / GX_BK, NG = d3f_cdiv(N, 32);
@@ -1053,11 +865,8 @@ extern "C" int d3f_gemm_x3(const float* A, int N1, int lda, int C1, const int* i
     }
     const GemmX3Plan pl = gemm_x3_plan(M, N, K, M_hint);
     const int S = pl.S, tps = pl.tps, bm = 32 * pl.waves;
-    float* slab = nullptr;
-    if (S > 1) {
-        if (!workspace || workspace_bytes < (size_t)S * M * N * sizeof(float)) return D3F_ERR_WORKSPACE;
-        slab = (float*)workspace;
-    }
+    float* slab;
+    if (int rc = gemm_slab(S, M, N, workspace, workspace_bytes, slab)) return rc;
     if (d3f_cdiv(M, bm) > 65535) return D3F_ERR_ARG;
     dim3 grid(d3f_cdiv(N, 32 * pl.tn), S, d3f_cdiv(M, bm));
 #define D3F_GX(TN_, WV_) gemm_x3_kernel<TN_, WV_><<<grid, 64 * WV_, 0, stream>>>(A, lda, (const unsigned short*)Wx, nkt, NG, C, ldc, M, N, tps, slab, E, M_dev, G)
@@ -1065,8 +874,7 @@ extern "C" int d3f_gemm_x3(const float* A, int N1, int lda, int C1, const int* i
     else if (pl.tn == 1) D3F_GX(1, 4);
     else D3F_GX(2, 4);
 #undef D3F_GX
-    if (S > 1)
-        gemm_splitk_reduce_kernel<<<d3f_cdiv((long long)M * N, 256), 256, 0, stream>>>(slab, S, M, N, C, ldc, E, M_dev);
+    gemm_reduce(slab, S, M, N, C, ldc, E, M_dev, stream);
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }

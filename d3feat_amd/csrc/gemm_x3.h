@@ -39,6 +39,7 @@
 // wave cost 0.48 us where the MFMAs alone cost 0.33, whatever the number of waves), which bounds this form at ~0.7 of the bf16
 // matrix rate it issues; the network's launches are short of that mostly for their size (<= 14 GFLOP, 2-24 k-tiles per workgroup).
 #pragma once
+#include "gemm_common.h"
 
 #define GX_BK 32
 #define GX_LS 40                      // bf16 per LDS row
@@ -101,9 +102,9 @@ __global__ void __launch_bounds__(256) gemm_pack_x3_kernel(const float* __restri
     unsigned out = 0u;
     if (kk < GX_BK && k < K && n < N) {
         float w = B[(size_t)k * ldb + n];
-        unsigned h = gb_rne(w);
-        if (p > 0) { w -= __uint_as_float(h << 16); h = gb_rne(w); }
-        if (p > 1) { w -= __uint_as_float(h << 16); h = gb_rne(w); }
+        unsigned h = d3f_bf16_rne(w);
+        if (p > 0) { w -= __uint_as_float(h << 16); h = d3f_bf16_rne(w); }
+        if (p > 1) { w -= __uint_as_float(h << 16); h = d3f_bf16_rne(w); }
         out = h;
     }
     Wx[t] = (unsigned short)out;

@@ -95,6 +95,139 @@ def test_gemm_strided_views(device):
     _close(got, big[:, 8:48].astype(np.float64) @ B, 2e-5, relative=True)
 
 
+# ---- gemm_fast_kernel: the register-staged fp32 tile kernel behind d3f_gemm_f32 / d3f_gemm_upsample_cat_f32.  ops._route sends
+# every float4-addressable call to d3f_gemm_f32t / d3f_gemm_x3, so the kernel is reached through the C ABI itself (what a direct
+# caller of the library gets) and through ops.gemm only with a weight that is a column view of a wider tensor.
+_EPIS = {"plain": (), "rows": ("rs",), "res": ("res",), "rows_res": ("rs", "res")}     # EPI 0, 1, 2, 3 of the kernel
+# (33, 8, 4) / (70000, 160, 64) / (9000, 512, 128; 6100 rows): unsplit, (200, 4096, 128) / (1580, 7680, 512; 1200 rows): split K --
+# shapes of test_gemm_split_plans_and_capacity_rows; (1000, 64, 32) and (300, 2048, 32): the 128 x 32 tile, unsplit and split
+_FAST_SHAPES = [(33, 8, 4, 0), (1000, 64, 32, 0), (300, 2048, 32, 170), (70000, 160, 64, 0), (200, 4096, 128, 0),
+                (9000, 512, 128, 6100), (1580, 7680, 512, 1200)]
+
+
+def _cabi_gemm_f32(device, A, B, ldb, N, out, rs=None, cs=None, ch=None, res=None, leaky=False, real=0):
+    """lib.d3f_gemm_f32 on device tensors; real > 0: the device-resident row count (rows past it are not written)."""
+    from d3feat_amd import _lib, ops
+    lib = _lib.load()
+    (M, K), p = A.shape, ops._ptr
+    ws = torch.empty(lib.d3f_gemm_workspace_bytes(M, N, K, real), dtype=torch.uint8, device=device)
+    m_dev = torch.tensor([real], dtype=torch.int32, device=device) if real else None
+    _lib.check(lib.d3f_gemm_f32(A.data_ptr(), A.stride(0), B.data_ptr(), ldb, out.data_ptr(), out.stride(0), M, N, K, p(rs), p(cs),
+                                p(ch), p(res), res.stride(0) if res is not None else 0, int(leaky), 0.2, ws.data_ptr(), ws.numel(),
+                                p(m_dev), real, ops._stream(device)), "gemm_f32")
+    torch.cuda.synchronize()
+
+
+def _fast_kernel_outputs(device, M, K, N, real):
+    """-> {epilogue name: (output of lib.d3f_gemm_f32 with a sentinel in every row, float64 reference of the first n rows, n)};
+    every call is made twice and must repeat bit for bit."""
+    rng = np.random.default_rng(M + K + N)
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    B = (rng.standard_normal((K, N)) / np.sqrt(K)).astype(np.float32)
+    v = dict(rs=rng.random(M).astype(np.float32) + 0.5, res=rng.standard_normal((M, N)).astype(np.float32))
+    cs = rng.random(N).astype(np.float32) + 0.5
+    ch = rng.standard_normal(N).astype(np.float32)
+    n = real or M
+    ref = A[:n].astype(np.float64) @ B.astype(np.float64)
+    tA, tB, tv = _t(A, device), _t(B, device), {k: _t(a, device) for k, a in v.items()}
+    found = {}
+    for name, terms in _EPIS.items():
+        kw = {k: tv[k] for k in terms}
+        if name != "plain":
+            kw.update(cs=_t(cs, device), ch=_t(ch, device), leaky=True)
+        outs = []
+        for rep in range(2):
+            outs.append(torch.full((M, N), 12345.0, dtype=torch.float32, device=device))
+            _cabi_gemm_f32(device, tA, tB, N, N, outs[-1], real=real, **kw)
+        assert torch.equal(outs[0], outs[1]), name
+        want = ref
+        if name != "plain":
+            want = ref * (v["rs"][:n, None] if "rs" in terms else 1.0) * cs + ch + (v["res"][:n] if "res" in terms else 0.0)
+            want = np.where(want > 0, want, 0.2 * want)
+        found[name] = (outs[0].cpu().numpy(), want, n)
+    return found
+
+
+@pytest.mark.parametrize("M,K,N,real", _FAST_SHAPES)
+def test_gemm_fast_kernel_c_abi(device, M, K, N, real):
+    """d3f_gemm_f32 with float4-addressable operands runs gemm_fast_kernel: both tile shapes (N <= 32: 128 x 32, else 64 x 64), K
+    split into slabs and not, a device row count below the capacity (the rows past it keep their sentinel), the four epilogue
+    instantiations; against float64 at the bound of the raw contraction tests, bit-equal from call to call."""
+    for name, (got, want, n) in _fast_kernel_outputs(device, M, K, N, real).items():
+        _close(got[:n], want, 2e-5, relative=True)      # raw contraction, random operands
+        assert (got[n:] == 12345.0).all(), name
+
+
+def _fast_upsample_cat_output(device, C1, C2, N):
+    """-> (output of lib.d3f_gemm_upsample_cat_f32, float64 reference): gathered first operand whose indices leave [0, n1) on both
+    sides (they read the zero row), concatenated second operand when C2 > 0; called twice, bit-equal."""
+    from d3feat_amd import _lib, ops
+    lib = _lib.load()
+    rng = np.random.default_rng(C1 + C2 + N)
+    n1, m, K, p = 700, 2500, C1 + C2, ops._ptr
+    x = rng.standard_normal((n1, C1)).astype(np.float32)
+    skip = rng.standard_normal((m, C2)).astype(np.float32) if C2 else None
+    idx = rng.integers(0, n1, (m, 3)).astype(np.int32)
+    idx[::17, 0], idx[5::23, 0], idx[7::29, 0] = n1, -1, n1 + 1000
+    W = (rng.standard_normal((K, N)) / np.sqrt(K)).astype(np.float32)
+    cs = rng.random(N).astype(np.float32) + 0.5
+    ch = rng.standard_normal(N).astype(np.float32)
+    tx, tidx, tW, tcs, tch = (_t(a, device) for a in (x, idx, W, cs, ch))
+    tskip = _t(skip, device) if C2 else None
+    ws = torch.empty(lib.d3f_gemm_workspace_bytes(m, N, K, 0), dtype=torch.uint8, device=device)
+    outs = []
+    for rep in range(2):
+        outs.append(torch.full((m, N), 12345.0, dtype=torch.float32, device=device))
+        _lib.check(lib.d3f_gemm_upsample_cat_f32(tx.data_ptr(), n1, C1, C1, tidx.data_ptr(), 3, p(tskip), C2, C2, tW.data_ptr(), N,
+                                                 outs[-1].data_ptr(), N, m, N, tcs.data_ptr(), tch.data_ptr(), 1, 0.2, ws.data_ptr(),
+                                                 ws.numel(), None, None, 0, ops._stream(device)), "gemm_upsample_cat_f32")
+        torch.cuda.synchronize()
+    assert torch.equal(outs[0], outs[1])
+    col = idx[:, 0]
+    rows = np.where(((col >= 0) & (col < n1))[:, None], x[np.clip(col, 0, n1 - 1)], 0.0)
+    ref = np.concatenate([rows] + ([skip] if C2 else []), 1).astype(np.float64) @ W.astype(np.float64)
+    ref = ref * cs + ch
+    return outs[0].cpu().numpy(), np.where(ref > 0, ref, 0.2 * ref)
+
+
+@pytest.mark.parametrize("C1,C2,N", [(128, 64, 64), (1024, 2048, 512), (64, 0, 32)])
+def test_gemm_fast_kernel_upsample_cat_c_abi(device, C1, C2, N):
+    """d3f_gemm_upsample_cat_f32 on gemm_fast_kernel: unsplit 64 x 64, split K, 128 x 32 without a second operand."""
+    got, want = _fast_upsample_cat_output(device, C1, C2, N)
+    _close(got, want, 2e-5, relative=True)      # raw contraction, random operands
+
+
+def _fast_weight_view_outputs(device, N):
+    """-> [(output of ops.gemm, float64 reference)] for a weight that is columns 8 .. 8 + N of a wider tensor (ldb = N + 24: a
+    multiple of 4, 16-byte aligned base), which only d3f_gemm_f32 takes; raw and with the whole epilogue."""
+    from d3feat_amd import ops
+    rng = np.random.default_rng(N)
+    M, K = 3000, 96
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    wide = (rng.standard_normal((K, N + 24)) / np.sqrt(K)).astype(np.float32)
+    rs = rng.random(M).astype(np.float32) + 0.5
+    cs = rng.random(N).astype(np.float32) + 0.5
+    ch = rng.standard_normal(N).astype(np.float32)
+    res = rng.standard_normal((M, N)).astype(np.float32)
+    tA, tW = _t(A, device), _t(wide, device)[:, 8:8 + N]
+    assert not tW.is_contiguous() and tW.stride(0) % 4 == 0 and tW.data_ptr() % 16 == 0
+    ref = A.astype(np.float64) @ wide[:, 8:8 + N].astype(np.float64)
+    full = ref * rs[:, None] * cs + ch + res
+    found = []
+    for want, args in ((ref, ()), (np.where(full > 0, full, 0.2 * full), (_t(rs, device), _t(cs, device), _t(ch, device), _t(res, device), True, 0.2))):
+        got = [ops.gemm(tA, tW, *args) for rep in range(2)]
+        assert torch.equal(got[0], got[1])
+        found.append((got[0].cpu().numpy(), want))
+    return found
+
+
+@pytest.mark.parametrize("N", [32, 64])
+def test_gemm_fast_kernel_weight_column_view(device, N):
+    """ops.gemm reaches gemm_fast_kernel when the weight is a column view of a wider tensor (ldb != N)."""
+    for got, want in _fast_weight_view_outputs(device, N):
+        _close(got, want, 2e-5, relative=True)      # raw contraction, random operands
+
+
 def _layer_case(seed, cin, cout, strided, layer=0):
     from d3feat_amd.utils.config import threedmatch_config
     cfg = threedmatch_config()
