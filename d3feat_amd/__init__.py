@@ -11,5 +11,6 @@ Layout (mirrors the reference's module paths for the hot path only):
   datasets/common.py           Dataset: descriptor pyramid, neighbour calibration       (reference: datasets/common.py)
   utils/config.py              Config (parameters.txt compatible)                       (reference: utils/config.py)
   parallel.py                  fragment sharding across GPUs + final RCCL gather
+  keypoints.py                 the K highest-scoring records per cloud, on the device   (reference: utils/tester.py:208-213 + evaluate.py:45-50)
 """
 __version__ = "0.1.0"

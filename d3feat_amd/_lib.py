@@ -16,6 +16,7 @@ ST_EMPTY_ELEMENT, ST_NEG_CELL, ST_KEY_RANGE, ST_HIT_OVERFLOW, ST_OUT_OVERFLOW, S
 PAD_NUM_SUPPORTS = -2147483648
 NEIGHBOR_CAP = 1024
 MAX_BATCH = 255
+TOPK_MAX = 8192
 
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
 
@@ -65,6 +66,9 @@ SIGNATURES = {
     "d3f_affine_act": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp]),
     "d3f_pack_descriptors": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "d3f_pack_descriptors_to": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "d3f_topk_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "d3f_topk_records": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz,
+                              _vp]),
     "d3f_feature_nn_workspace_bytes": (_sz, [_i]),
     "d3f_feature_nn": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "d3f_mutual_matches_workspace_bytes": (_sz, [_i]),

@@ -21,7 +21,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, keypoints as kpts, ops
 from . import tf_custom_ops as tfo
 from .datasets.common import FragmentDataset
 from .models.KPFCNN_model import KernelPointFCNN
@@ -53,7 +53,7 @@ class _Slot:
 class FragmentEngine:
     def __init__(self, config, weights, neighborhood_limits, raw_cap=320000, n0_cap=40000, level_ratio=0.4, slots=2,
                  device=None, seed=42, n0_hint=None, mirror_self_pair=False, streams=None, two_clouds=False, batch=1,
-                 bf16=False, bf16_features=False, stage0=True, internal_order=None):
+                 bf16=False, bf16_features=False, stage0=True, internal_order=None, keypoints=None):
         """raw_cap / n0_cap: raw points / voxels per FRAGMENT that a slot can take (a fragment beyond them is recomputed by
         the eager path).
         batch: fragments per graph replay.  The per-fragment cost of this path is dominated by the ~270 dependent launches
@@ -79,6 +79,10 @@ class FragmentEngine:
         stage0=False: the submitted clouds are ALREADY at the first subsampling resolution (the reference's scripts subsample
         before the dataset sees a cloud: demo_registration.py:24, datasets/ThreeDMatch.py:349) -- no stage-0 voxelisation, the
         cloud is stacked with itself as it is; raw_cap is then the voxel capacity n0_cap.
+        keypoints=K: the replay additionally selects, per kept cloud, the K records with the highest detection scores in ascending
+        score order (keypoints.topk: what the reference's testers and consumers do on the host, utils/tester.py:208-213 +
+        geometric_registration/evaluate.py:45-50) -- one more launch after the record packing, a static f32[F * keep_clouds, K, 36]
+        buffer per slot; fetch(slot, keypoints=True) returns them.  None (default): nothing is added to the sequence.
     Weights are captured BY ADDRESS: a replayed graph reads the model's tensors and their packed copies (transposed / pre-split planes,
     made once per tensor: ops._packed_on_tensor) through raw pointers.  `refresh_weights(values)` is the supported way to change
     them under live graphs: device tensors and packed copies are rewritten IN PLACE (same addresses), so the next replay computes
@@ -96,6 +100,9 @@ class FragmentEngine:
             internal_order = os.environ.get("D3F_INTERNAL_ORDER", "1") != "0"
         self.internal = bool(internal_order)
         self.stage0 = bool(stage0)
+        if keypoints is not None and not 1 <= int(keypoints) <= _lib.TOPK_MAX:
+            raise ValueError("keypoints = %s outside 1..%d" % (keypoints, _lib.TOPK_MAX))
+        self.keypoints = int(keypoints) if keypoints is not None else None
         if not self.stage0:
             if self.mirror or self.two:
                 raise ValueError("stage0=False is implemented for stacked self-pairs only")
@@ -182,6 +189,12 @@ class FragmentEngine:
         per = 1 if self.mirror else 2                       # stack entries per fragment
         sl.packed = ops.pack_descriptors(flat[0] if self.internal else pts, desc, score, lens=lens, group=per, keep=self.keep_clouds,
                                          dst=sl.dst_ptrs, row_map=row_map)
+        if self.keypoints:
+            # the K highest-scoring records of every kept cloud, from the same inputs as the packing (so it does not matter where
+            # submit(out=...) sent the full records); the valid rows of a cloud are min(len, K) and the lens already travel in the
+            # replay's status block: nothing more is read back
+            kpts.topk(flat[0] if self.internal else pts, desc, score, self.keypoints, lens=lens, group=per, keep=self.keep_clouds,
+                      row_map=row_map, out=sl.kp, count=sl.kp_count, n_cap=self.n0_cap)
         if self.internal:
             # the separate outputs of fetch(packed=False) in the reference's row order: column views of the record block
             desc, score = sl.packed[:, 3:3 + desc.shape[1]], sl.packed[:, 3 + desc.shape[1]:]
@@ -204,6 +217,9 @@ class FragmentEngine:
         sl.host_dst = sl.meta_host[2 * self.nin: nw].view(torch.int64)
         sl.host_n = sl.meta_host[nw:]
         sl.status0 = torch.zeros((2,), dtype=torch.int32, device=dev)
+        if self.keypoints:
+            sl.kp = torch.zeros((self.F * self.keep_clouds, self.keypoints, 36), dtype=torch.float32, device=dev)
+            sl.kp_count = torch.zeros((self.F * self.keep_clouds,), dtype=torch.int32, device=dev)
         sl.ds = FragmentDataset([], fast=True)
         sl.ds.device = dev
         sl.ds.neighborhood_limits = self.limits
@@ -334,11 +350,33 @@ class FragmentEngine:
             sl.host_stat.copy_(sl.dev_stat, non_blocking=True)
             sl.done.record(sl.stream)
 
-    def fetch(self, slot, packed=False):
+    def _kp_views(self, kp, lens):
+        """Keypoint block f32[keep_clouds, K, 36] of one fragment + the host lengths of its kept clouds -> the valid rows."""
+        v = tuple(kp[c, :min(int(lens[c]), self.keypoints)] for c in range(self.keep_clouds))
+        return v if self.two else v[0]
+
+    def _eager_out(self, fr, packed, want_kp, keep):
+        """One fragment through the eager path, in the form fetch returns."""
+        o = self.run_eager(fr)
+        rec = ops.pack_descriptors(*o) if (packed or want_kp) else None
+        main = keep(rec) if packed else o
+        if not want_kp:
+            return main
+        lens = self._eager_lens                     # [n, n] of the stacked self-pair / [n_a, n_b]: known on the host
+        kp, _ = kpts.topk_records(rec, self.keypoints, lens=lens, group=2, keep=self.keep_clouds)
+        kp = self._kp_views(kp, ops.host_lens(lens))
+        return (main, kp) if packed else kp
+
+    def fetch(self, slot, packed=False, keypoints=False):
         """Wait for slot `slot`; -> (points f32[2n,3], descriptors f32[2n,32], scores f32[2n,1]) device tensors of the stacked
         pair (views into the slot's buffers: valid until the slot is submitted again); a list of such tuples when the
         submit was given a list.  packed=True: one f32[2n, 36] tensor of [xyz | desc | score] records per fragment instead of
-        the tuple (a contiguous view: the unit the sharded runner keeps and gathers)."""
+        the tuple (a contiguous view: the unit the sharded runner keeps and gathers).
+        keypoints=True (engine built with keypoints=K): per fragment the f32[min(n, K), 36] records of the kept cloud's K highest scores
+        in ascending score order instead (a pair of them with two_clouds; views of the slot's keypoint buffer, valid until the slot is
+        submitted again); with packed=True the pair (records, keypoints) of the same replay."""
+        if keypoints and not self.keypoints:
+            raise ValueError("fetch(keypoints=True) on an engine built without keypoints")
         sl = self.slots[slot]
         assert sl.busy, "slot %d is empty" % slot
         sl.busy = False
@@ -373,6 +411,9 @@ class FragmentEngine:
                         if self.mirror:   # stacked layout of the reference: both halves hold the cloud
                             p, d, s = torch.cat([p, p]), torch.cat([d, d]), torch.cat([s, s])
                         outs.append((p, d, s))
+                    if keypoints:
+                        kv = self._kp_views(sl.kp[i * self.keep_clouds:(i + 1) * self.keep_clouds], lens[i * per:])
+                        outs[-1] = (outs[-1], kv) if packed else kv
                     o += n
         if outs is None and sl.nfrag > 1:
             # A flagged replay of several fragments: the flags are per stacked call, not per cloud, so the fragments are
@@ -392,11 +433,15 @@ class FragmentEngine:
                 if (sum(int(x.shape[0]) for x in fr) if self.two else int(fr.shape[0])) > self.raw_cap:
                     self.fragments += 1
                     self.fallbacks += 1
-                    o = self.run_eager(fr)
-                    outs.append(keep(ops.pack_descriptors(*o)) if packed else o)
+                    outs.append(self._eager_out(fr, packed, keypoints, keep))
                     continue
                 self.submit(slot, [fr])
-                o = self.fetch(slot, packed)[0]                 # (counts the fragment, and its fallback if it takes one)
+                o = self.fetch(slot, packed, keypoints)[0]      # (counts the fragment, and its fallback if it takes one)
+                if keypoints:
+                    main, kv = o if packed else (None, o)
+                    kv = tuple(t.clone() for t in kv) if self.two else kv.clone()
+                    outs.append((keep(main).clone(), kv) if packed else kv)
+                    continue
                 outs.append(keep(o).clone() if packed else tuple(t.clone() for t in o))   # the slot's buffers are reused at once
             return outs[0] if single else outs
         self.fragments += sl.nfrag
@@ -416,9 +461,7 @@ class FragmentEngine:
                 warnings.warn("FragmentEngine: %d of %d fragments took the eager fallback (capacities raw_cap=%d n0_cap=%d "
                               "too small for this data, or degenerate clouds): throughput is that of the op-by-op path"
                               % (self.fallbacks, self.fragments, self.raw_cap, self.n0_cap))
-            outs = [self.run_eager(fr) for fr in sl.raw_src]
-            if packed:
-                outs = [keep(ops.pack_descriptors(*o)) for o in outs]
+            outs = [self._eager_out(fr, packed, keypoints, keep) for fr in sl.raw_src]
         return outs[0] if sl.single else outs
 
     def reference_order_flat(self, slot):
@@ -472,6 +515,7 @@ class FragmentEngine:
             n = sub.shape[0]
             pts = torch.cat([sub, sub], 0)
             lens = ops.as_lens([n, n], self.device)
+        self._eager_lens = lens
         flat = self._eager_map(pts, None, None, None, lens, ("a", "a"), pts)
         with ops.bf16_contraction(self.bf16, features=self.bf16_features):
             desc, score = self.model.run(flat)

@@ -4,6 +4,8 @@
     build_correspondence(src_desc, tgt_desc) mutually closest pairs                      evaluate.py:11-27 (same name)
     ransac_feature_matching(...)            open3d.registration_ransac_based_on_feature_matching as the reference calls it
                                             (evaluate.py:93-99, demo_registration.py:184-192)
+    register_keypoints(src_rec, tgt_rec)    both of them on the last num_keypts rows of two keypoint record blocks
+                                            (evaluate.py:45-50,67,93-99), the records never leaving the device
 
 Every computation is a kernel of libd3feat_amd.so (csrc/registration.hip, csrc/radius_neighbors.hip); numpy / torch only
 move data and run the host loop over batches of hypotheses.  Open3D's own random stream is unspecified, so results are
@@ -120,3 +122,24 @@ def ransac_feature_matching(source_points, target_points, source_desc, target_de
     M[:3, :4] = Tb.cpu().numpy().reshape(3, 4).astype(np.float64)
     return dict(transformation=M, fitness=float(cnt[b]) / Ns, inlier_rmse=float(rmse[b]),
                 correspondence_set=np.stack([sel, near[sel]], 1).astype(np.int64), iterations=it0, validations=V)
+
+
+def register_keypoints(src_records, tgt_records, num_keypts=None, device=None, **ransac_kw):
+    """Registration of two fragments from their keypoint records: device f32[k, 3 + C + 1] blocks of [xyz | desc | score] rows in
+    ascending score order (keypoints.topk_records, FragmentEngine.fetch(keypoints=True)).  As geometric_registration/evaluate.py
+    does with the files of a pair: the last `num_keypts` rows of each (:45-50; None = all rows) -> build_correspondence (:67) and
+    ransac_feature_matching (:93-99, `ransac_kw` are its arguments, max_correspondence_distance among them) -- slicing only, the
+    records do not visit the host.  -> the RANSAC dict plus `correspondences` (the mutually closest pairs, i64[k, 2])."""
+    dev = _dev(device)
+    blocks = []
+    for name, rec in (("src_records", src_records), ("tgt_records", tgt_records)):
+        rec = ops._req(rec, torch.float32, name, 2)
+        if rec.shape[1] < 5:
+            raise ValueError("register_keypoints: %s of %d floats per row" % (name, rec.shape[1]))
+        if num_keypts is not None:
+            rec = rec[max(rec.shape[0] - int(num_keypts), 0):]
+        blocks.append(rec)
+    (s, t), w = blocks, blocks[0].shape[1]
+    out = ransac_feature_matching(s[:, :3], t[:, :3], s[:, 3:w - 1], t[:, 3:w - 1], device=dev, **ransac_kw)
+    out["correspondences"] = build_correspondence(s[:, 3:w - 1], t[:, 3:w - 1], device=dev)
+    return out

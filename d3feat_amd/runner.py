@@ -52,14 +52,17 @@ def run_sharded(fragment_ids, sizes, load, config, weights, make_engine, calibra
     calibrate(raws) -> int64 histograms [layers, bins] of this rank's fragments.
     keep: what a fragment contributes to the shard that is gathered -- "first": the first cloud's records, which is what
     utils/tester.py:208-229 keeps of a stacked self-pair; "pair": the whole stacked block (KITTI pairs).  `save` always
-    receives the whole block.
+    receives the whole block.  "keypoints" (an engine built with keypoints=K: engine.keypoints, fetch(slot, keypoints=True)): the
+    fragment's K highest-scoring records in ascending score order, selected on the device -- what every consumer of the tester's
+    files reads (geometric_registration/evaluate.py:45-50); the full records are not fetched, `save` receives the keypoint block
+    (save_keypoints_3dmatch) and the stride of the overlapped exchange is K rows instead of engine.n0_cap.
     overlap_chunk > 0: the shards are exchanged while they are produced, `overlap_chunk` fragments per asynchronous collective
     (parallel.ShardCollector overlapped mode; fixed stride = the engine's row capacity of one contribution, `engine.n0_cap` --
     required, the same number on every rank; a fragment beyond it, i.e. the engine's eager fallback of an oversize cloud, goes
     through the collector's trailing variable-length exchange).
     dst: the rank that receives the shards (default 0: north_star's "gather of descriptors only at the end"); None = every rank.
     -> dict(limits, mine, order (rank 0..W-1 -> fragment indices), shards (list over ranks of (records, frag_rows)) | None)."""
-    assert keep in ("first", "pair")
+    assert keep in ("first", "pair", "keypoints")
     rank, world = parallel.world()
     n = len(fragment_ids)
     mine = parallel.shard_fragments(n, rank, world, sizes=sizes)
@@ -75,7 +78,13 @@ def run_sharded(fragment_ids, sizes, load, config, weights, make_engine, calibra
     engine = make_engine(config, weights, limits, int(max(sizes) * 1.05) + 1024 if sizes else 1024)
     collector = None
     stride = 0
-    if overlap_chunk > 0 and gather:
+    kp_rows = 0
+    if keep == "keypoints":
+        if not getattr(engine, "keypoints", None):
+            raise ValueError("run_sharded(keep='keypoints') needs an engine built with keypoints=K")
+        kp_rows = int(engine.keypoints) * int(getattr(engine, "keep_clouds", 1))       # rows one fragment can contribute
+        stride = kp_rows
+    elif overlap_chunk > 0 and gather:
         if not hasattr(engine, "n0_cap"):
             raise ValueError("run_sharded(overlap_chunk > 0) needs engine.n0_cap: the per-fragment stride of the chunk collectives "
                              "must be the same number on every rank")
@@ -86,7 +95,9 @@ def run_sharded(fragment_ids, sizes, load, config, weights, make_engine, calibra
 
     def drain(sl):
         nonlocal collector
-        for i, rec in zip(pending[sl], engine.fetch(sl, packed=True)):
+        for i, rec in zip(pending[sl], engine.fetch(sl, keypoints=True) if kp_rows else engine.fetch(sl, packed=True)):
+            if isinstance(rec, (tuple, list)):          # both clouds of a pair of different clouds
+                rec = torch.cat(list(rec))
             if collector is None:
                 if overlap_chunk > 0 and gather:
                     # fixed stride = the engine's row capacity of one contribution: the SAME number on every rank (the chunk
@@ -95,8 +106,8 @@ def run_sharded(fragment_ids, sizes, load, config, weights, make_engine, calibra
                                                         chunk_frags=overlap_chunk, frag_rows=stride, async_chunks=async_chunks,
                                                         dst=dst)
                 else:
-                    collector = parallel.ShardCollector(rows_cap=max(int(rec.shape[0]) * max(len(mine), 1), 1), width=rec.shape[1],
-                                                        device=rec.device, dst=dst)
+                    collector = parallel.ShardCollector(rows_cap=max((kp_rows or int(rec.shape[0])) * max(len(mine), 1), 1),
+                                                        width=rec.shape[1], device=rec.device, dst=dst)
             collector.add(rec[: rec.shape[0] // 2] if keep == "first" else rec)
             produced.append(i)
             if save is not None:
@@ -139,15 +150,26 @@ def save_records_3dmatch(root):
     return save
 
 
-def gpu_engine_factory(slots=4, batch=4, mirror=False):
+def save_keypoints_3dmatch(root):
+    """save(fragment_id, keypoint records) for run_sharded(keep="keypoints"): the three files of utils/tester.py:215-229 holding
+    the fragment's K highest-scoring rows (utils.results.save_3dmatch_keypoints)."""
+    from .utils.results import save_3dmatch_keypoints
+
+    def save(fid, kp):
+        save_3dmatch_keypoints(root, fid, kp.cpu().numpy())
+    return save
+
+
+def gpu_engine_factory(slots=4, batch=4, mirror=False, keypoints=None):
     """make_engine for real GPUs: d3feat_amd.engine.FragmentEngine; n0_cap from a first-level estimate, fragments that
-    exceed a capacity take the engine's eager fallback."""
+    exceed a capacity take the engine's eager fallback.  keypoints=K: the engine also selects every fragment's K highest-scoring
+    records (run_sharded(keep="keypoints"))."""
     def make(config, weights, limits, raw_cap):
         from .engine import FragmentEngine
         n0_cap = max(int(raw_cap * 0.16), 4096)          # ~0.1 of the raw points survive the 0.03 m grid on 3DMatch fragments
         dev = torch.device("cuda", torch.cuda.current_device())
         return FragmentEngine(config, weights, limits, raw_cap=raw_cap, n0_cap=n0_cap, slots=slots, device=dev,
-                              mirror_self_pair=mirror, batch=batch)
+                              mirror_self_pair=mirror, batch=batch, keypoints=keypoints)
     return make
 
 

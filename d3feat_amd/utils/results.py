@@ -53,3 +53,27 @@ def save_3dmatch_results(root, anc_id, points, features, scores, first_len):
         np.save(p, arr)
         out.append(p + ".npy")
     return out
+
+
+def save_3dmatch_keypoints(root, anc_id, kp_records):
+    """The three files of utils/tester.py:215-229 for a fragment of which only the K highest-scoring rows were kept: kp_records
+    f32[k, 3 + C + 1] rows [xyz | desc | score] in ascending score order (keypoints.topk_records / FragmentEngine.fetch(keypoints=True),
+    brought to the host by the caller).  The files hold those k rows: for any num_keypts <= k the consumer's [-num_keypts:]
+    (geometric_registration/evaluate.py:47-50) reads the same rows as from the full files save_3dmatch_results writes.
+    Returns the three paths."""
+    if isinstance(anc_id, bytes):
+        anc_id = anc_id.decode("utf-8")
+    r = np.asarray(kp_records, dtype=np.float32)
+    if r.ndim != 2 or r.shape[1] < 5:
+        raise ValueError("save_3dmatch_keypoints: records of shape %s" % (r.shape,))
+    scene = anc_id.split("/")[0]
+    num_frag = int(anc_id.split("_")[-1][:-4])
+    out = []
+    for sub, name, arr in (("descriptors", "cloud_bin_%d.D3Feat" % num_frag, r[:, 3:-1]), ("keypoints", "cloud_bin_%d" % num_frag, r[:, :3]),
+                           ("scores", "cloud_bin_%d" % num_frag, r[:, -1:])):
+        d = os.path.join(root, sub, scene)
+        os.makedirs(d, exist_ok=True)
+        p = os.path.join(d, name)
+        np.save(p, np.ascontiguousarray(arr))
+        out.append(p + ".npy")
+    return out

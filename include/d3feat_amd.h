@@ -42,6 +42,7 @@ extern "C" {
 
 #define D3F_MAX_BATCH 255        /* batch elements per stacked call */
 #define D3F_NEIGHBOR_CAP 1024    /* max in-radius supports per query that can be ordered */
+#define D3F_TOPK_MAX 8192        /* most keypoints per cloud d3f_topk_records selects */
 #define D3F_NUM_KP_MAX 16        /* kernel points per KPConv (reference uses 15) */
 
 int d3f_version(void);
@@ -371,6 +372,32 @@ int d3f_pack_descriptors_to(const float* xyz, const float* desc, int ldd, int C,
                             int ldo, const int* N_dev, const int* lens_dev, int B, int group, int keep,
                             const long long* dst_ptrs_dev, const int* row_map_dev, void* stream);
 
+/* Keypoint selection: for every kept cloud of a stack the K records with the highest detection scores, in ascending score order --
+ *     sel = np.argsort(s, kind="stable")[-K:];  out = records[sel]                      (min(n, K) rows)
+ * which is what the reference does on the host after every sess.run: its testers order a fragment's rows by score
+ * (utils/tester.py:208-213, demo_registration.py:159-163: np.argsort(scores)) and every consumer keeps the tail
+ * (geometric_registration/evaluate.py:45-50 [-num_keypts:], utils/tester.py:283-284, demo_registration.py:249,261 [-50:]).
+ * Order of the keys: numpy's for float32 (-0.0 == +0.0, every NaN after +inf, all NaNs tied); ties in ascending row index, so among
+ * the rows whose score equals the K-th largest the HIGHEST rows are kept.  Rows are the reference's rows of the cloud.
+ * Inputs as d3f_pack_descriptors_to takes them, each with its own row stride in floats: xyz (ldx >= 3), desc (ldd >= C), score
+ * (lds >= 1) -- a finished record block `rec` of row stride ld is xyz = rec, desc = rec + 3, score = rec + 3 + C, all strides ld.
+ * The stack holds B clouds (lens_dev i32[B]; N bounds the stack's rows, N_dev optional as everywhere); a fragment is `group`
+ * consecutive clouds and its first `keep` are kept (d3f_pack_descriptors_to's rule); row_map_dev (optional) has that function's
+ * meaning: input row n is stack-global reference row row_map_dev[n], a cloud's rows stay inside its own range, and the row of a
+ * record is its reference row minus the cloud's start.  n_cap: upper bound of one cloud's rows, < 2^24 (rows of a cloud beyond it
+ * are not looked at); it plans the launch (workgroups per cloud, keys in LDS or through the workspace).
+ * Kept cloud j (stack order, ceil(B / group) * keep of them): rows out + j * K * ldo, [xyz | desc | score] of ldo >= C + 4 floats, the
+ * first count_dev[j] = min(n_j, K) rows written, the rest untouched; idx_out (optional) i32[., K] the reference row inside the
+ * cloud; count_dev (optional) i32[.].  `out` must not overlap the inputs.  One launch, asynchronous on `stream`, no allocation, no
+ * synchronisation; every data-dependent size is read on the device.  1 <= K <= D3F_TOPK_MAX.
+ * tickets_dev (optional) i32[kept clouds], ZERO before the first call and left zero by every call: with it a long cloud is split over
+ * up to 16 workgroups that hand their candidates to the last one to finish; calls that can overlap (different streams) need their own.
+ * NULL: one workgroup per cloud.  workspace >= d3f_topk_workspace_bytes(N, B, n_cap, K), else D3F_ERR_WORKSPACE. */
+size_t d3f_topk_workspace_bytes(int N, int B, int n_cap, int K);
+int d3f_topk_records(const float* xyz, int ldx, const float* desc, int ldd, int C, const float* score, int lds, int N,
+                     const int* N_dev, const int* lens_dev, int B, int group, int keep, const int* row_map_dev, int n_cap, int K,
+                     float* out, int ldo, int* idx_out, int* count_dev, int* tickets_dev, void* workspace, size_t workspace_bytes,
+                     void* stream);
 
 /* LDS-DMA form of the fp32 contractions (round 4): the operator of d3f_gemm_f32 / d3f_gemm_upsample_cat_f32 with the same
  * composite A operand as d3f_gemm_bf16 below -- A f32[., C1] (rows in place when idx == NULL, else the gathered rows x'[idx[m,0]],

@@ -35,6 +35,9 @@ def main():
     ap.add_argument("--slots", type=int, default=4)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--no-gather", action="store_true")
+    ap.add_argument("--keypoints", type=int, default=0,
+                    help="K > 0: keep, write and gather only every fragment's K highest-scoring records in ascending score order, selected "
+                         "on the device (what evaluate.py's [-num_keypts:] reads for any num_keypts <= K) instead of the full records")
     ap.add_argument("--gather-to", default="0", help="rank that receives the shards (default 0: gather at the end), or 'all'")
     ap.add_argument("--overlap-chunk", type=int, default=0,
                     help="exchange the shards in asynchronous chunks of this many fragments while they are produced (0: one "
@@ -84,8 +87,11 @@ def main():
         def load(i):
             return read_ply_xyz(os.path.join(a.fragments, ids[i]))
     t0 = time.perf_counter()
-    res = runner.run_sharded(ids, sizes, load, cfg, W, runner.gpu_engine_factory(a.slots, a.batch), runner.gpu_calibrate(cfg), dev,
-                             gather=not a.no_gather, save=runner.save_records_3dmatch(a.out), overlap_chunk=a.overlap_chunk,
+    kp = a.keypoints if a.keypoints > 0 else None
+    res = runner.run_sharded(ids, sizes, load, cfg, W, runner.gpu_engine_factory(a.slots, a.batch, keypoints=kp),
+                             runner.gpu_calibrate(cfg), dev, gather=not a.no_gather,
+                             save=runner.save_keypoints_3dmatch(a.out) if kp else runner.save_records_3dmatch(a.out),
+                             keep="keypoints" if kp else "first", overlap_chunk=a.overlap_chunk,
                              dst=None if a.gather_to == "all" else int(a.gather_to))
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
