@@ -17,6 +17,7 @@ PAD_NUM_SUPPORTS = -2147483648
 NEIGHBOR_CAP = 1024
 MAX_BATCH = 255
 TOPK_MAX = 8192
+PAIRS_KMAX = 1024
 
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
 
@@ -76,6 +77,9 @@ SIGNATURES = {
     "d3f_ransac_hypotheses": (_i, [_vp, _i, _vp, _i, _vp, _i, _f, _f, C.c_uint64, C.c_uint64, _i, _vp, _vp, _vp]),
     "d3f_ransac_draw": (_i, [C.c_uint64, C.c_uint64, _i, _i]),
     "d3f_neighbor_grid_score": (_i, [_vp, _sz, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp]),
+    "d3f_register_pairs_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "d3f_register_pairs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _i, _f, _f, _i, _i, C.c_uint64, _vp, _f] + [_vp] * 11
+                           + [_sz, _vp]),
     "d3f_gemm_pack_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_pack_f32t": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_f32t": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _sz,

@@ -202,16 +202,13 @@ __device__ void rg_horn(const double S[3][3], double R[3][3]) {
 
 #define RG_MAXN 8
 
-// T[h] = 12 floats (row-major 3x4 [R | t]); valid[h] = 1 iff the samples are distinct, every sample has a match, the
-// edge-length checker (if edge_sim > 0) and, after the fit, the distance checker (if dist_thr > 0) pass.
-__global__ void __launch_bounds__(256) rg_hypotheses_kernel(const float* __restrict__ src, int Ns, const float* __restrict__ tgt,
-                                                            int Nt, const int* __restrict__ nn, int n,
-                                                            float edge_sim, float dist_thr, unsigned long long seed,
-                                                            unsigned long long it0, int H, float* __restrict__ T,
-                                                            unsigned char* __restrict__ valid) {
-    const int h = blockIdx.x * 256 + threadIdx.x;
-    if (h >= H) return;
-    const unsigned long long it = it0 + (unsigned long long)h;
+// Hypothesis of iteration `it`, in two steps that every caller runs in this order.  A pure function of (seed, it) and the data:
+// every caller gets the same bits.  src / tgt: xyz rows of lds / ldt floats.
+struct RgSample { double s[RG_MAXN][3], t[RG_MAXN][3]; };
+// the sample: true iff the draws are distinct, every drawn point has a match and the edge-length checker (if edge_sim > 0) passes
+__device__ __forceinline__ bool rg_sample(const float* __restrict__ src, int lds, int Ns, const float* __restrict__ tgt, int ldt, int Nt,
+                                          const int* __restrict__ nn, int n, float edge_sim, unsigned long long seed,
+                                          unsigned long long it, RgSample& q) {
     int si[RG_MAXN], ti[RG_MAXN];
     bool ok = true;
     for (int d = 0; d < n; ++d) {
@@ -220,10 +217,10 @@ __global__ void __launch_bounds__(256) rg_hypotheses_kernel(const float* __restr
         if (ti[d] < 0 || ti[d] >= Nt) ok = false;
         for (int e = 0; e < d; ++e) if (si[e] == si[d]) ok = false;
     }
-    double s[RG_MAXN][3], t[RG_MAXN][3];
+    double (&s)[RG_MAXN][3] = q.s, (&t)[RG_MAXN][3] = q.t;
     if (ok) {
         for (int d = 0; d < n; ++d)
-            for (int c = 0; c < 3; ++c) { s[d][c] = (double)src[3 * (size_t)si[d] + c]; t[d][c] = (double)tgt[3 * (size_t)ti[d] + c]; }
+            for (int c = 0; c < 3; ++c) { s[d][c] = (double)src[(size_t)lds * si[d] + c]; t[d][c] = (double)tgt[(size_t)ldt * ti[d] + c]; }
         if (edge_sim > 0.f) {   // CorrespondenceCheckerBasedOnEdgeLength: every pair of edges similar in length both ways
             for (int a = 0; a < n && ok; ++a)
                 for (int b = a + 1; b < n; ++b) {
@@ -234,30 +231,54 @@ __global__ void __launch_bounds__(256) rg_hypotheses_kernel(const float* __restr
                 }
         }
     }
-    float out[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    if (ok) {
-        double ms[3] = {0, 0, 0}, mt[3] = {0, 0, 0};
-        for (int d = 0; d < n; ++d) for (int c = 0; c < 3; ++c) { ms[c] += s[d][c]; mt[c] += t[d][c]; }
-        for (int c = 0; c < 3; ++c) { ms[c] /= n; mt[c] /= n; }
-        double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-        for (int d = 0; d < n; ++d)
-            for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) S[a][b] += (s[d][a] - ms[a]) * (t[d][b] - mt[b]);
-        double R[3][3];
-        rg_horn(S, R);
-        double tr[3];
-        for (int a = 0; a < 3; ++a) tr[a] = mt[a] - (R[a][0] * ms[0] + R[a][1] * ms[1] + R[a][2] * ms[2]);
-        if (dist_thr > 0.f) {   // CorrespondenceCheckerBasedOnDistance on the aligned samples
-            for (int d = 0; d < n; ++d) {
-                double e2 = 0;
-                for (int a = 0; a < 3; ++a) {
-                    const double v = R[a][0] * s[d][0] + R[a][1] * s[d][1] + R[a][2] * s[d][2] + tr[a] - t[d][a];
-                    e2 += v * v;
-                }
-                if (sqrt(e2) > (double)dist_thr) ok = false;
+    return ok;
+}
+// the rigid fit of a sample that passed: out = 12 floats (row-major 3x4 [R | t]); true iff the distance checker (if dist_thr > 0) passes
+__device__ __forceinline__ bool rg_fit(const RgSample& q, int n, float dist_thr, float out[12]) {
+    const double (&s)[RG_MAXN][3] = q.s, (&t)[RG_MAXN][3] = q.t;
+    bool ok = true;
+    double ms[3] = {0, 0, 0}, mt[3] = {0, 0, 0};
+    for (int d = 0; d < n; ++d) for (int c = 0; c < 3; ++c) { ms[c] += s[d][c]; mt[c] += t[d][c]; }
+    for (int c = 0; c < 3; ++c) { ms[c] /= n; mt[c] /= n; }
+    double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    for (int d = 0; d < n; ++d)
+        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) S[a][b] += (s[d][a] - ms[a]) * (t[d][b] - mt[b]);
+    double R[3][3];
+    rg_horn(S, R);
+    double tr[3];
+    for (int a = 0; a < 3; ++a) tr[a] = mt[a] - (R[a][0] * ms[0] + R[a][1] * ms[1] + R[a][2] * ms[2]);
+    if (dist_thr > 0.f) {   // CorrespondenceCheckerBasedOnDistance on the aligned samples
+        for (int d = 0; d < n; ++d) {
+            double e2 = 0;
+            for (int a = 0; a < 3; ++a) {
+                const double v = R[a][0] * s[d][0] + R[a][1] * s[d][1] + R[a][2] * s[d][2] + tr[a] - t[d][a];
+                e2 += v * v;
             }
+            if (sqrt(e2) > (double)dist_thr) ok = false;
         }
-        for (int a = 0; a < 3; ++a) { out[4 * a] = (float)R[a][0]; out[4 * a + 1] = (float)R[a][1]; out[4 * a + 2] = (float)R[a][2]; out[4 * a + 3] = (float)tr[a]; }
     }
+    for (int a = 0; a < 3; ++a) { out[4 * a] = (float)R[a][0]; out[4 * a + 1] = (float)R[a][1]; out[4 * a + 2] = (float)R[a][2]; out[4 * a + 3] = (float)tr[a]; }
+    return ok;
+}
+// both steps: out is the identity when the sample fails, else the fit (whether or not the distance checker passes)
+__device__ __forceinline__ bool rg_hypothesis(const float* __restrict__ src, int lds, int Ns, const float* __restrict__ tgt, int ldt,
+                                              int Nt, const int* __restrict__ nn, int n, float edge_sim, float dist_thr,
+                                              unsigned long long seed, unsigned long long it, float out[12]) {
+    out[0] = 1; out[1] = 0; out[2] = 0; out[3] = 0; out[4] = 0; out[5] = 1; out[6] = 0; out[7] = 0; out[8] = 0; out[9] = 0; out[10] = 1; out[11] = 0;
+    RgSample q;
+    return rg_sample(src, lds, Ns, tgt, ldt, Nt, nn, n, edge_sim, seed, it, q) && rg_fit(q, n, dist_thr, out);
+}
+
+// T[h], valid[h]: rg_hypothesis of iteration it0 + h, one thread each.
+__global__ void __launch_bounds__(256) rg_hypotheses_kernel(const float* __restrict__ src, int Ns, const float* __restrict__ tgt,
+                                                            int Nt, const int* __restrict__ nn, int n,
+                                                            float edge_sim, float dist_thr, unsigned long long seed,
+                                                            unsigned long long it0, int H, float* __restrict__ T,
+                                                            unsigned char* __restrict__ valid) {
+    const int h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= H) return;
+    float out[12];
+    const bool ok = rg_hypothesis(src, 3, Ns, tgt, 3, Nt, nn, n, edge_sim, dist_thr, seed, it0 + (unsigned long long)h, out);
     for (int k = 0; k < 12; ++k) T[(size_t)h * 12 + k] = out[k];
     valid[h] = ok ? 1 : 0;
 }
@@ -279,4 +300,350 @@ extern "C" int d3f_ransac_hypotheses(const float* src, int Ns, const float* tgt,
 // host copy of the sampler (bindings / tests draw the very same indices)
 extern "C" int d3f_ransac_draw(uint64_t seed, uint64_t iteration, int d, int n) {
     return n > 0 ? rg_draw(seed, iteration, d, n) : -1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Batched registration: every pair of a scene in four launches (d3f_register_pairs)
+// ---------------------------------------------------------------------------------------------------------------------
+// What registration.register_keypoints does for ONE pair through a host loop -- mutual nearest descriptors, RANSAC on the
+// nearest features, the winner's correspondences -- for P pairs of keypoint blocks, with every decision taken on the device:
+//   rp_match_kernel       one workgroup per pair: both nearest-descriptor directions (the loop of rg_feature_nn_kernel with the
+//                         roles swapped for the second direction: t - s is the exact negation of s - t, so both passes see the
+//                         same d2 bits), mutual pairs in ascending source order, inliers of the mutual pairs under gt
+//   rp_hypotheses_kernel  one workgroup per pair walks the iterations RP_CHUNK at a time: rg_sample for all of them, rg_fit (the fp64
+//                         Horn fit, 100 x the cost of a sample) for the few that pass, gathered onto dense lanes; the valid ones are
+//                         appended in ITERATION order (ballot + prefix over the waves) until the pair's list holds max_validation
+//   rp_score_kernel       workgroup = (pair, 16 validated hypotheses): the pair's points in LDS, a brute-force scan per (hypothesis,
+//                         source point) with the metric, the radius test and the tie rule of nb_score_kernel; integer totals
+//   rp_select_kernel      one workgroup per pair: largest count, then smallest sumd2, then earliest iteration; one more scan
+//                         for the winner's correspondences
+// No workgroup waits for another, nothing depends on the order of arrival, and the number of launches does not depend on P.
+#define RP_SLICE 16   // validated hypotheses per workgroup of rp_score_kernel
+#define RP_CHUNK 1024 // iterations whose samples rp_hypotheses_kernel tests before it fits the ones that passed
+
+struct RpRows { int blk, r0, n; };
+// rows [count - min(count, nk), count) of block pairs[p][which] (evaluate.py:45-50: the tail in ascending score order); an index
+// outside [0, n_blocks) selects no rows
+__device__ __forceinline__ RpRows rp_rows(const int* __restrict__ count, const int* __restrict__ pairs, int p, int which, int n_blocks,
+                                          int K, int nk) {
+    RpRows r{0, 0, 0};
+    const int b = pairs[2 * (size_t)p + which];
+    if (b < 0 || b >= n_blocks) return r;
+    const int c = min(max(count[b], 0), K);
+    r.blk = b;
+    r.n = min(c, nk);
+    r.r0 = c - r.n;
+    return r;
+}
+
+// out[i] = argmin_j ||A_i - B_j||^2 for the rows of one pair (lowest j on ties, -1 without a candidate): the chain of
+// rg_feature_nn_kernel, B through the LDS tile, the whole workgroup walking A 256 rows at a time.
+template <int C>
+__device__ __forceinline__ void rp_nn_pass(const float* __restrict__ A, int Na, int lda, const float* __restrict__ B, int Nb, int ldb,
+                                           float* tile, int* out) {
+    for (int i0 = 0; i0 < Na; i0 += 256) {
+        const int i = i0 + threadIdx.x;
+        float a[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) a[c] = (i < Na) ? A[(size_t)i * lda + c] : 0.f;
+        float best = 3.402823466e38f;
+        int bj = -1;
+        for (int t0 = 0; t0 < Nb; t0 += RG_TB) {
+            const int nt = min(RG_TB, Nb - t0);
+            __syncthreads();
+            for (int e = threadIdx.x; e < nt * C; e += 256) tile[e] = B[(size_t)(t0 + e / C) * ldb + (e % C)];
+            __syncthreads();
+            for (int j = 0; j < nt; ++j) {
+                float d2 = 0.f;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const float d = a[c] - tile[j * C + c];
+                    d2 = fmaf(d, d, d2);
+                }
+                if (d2 < best) { best = d2; bj = t0 + j; }   // strict: ties keep the lowest column
+            }
+        }
+        if (i < Na) out[i] = bj;
+    }
+    __syncthreads();
+}
+
+// exclusive prefix of `flag` over the 256 threads of the workgroup in thread order; total = the workgroup's sum (wsum: 4 ints of LDS)
+__device__ __forceinline__ int rp_block_prefix(bool flag, int* wsum, int& total) {
+    const unsigned long long bal = __ballot(flag);
+    const int w = threadIdx.x >> 6;
+    if (d3f_lane() == 0) wsum[w] = __popcll(bal);
+    __syncthreads();
+    int base = 0;
+    total = 0;
+    for (int k = 0; k < 4; ++k) { const int c = wsum[k]; base += (k < w) ? c : 0; total += c; }
+    __syncthreads();
+    return base + __popcll(bal & d3f_lanemask_lt());
+}
+
+// p = M x + t with the fmaf nest of nb_score_kernel
+__device__ __forceinline__ void rp_apply(const float* __restrict__ M, float x, float y, float z, float& qx, float& qy, float& qz) {
+    qx = fmaf(M[0], x, fmaf(M[1], y, fmaf(M[2], z, M[3])));
+    qy = fmaf(M[4], x, fmaf(M[5], y, fmaf(M[6], z, M[7])));
+    qz = fmaf(M[8], x, fmaf(M[9], y, fmaf(M[10], z, M[11])));
+}
+// nb_score_kernel's squared distance: no contraction, (dx^2 + dy^2) + dz^2
+__device__ __forceinline__ float rp_d2(float qx, float qy, float qz, float x, float y, float z) {
+    const float dx = __fsub_rn(qx, x), dy = __fsub_rn(qy, y), dz = __fsub_rn(qz, z);
+    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+// nearest of the n points pts[3 * j ..] strictly inside r2, lowest j on ties (the scan is ascending); -1 for none.  The grid walk of
+// nb_score_kernel visits a superset of the points inside the radius and keeps the same minimum.
+__device__ __forceinline__ int rp_nearest(const float* pts, int n, float qx, float qy, float qz, float r2, float& bd2) {
+    int bidx = -1;
+    bd2 = 3.4e38f;
+    for (int j = 0; j < n; ++j) {
+        const float d2 = rp_d2(qx, qy, qz, pts[3 * j], pts[3 * j + 1], pts[3 * j + 2]);
+        if (d2 < r2 && d2 < bd2) { bd2 = d2; bidx = j; }
+    }
+    return bidx;
+}
+// xyz of `n` record rows into LDS, 3 floats per point
+__device__ __forceinline__ void rp_stage_xyz(const float* __restrict__ rec, int n, int ld, float* dst) {
+    for (int e = threadIdx.x; e < 3 * n; e += 256) dst[e] = rec[(size_t)(e / 3) * ld + (e % 3)];
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) rp_match_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
+                                                       const int* __restrict__ count, const int* __restrict__ pairs, int nk, int Kmax,
+                                                       const float* __restrict__ gt, float thr2, int* __restrict__ nn_st_out,
+                                                       int* __restrict__ mutual_count, int* __restrict__ mutual,
+                                                       int* __restrict__ gt_inliers) {
+    __shared__ float tile[RG_TB * C];
+    __shared__ int nn_st[D3F_PAIRS_KMAX], nn_ts[D3F_PAIRS_KMAX];
+    __shared__ int wsum[4];
+    __shared__ int n_gt;
+    const int p = blockIdx.x;
+    const RpRows a = rp_rows(count, pairs, p, 0, n_blocks, K, nk), b = rp_rows(count, pairs, p, 1, n_blocks, K, nk);
+    const float* S = kp + ((size_t)a.blk * K + a.r0) * ld;
+    const float* T = kp + ((size_t)b.blk * K + b.r0) * ld;
+    if (threadIdx.x == 0) n_gt = 0;
+    rp_nn_pass<C>(S + 3, a.n, ld, T + 3, b.n, ld, tile, nn_st);
+    rp_nn_pass<C>(T + 3, b.n, ld, S + 3, a.n, ld, tile, nn_ts);
+    int base = 0, mine_gt = 0;
+    for (int i0 = 0; i0 < a.n; i0 += 256) {
+        const int i = i0 + threadIdx.x;
+        const int j = (i < a.n) ? nn_st[i] : -1;
+        if (i < a.n) nn_st_out[(size_t)p * Kmax + i] = j;
+        const bool m = j >= 0 && j < b.n && nn_ts[j] == i;
+        int total;
+        const int slot = base + rp_block_prefix(m, wsum, total);
+        base += total;
+        if (m) {
+            if (mutual) { mutual[((size_t)p * Kmax + slot) * 2] = i; mutual[((size_t)p * Kmax + slot) * 2 + 1] = j; }
+            if (gt) {   // gt takes the TARGET frame into the SOURCE frame (evaluate.py:70-77)
+                float qx, qy, qz;
+                rp_apply(gt + (size_t)p * 12, T[(size_t)j * ld], T[(size_t)j * ld + 1], T[(size_t)j * ld + 2], qx, qy, qz);
+                mine_gt += rp_d2(qx, qy, qz, S[(size_t)i * ld], S[(size_t)i * ld + 1], S[(size_t)i * ld + 2]) < thr2 ? 1 : 0;
+            }
+        }
+    }
+    if (threadIdx.x == 0) mutual_count[p] = base;
+    if (mutual)   // padding rows
+        for (int e = 2 * base + threadIdx.x; e < 2 * Kmax; e += 256) mutual[(size_t)p * Kmax * 2 + e] = -1;
+    if (gt) {
+        if (mine_gt) atomicAdd(&n_gt, mine_gt);
+        __syncthreads();
+        if (threadIdx.x == 0) gt_inliers[p] = n_gt;
+    }
+}
+
+__global__ void __launch_bounds__(256) rp_hypotheses_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
+                                                            const int* __restrict__ count, const int* __restrict__ pairs, int nk, int Kmax,
+                                                            const int* __restrict__ nn_st, int n, float radius, float edge_sim,
+                                                            float dist_thr, unsigned long long seed, int max_iteration,
+                                                            int max_validation, float* __restrict__ Tlist, int* __restrict__ itlist,
+                                                            int* __restrict__ validations, int* __restrict__ iterations) {
+    __shared__ int wsum[4];
+    __shared__ int cand[RP_CHUNK];
+    const int p = blockIdx.x;
+    const RpRows a = rp_rows(count, pairs, p, 0, n_blocks, K, nk), b = rp_rows(count, pairs, p, 1, n_blocks, K, nk);
+    if (a.n < n || b.n < n || radius <= 0.f) {   // registration.py: nothing is tried
+        if (threadIdx.x == 0) { validations[p] = 0; iterations[p] = 0; }
+        return;
+    }
+    const float* S = kp + ((size_t)a.blk * K + a.r0) * ld;
+    const float* T = kp + ((size_t)b.blk * K + b.r0) * ld;
+    const int* nn = nn_st + (size_t)p * Kmax;
+    float* Tl = Tlist + (size_t)p * max_validation * 12;
+    int* il = itlist + (size_t)p * max_validation;
+    int nval = 0;
+    for (int it0 = 0; it0 < max_iteration && nval < max_validation; it0 += RP_CHUNK) {
+        // the cheap step for RP_CHUNK iterations: the ones whose sample passes, in iteration order
+        int ncand = 0, total;
+        for (int k = 0; k < RP_CHUNK; k += 256) {
+            const int it = it0 + k + threadIdx.x;
+            RgSample q;
+            const bool pass = it < max_iteration && rg_sample(S, ld, a.n, T, ld, b.n, nn, n, edge_sim, seed, (unsigned long long)it, q);
+            const int slot = ncand + rp_block_prefix(pass, wsum, total);
+            if (pass) cand[slot] = it;
+            ncand += total;
+        }
+        __syncthreads();
+        // the fit (fp64 Horn) on dense lanes: only for those; the place in the list comes from the iteration index, never from arrival
+        for (int c0 = 0; c0 < ncand && nval < max_validation; c0 += 256) {
+            const int c = c0 + threadIdx.x, it = c < ncand ? cand[c] : 0;
+            float out[12];
+            bool ok = false;
+            if (c < ncand) {
+                RgSample q;
+                rg_sample(S, ld, a.n, T, ld, b.n, nn, n, edge_sim, seed, (unsigned long long)it, q);
+                ok = rg_fit(q, n, dist_thr, out);
+            }
+            const int slot = nval + rp_block_prefix(ok, wsum, total);
+            if (ok && slot < max_validation) {
+                for (int k = 0; k < 12; ++k) Tl[(size_t)slot * 12 + k] = out[k];
+                il[slot] = it;
+                if (slot == max_validation - 1) iterations[p] = it + 1;
+            }
+            nval += total;
+        }
+    }
+    if (threadIdx.x == 0) {
+        validations[p] = min(nval, max_validation);
+        if (nval < max_validation) iterations[p] = max_iteration;
+    }
+}
+
+// grid (P, slices of RP_SLICE hypotheses).  cnt / sd2 [P, max_validation]: every (pair, hypothesis) has exactly one writer.
+__global__ void __launch_bounds__(256) rp_score_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
+                                                       const int* __restrict__ count, const int* __restrict__ pairs, int nk,
+                                                       const float* __restrict__ Tlist, const int* __restrict__ validations,
+                                                       int max_validation, float r2, int* __restrict__ cnt,
+                                                       unsigned long long* __restrict__ sd2) {
+    __shared__ float spt[3 * D3F_PAIRS_KMAX], tpt[3 * D3F_PAIRS_KMAX];
+    __shared__ float M[RP_SLICE * 12];
+    __shared__ int c_l[RP_SLICE];
+    __shared__ unsigned long long s_l[RP_SLICE];
+    const int p = blockIdx.x, v0 = blockIdx.y * RP_SLICE;
+    const int nv = min(validations[p] - v0, RP_SLICE);
+    if (nv <= 0) return;
+    const RpRows a = rp_rows(count, pairs, p, 0, n_blocks, K, nk), b = rp_rows(count, pairs, p, 1, n_blocks, K, nk);
+    rp_stage_xyz(kp + ((size_t)a.blk * K + a.r0) * ld, a.n, ld, spt);
+    rp_stage_xyz(kp + ((size_t)b.blk * K + b.r0) * ld, b.n, ld, tpt);
+    if (threadIdx.x < nv * 12) M[threadIdx.x] = Tlist[((size_t)p * max_validation + v0) * 12 + threadIdx.x];
+    if (threadIdx.x < RP_SLICE) { c_l[threadIdx.x] = 0; s_l[threadIdx.x] = 0ull; }
+    __syncthreads();
+    for (int e = threadIdx.x; e < nv * a.n; e += 256) {
+        const int v = e / a.n, i = e - v * a.n;
+        float qx, qy, qz, bd2;
+        rp_apply(M + 12 * v, spt[3 * i], spt[3 * i + 1], spt[3 * i + 2], qx, qy, qz);
+        if (rp_nearest(tpt, b.n, qx, qy, qz, r2, bd2) >= 0) {
+            atomicAdd(&c_l[v], 1);
+            atomicAdd(&s_l[v], (unsigned long long)((double)bd2 * 4294967296.0));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < nv) {
+        cnt[(size_t)p * max_validation + v0 + threadIdx.x] = c_l[threadIdx.x];
+        sd2[(size_t)p * max_validation + v0 + threadIdx.x] = s_l[threadIdx.x];
+    }
+}
+
+// better(a, b): larger count, then smaller sumd2, then earlier place in the list (= earlier iteration)
+struct RpBest { int c; unsigned long long s; int v; };
+__device__ __forceinline__ bool rp_better(const RpBest& x, const RpBest& y) {
+    if (x.c != y.c) return x.c > y.c;
+    if (x.s != y.s) return x.s < y.s;
+    return x.v < y.v;
+}
+
+__global__ void __launch_bounds__(256) rp_select_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
+                                                        const int* __restrict__ count, const int* __restrict__ pairs, int nk, int Kmax,
+                                                        const float* __restrict__ Tlist, const int* __restrict__ itlist,
+                                                        const int* __restrict__ cnt, const unsigned long long* __restrict__ sd2,
+                                                        const int* __restrict__ validations, int max_validation, float r2,
+                                                        float* __restrict__ T_out, int* __restrict__ inliers,
+                                                        unsigned long long* __restrict__ sumd2, int* __restrict__ best_iteration,
+                                                        int* __restrict__ nearest) {
+    __shared__ float tpt[3 * D3F_PAIRS_KMAX];
+    __shared__ RpBest red[256];
+    __shared__ float M[12];
+    const int p = blockIdx.x, V = validations[p];
+    RpBest me{-1, ~0ull, 0x7fffffff};
+    for (int v = threadIdx.x; v < V; v += 256) {
+        const RpBest c{cnt[(size_t)p * max_validation + v], sd2[(size_t)p * max_validation + v], v};
+        if (rp_better(c, me)) me = c;
+    }
+    red[threadIdx.x] = me;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s && rp_better(red[threadIdx.x + s], red[threadIdx.x])) red[threadIdx.x] = red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const RpBest w = red[0];
+    int* near = nearest + (size_t)p * Kmax;
+    if (V <= 0) {   // nothing validated: the identity, no correspondences
+        if (threadIdx.x < 12) T_out[(size_t)p * 12 + threadIdx.x] = (threadIdx.x % 5 == 0) ? 1.f : 0.f;
+        if (threadIdx.x == 0) { inliers[p] = 0; sumd2[p] = 0ull; best_iteration[p] = -1; }
+        for (int i = threadIdx.x; i < Kmax; i += 256) near[i] = -1;
+        return;
+    }
+    const RpRows a = rp_rows(count, pairs, p, 0, n_blocks, K, nk), b = rp_rows(count, pairs, p, 1, n_blocks, K, nk);
+    const float* S = kp + ((size_t)a.blk * K + a.r0) * ld;
+    rp_stage_xyz(kp + ((size_t)b.blk * K + b.r0) * ld, b.n, ld, tpt);
+    if (threadIdx.x < 12) T_out[(size_t)p * 12 + threadIdx.x] = M[threadIdx.x] = Tlist[((size_t)p * max_validation + w.v) * 12 + threadIdx.x];
+    if (threadIdx.x == 0) { inliers[p] = w.c; sumd2[p] = w.s; best_iteration[p] = itlist[(size_t)p * max_validation + w.v]; }
+    __syncthreads();
+    for (int i = threadIdx.x; i < Kmax; i += 256) {
+        int j = -1;
+        if (i < a.n) {
+            float qx, qy, qz, bd2;
+            rp_apply(M, S[(size_t)i * ld], S[(size_t)i * ld + 1], S[(size_t)i * ld + 2], qx, qy, qz);
+            j = rp_nearest(tpt, b.n, qx, qy, qz, r2, bd2);
+        }
+        near[i] = j;
+    }
+}
+
+static inline int rp_kmax(int K, int num_keypts) { return (num_keypts > 0 && num_keypts < K) ? num_keypts : K; }
+
+extern "C" size_t d3f_register_pairs_workspace_bytes(int P, int K, int num_keypts, int max_validation) {
+    if (P < 0 || K < 1 || max_validation < 1) return 0;
+    const size_t p = (size_t)(P > 0 ? P : 1), pv = p * (size_t)max_validation;
+    return d3f_align(p * (size_t)rp_kmax(K, num_keypts) * 4) + d3f_align(pv * 48) + 2 * d3f_align(pv * 4) + d3f_align(pv * 8) + 256;
+}
+
+extern "C" int d3f_register_pairs(const float* kp, int n_blocks, int K, int ld, int C, const int* count_dev, const int* pairs_dev, int P,
+                                  int num_keypts, float max_correspondence_distance, int ransac_n, float edge_similarity,
+                                  float checker_distance, int max_iteration, int max_validation, uint64_t seed, const float* gt,
+                                  float distance_threshold, float* T_out, int* inliers, uint64_t* sumd2, int* validations,
+                                  int* iterations, int* best_iteration, int* mutual_count, int* nearest, int* mutual, int* gt_inliers,
+                                  void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (P < 0 || n_blocks < 1 || K < 1 || (C != 16 && C != 32 && C != 64) || ld < C + 4) return D3F_ERR_ARG;
+    const int Kmax = rp_kmax(K, num_keypts);
+    if (Kmax > D3F_PAIRS_KMAX || ransac_n < 3 || ransac_n > RG_MAXN) return D3F_ERR_ARG;
+    if (max_iteration < 0 || max_iteration > (1 << 30) || max_validation < 1 || max_validation > (1 << 20)) return D3F_ERR_ARG;
+    if (!(max_correspondence_distance == max_correspondence_distance) || !(distance_threshold == distance_threshold)) return D3F_ERR_ARG;
+    if (P == 0) return D3F_OK;
+    if (!kp || !count_dev || !pairs_dev || !T_out || !inliers || !sumd2 || !validations || !iterations || !best_iteration ||
+        !mutual_count || !nearest || (gt && !gt_inliers))
+        return D3F_ERR_ARG;
+    if (!workspace || workspace_bytes < d3f_register_pairs_workspace_bytes(P, K, num_keypts, max_validation)) return D3F_ERR_WORKSPACE;
+    D3fArena ar(workspace, workspace_bytes);
+    const size_t pv = (size_t)P * max_validation;
+    int* nn_st = ar.take<int>((size_t)P * Kmax);
+    float* Tlist = ar.take<float>(pv * 12);
+    int* itlist = ar.take<int>(pv);
+    int* cnt = ar.take<int>(pv);
+    unsigned long long* sd2 = ar.take<unsigned long long>(pv);
+    if (!ar.ok) return D3F_ERR_WORKSPACE;
+    const float r = max_correspondence_distance, thr2 = distance_threshold * distance_threshold;
+    if (C == 16) rp_match_kernel<16><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, gt, thr2, nn_st, mutual_count, mutual, gt_inliers);
+    else if (C == 32) rp_match_kernel<32><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, gt, thr2, nn_st, mutual_count, mutual, gt_inliers);
+    else rp_match_kernel<64><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, gt, thr2, nn_st, mutual_count, mutual, gt_inliers);
+    rp_hypotheses_kernel<<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, nn_st, ransac_n, r, edge_similarity,
+                                                checker_distance, seed, max_iteration, max_validation, Tlist, itlist, validations, iterations);
+    rp_score_kernel<<<dim3(P, d3f_cdiv(max_validation, RP_SLICE)), 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Tlist,
+                                                                                   validations, max_validation, r * r, cnt, sd2);
+    rp_select_kernel<<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, Tlist, itlist, cnt, sd2, validations,
+                                            max_validation, r * r, T_out, inliers, (unsigned long long*)sumd2, best_iteration, nearest);
+    D3F_LAUNCH_CHECK();
+    return D3F_OK;
 }

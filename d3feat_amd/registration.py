@@ -6,6 +6,9 @@
                                             (evaluate.py:93-99, demo_registration.py:184-192)
     register_keypoints(src_rec, tgt_rec)    both of them on the last num_keypts rows of two keypoint record blocks
                                             (evaluate.py:45-50,67,93-99), the records never leaving the device
+    register_pairs(kp, count, pairs, ...)   register_keypoints for every pair of a scene's fragments in one call (evaluate.py:150-156):
+                                            four launches, no read-back in between, capturable; scene_pairs, stack_keypoints,
+                                            EVALUATE_3DMATCH go with it
 
 Every computation is a kernel of libd3feat_amd.so (csrc/registration.hip, csrc/radius_neighbors.hip); numpy / torch only
 move data and run the host loop over batches of hypotheses.  Open3D's own random stream is unspecified, so results are
@@ -142,4 +145,137 @@ def register_keypoints(src_records, tgt_records, num_keypts=None, device=None, *
     (s, t), w = blocks, blocks[0].shape[1]
     out = ransac_feature_matching(s[:, :3], t[:, :3], s[:, 3:w - 1], t[:, 3:w - 1], device=dev, **ransac_kw)
     out["correspondences"] = build_correspondence(s[:, 3:w - 1], t[:, 3:w - 1], device=dev)
+    return out
+
+
+# ---- every pair of a scene in one call (geometric_registration/evaluate.py:150-156) -------------------------------------------
+# evaluate.py:93-99: the call the reference makes for every pair (compat/open3d spells it for one pair)
+EVALUATE_3DMATCH = dict(max_correspondence_distance=0.05, ransac_n=3, edge_similarity=0.9, checker_distance=0.05,
+                        max_iteration=50000, max_validation=1000)
+PAIRS_PER_CALL = 4096
+
+
+def scene_pairs(n, device=None):
+    """All pairs id1 < id2 of n fragments in the order of evaluate.py:154-155 -> device i32[n (n - 1) / 2, 2]."""
+    iu = np.triu_indices(int(n), 1)
+    return torch.from_numpy(np.stack(iu, 1).astype(np.int32).reshape(-1, 2)).to(_dev(device))
+
+
+def stack_keypoints(blocks, K=None, device=None):
+    """A list of [k_i, ld] keypoint record blocks (what FragmentEngine.fetch(slot, keypoints=True) returns per fragment, ascending
+    score order) -> (kp f32[n, K, ld], count i32[n]) on the device; a block longer than K keeps its LAST K rows."""
+    blocks = [b if isinstance(b, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32)) for b in blocks]
+    if not blocks or any(b.dim() != 2 or b.shape[1] != blocks[0].shape[1] for b in blocks):
+        raise ValueError("stack_keypoints: blocks of shapes %s" % ([tuple(b.shape) for b in blocks],))
+    dev = _dev(device) if device is not None or not blocks[0].is_cuda else blocks[0].device
+    K = int(K) if K is not None else max(b.shape[0] for b in blocks)
+    kp = torch.zeros((len(blocks), max(K, 1), blocks[0].shape[1]), dtype=torch.float32, device=dev)
+    for f, b in enumerate(blocks):
+        b = b[max(b.shape[0] - K, 0):]
+        kp[f, :b.shape[0]].copy_(b, non_blocking=True)
+    count = torch.tensor([min(b.shape[0], K) for b in blocks], dtype=torch.int32).to(dev)
+    return kp, count
+
+
+class PairRegistration:
+    """Result of register_pairs: DEVICE tensors, one row per pair.
+    T f32[P,3,4] ([R | t] of the winner, identity without one), inliers i32[P], sumd2 i64[P] (2^-32 units), validations i32[P],
+    iterations i32[P], best_iteration i32[P] (-1: none), mutual_count i32[P], nearest i32[P,Kmax] (target row of every source row
+    under the winner, -1: none); mutual i32[P,Kmax,2] / gt_inliers i32[P] when asked for.  Rows are numbered inside the rows a
+    pair uses (the last min(count, num_keypts) of a block)."""
+    FIELDS = ("T", "inliers", "sumd2", "validations", "iterations", "best_iteration", "mutual_count", "nearest", "mutual", "gt_inliers")
+
+    def __init__(self, P, Kmax, device, correspondences, gt):
+        i32 = dict(dtype=torch.int32, device=device)
+        self.P, self.Kmax = P, Kmax
+        self.T = torch.empty((P, 3, 4), dtype=torch.float32, device=device)
+        self.inliers, self.validations, self.iterations = (torch.empty((P,), **i32) for _ in range(3))
+        self.best_iteration, self.mutual_count = torch.empty((P,), **i32), torch.empty((P,), **i32)
+        self.sumd2 = torch.empty((P,), dtype=torch.int64, device=device)
+        self.nearest = torch.empty((P, Kmax), **i32)
+        self.mutual = torch.empty((P, Kmax, 2), **i32) if correspondences else None
+        self.gt_inliers = torch.empty((P,), **i32) if gt else None
+        self.ns = self.nt = None
+
+    def _host(self):
+        # one read-back of the whole result, kept until the next register_pairs(out=self)
+        if self._cache is None:
+            self._cache = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS + ("ns", "nt") if getattr(self, k) is not None}
+        return self._cache
+
+    _cache = None
+
+    def host(self, p):
+        """The dict register_keypoints returns for pair p (plus best_iteration, and inlier_ratio when gt was given)."""
+        h = self._host()
+        Ns, cnt = int(h["ns"][p]), np.int64(h["inliers"][p])
+        sd2 = np.float64(h["sumd2"][p]) / 4294967296.0
+        near = h["nearest"][p, :Ns]
+        sel = np.nonzero(near >= 0)[0]
+        M = np.eye(4)
+        M[:3, :4] = h["T"][p].astype(np.float64)
+        out = dict(transformation=M, fitness=float(cnt) / Ns if Ns else 0.0, inlier_rmse=float(np.sqrt(sd2 / np.maximum(cnt, 1))),
+                   correspondence_set=np.stack([sel, near[sel]], 1).astype(np.int64), iterations=int(h["iterations"][p]),
+                   validations=int(h["validations"][p]), best_iteration=int(h["best_iteration"][p]))
+        k = int(h["mutual_count"][p])
+        if "mutual" in h:
+            out["correspondences"] = h["mutual"][p, :k].astype(np.int64)
+        if "gt_inliers" in h:
+            out["gt_inliers"] = int(h["gt_inliers"][p])
+            out["inlier_ratio"] = out["gt_inliers"] / k if k else 0.0
+        return out
+
+
+def register_pairs(kp, count, pairs, max_correspondence_distance, num_keypts=None, ransac_n=4, edge_similarity=0.9,
+                   checker_distance=None, max_iteration=100000, max_validation=100, seed=0, gt=None, distance_threshold=0.10,
+                   correspondences=False, out=None):
+    """register_keypoints for P pairs of keypoint blocks in one call: kp f32[n_blocks, K, ld] ([xyz | desc | score] rows in ascending
+    score order, keypoints.topk_records / stack_keypoints), count i32[n_blocks], pairs i32[P, 2] (source, target) block indices, all on
+    the device.  Four launches per PAIRS_PER_CALL pairs, no read-back and no host decision in between (capturable: pass the previous
+    result as `out`); per pair bit-identical to register_keypoints(kp[a, :count[a]], kp[b, :count[b]], num_keypts, ...) -- the keywords
+    are ransac_feature_matching's.  gt f32[P, 3, 4] (target -> source) adds gt_inliers (evaluate.py:70-77, distance_threshold);
+    correspondences=True adds the mutually closest pairs themselves.  -> PairRegistration (device tensors; .host(p) for a dict)."""
+    lib = _lib.load()
+    kp = ops._req(kp, torch.float32, "kp", 3)
+    count = ops._req(count, torch.int32, "count", 1)
+    pairs = ops._req(pairs, torch.int32, "pairs", 2)
+    dev = kp.device
+    if not kp.is_contiguous() or not count.is_contiguous() or not pairs.is_contiguous() or pairs.shape[1] != 2:
+        raise ValueError("register_pairs: kp, count and pairs must be contiguous, pairs [P, 2]")
+    n_blocks, K, ld = kp.shape
+    C = ld - 4
+    Kmax = min(K, int(num_keypts)) if num_keypts is not None else K
+    if count.shape[0] != n_blocks or n_blocks < 1 or Kmax < 1:
+        raise ValueError("register_pairs: kp %s, count %s, num_keypts %s" % (tuple(kp.shape), tuple(count.shape), num_keypts))
+    if Kmax > _lib.PAIRS_KMAX or C not in (16, 32, 64) or not 3 <= int(ransac_n) <= 8:
+        raise ValueError("register_pairs takes up to %d rows per block, descriptors of 16, 32 or 64 floats and ransac_n in 3..8 (got %d "
+                         "rows, %d floats, ransac_n %s): use register_keypoints for one pair of larger blocks"
+                         % (_lib.PAIRS_KMAX, Kmax, C, ransac_n))
+    P = pairs.shape[0]
+    if gt is not None:
+        gt = ops._req(gt, torch.float32, "gt", 3)
+        if tuple(gt.shape) != (P, 3, 4) or not gt.is_contiguous():
+            raise ValueError("register_pairs: gt of shape %s for %d pairs" % (tuple(gt.shape), P))
+    if out is None:
+        out = PairRegistration(P, Kmax, dev, correspondences, gt is not None)
+    elif (out.P, out.Kmax, out.mutual is not None, out.gt_inliers is not None) != (P, Kmax, bool(correspondences), gt is not None):
+        raise ValueError("register_pairs: out= was made for another call")
+    out._cache = None
+    # rows each pair uses (plumbing for host(): fitness = inliers / Ns)
+    used = count.clamp(0, Kmax)
+    out.ns, out.nt = used[pairs[:, 0].long()], used[pairs[:, 1].long()]
+    st = ops._stream(dev)
+    nk, mv = int(num_keypts) if num_keypts is not None else 0, int(max_validation)
+    for p0 in range(0, P, PAIRS_PER_CALL):
+        n = min(PAIRS_PER_CALL, P - p0)
+        ws = ops.workspace(lib.d3f_register_pairs_workspace_bytes(n, K, nk, mv), dev)
+        s = slice(p0, p0 + n)
+        rc = lib.d3f_register_pairs(
+            kp.data_ptr(), n_blocks, K, ld, C, count.data_ptr(), pairs[s].data_ptr(), n, nk, float(max_correspondence_distance),
+            int(ransac_n), float(edge_similarity or 0.0), float(checker_distance or 0.0), int(max_iteration), mv, int(seed),
+            gt[s].data_ptr() if gt is not None else None, float(distance_threshold), out.T[s].data_ptr(), out.inliers[s].data_ptr(),
+            out.sumd2[s].data_ptr(), out.validations[s].data_ptr(), out.iterations[s].data_ptr(), out.best_iteration[s].data_ptr(),
+            out.mutual_count[s].data_ptr(), out.nearest[s].data_ptr(), out.mutual[s].data_ptr() if correspondences else None,
+            out.gt_inliers[s].data_ptr() if gt is not None else None, ws.data_ptr(), ws.numel(), st)
+        _lib.check(rc, "register_pairs")
     return out

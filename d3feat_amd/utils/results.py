@@ -77,3 +77,59 @@ def save_3dmatch_keypoints(root, anc_id, kp_records):
         np.save(p, np.ascontiguousarray(arr))
         out.append(p + ".npy")
     return out
+
+
+# ---- the files of geometric_registration/evaluate.py -------------------------------------------------------------------------
+def read_gt_log(path):
+    """A gt.log (blocks of `id1 \\t id2 \\t n` + four rows of a 4x4 matrix) -> {"id1_id2": f64[4,4]}  (geometric_registration/
+    utils.py:20-35).  The blocks write_registration_log writes parse the same way."""
+    with open(path) as f:
+        content = f.readlines()
+    result = {}
+    for i in range(0, len(content) - 4, 5):
+        head = content[i].replace("\n", "").split("\t")[0:3]
+        trans = np.zeros([4, 4])
+        for r in range(4):
+            trans[r] = [float(x) for x in content[i + 1 + r].replace("\n", "").split("\t")[0:4]]
+        result["%d_%d" % (int(head[0]), int(head[1]))] = trans
+    return result
+
+
+def write_registration_log(path, pairs, transformations):
+    """Appends the .log blocks of evaluate.py:101-110: per pair (id1, id2) the header `id1 \\t id2 \\t  37` and the four rows of the
+    INVERSE of the estimated transformation (source -> target as register_pairs / register_keypoints return it)."""
+    with open(path, "a+") as f:
+        for (id1, id2), T in zip(pairs, transformations):
+            trans = np.linalg.inv(np.asarray(T, dtype=np.float64))
+            f.write(f'{int(id1)}\t {int(id2)}\t  37\n')
+            for r in range(4):
+                f.write(f"{trans[r, 0]}\t {trans[r, 1]}\t {trans[r, 2]}\t {trans[r, 3]}\t \n")
+
+
+def write_pair_results(directory, pairs, num_inliers, inlier_ratio, gt_flag):
+    """The cloud_bin_<s>_cloud_bin_<t>.rt.txt files of evaluate.py:113-115, one per pair.  Returns the rows
+    [num_inliers, inlier_ratio, gt_flag] as evaluate.py:203-204 reads them back (the ratio at the 8 decimals of the file)."""
+    os.makedirs(directory, exist_ok=True)
+    rows = []
+    for (id1, id2), n, r, g in zip(pairs, num_inliers, inlier_ratio, gt_flag):
+        s, t = "cloud_bin_%d" % int(id1), "cloud_bin_%d" % int(id2)
+        line = f"{s}\t{t}\t{int(n)}\t{float(r):.8f}\t{int(g)}"
+        with open(os.path.join(directory, f"{s}_{t}.rt.txt"), "w+") as f:
+            f.write(line)
+        nums = line.split("\t")[2:5]
+        rows.append([int(nums[0]), float(nums[1]), int(nums[2])])
+    return rows
+
+
+def feature_matching_recall(rows, inlier_ratio=0.05):
+    """Per-scene figures of evaluate.py:200-219 from rows [num_inliers, inlier_ratio, gt_flag]: -> dict(correct, gt, recall in
+    percent, ave_num_inliers, ave_inlier_ratio) -- as there, the averages divide the sums over the ground-truth pairs by the
+    number of pairs above the ratio."""
+    result = np.array(rows, dtype=np.float64).reshape(-1, 3)
+    gt_results = int(np.sum(result[:, 2] == 1))
+    pred_results = int(np.sum(result[:, 1] > inlier_ratio))
+    zeros = np.zeros(result.shape[0])
+    div = lambda a: float(a / pred_results) if pred_results else 0.0
+    return dict(correct=pred_results, gt=gt_results, recall=float(pred_results / gt_results) * 100 if gt_results else 0.0,
+                ave_num_inliers=div(np.sum(np.where(result[:, 2] == 1, result[:, 0], zeros))),
+                ave_inlier_ratio=div(np.sum(np.where(result[:, 2] == 1, result[:, 1], zeros))))

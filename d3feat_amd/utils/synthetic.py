@@ -62,3 +62,30 @@ def lidar_sweep(seed=0, n_raw=120000, rings=64):
     pts = dirs * t[:, None]
     pts += rng.normal(scale=0.01, size=pts.shape)
     return pts.astype(np.float32)
+
+
+def scene(seed, n_frag=8, K=250, edge=3.0, crop=1.1, noise=0.003, dnoise=0.05, outliers=0.3):
+    """n_frag keypoint blocks [xyz | 32-d unit desc | score] cut out of ONE room, each in its own frame; poses[f] takes
+    fragment f into the world.  gt for pair (a, b), target -> source: inv(poses[a]) @ poses[b]."""
+    rng = np.random.default_rng(seed)
+    world = room_fragment(seed, n_raw=40000, edge=edge).astype(np.float64)
+    wdesc = rng.standard_normal((len(world), 32)); wdesc /= np.linalg.norm(wdesc, axis=1, keepdims=True)
+    wscore = rng.random(len(world))
+    lo, hi = world.min(0), world.max(0)
+    cent = lo + (hi - lo) * (0.25 + 0.5 * rng.random((n_frag, 3)))
+    blocks, poses = [], []
+    for f in range(n_frag):
+        inside = np.nonzero(np.linalg.norm(world - cent[f], axis=1) < crop)[0]
+        s = wscore[inside] + 0.15 * rng.random(len(inside))      # detection repeats across fragments, not exactly
+        sel = inside[np.argsort(s, kind="stable")[-K:]]
+        q, _ = np.linalg.qr(rng.standard_normal((3, 3))); R = q * np.sign(np.linalg.det(q)); t = rng.uniform(-1, 1, 3)
+        xyz = (world[sel] - t) @ R + rng.normal(scale=noise, size=(len(sel), 3))
+        d = wdesc[sel] + dnoise * rng.standard_normal((len(sel), 32))
+        bad = rng.random(len(sel)) < outliers
+        d[bad] = rng.standard_normal((int(bad.sum()), 32))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        sc = np.sort(rng.random(len(sel)))
+        blocks.append(np.concatenate([xyz, d, sc[:, None]], 1).astype(np.float32))
+        M = np.eye(4); M[:3, :3] = R; M[:3, 3] = t
+        poses.append(M)
+    return blocks, poses

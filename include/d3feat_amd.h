@@ -43,6 +43,7 @@ extern "C" {
 #define D3F_MAX_BATCH 255        /* batch elements per stacked call */
 #define D3F_NEIGHBOR_CAP 1024    /* max in-radius supports per query that can be ordered */
 #define D3F_TOPK_MAX 8192        /* most keypoints per cloud d3f_topk_records selects */
+#define D3F_PAIRS_KMAX 1024      /* most rows of one keypoint block d3f_register_pairs uses */
 #define D3F_NUM_KP_MAX 16        /* kernel points per KPConv (reference uses 15) */
 
 int d3f_version(void);
@@ -494,6 +495,38 @@ int d3f_ransac_draw(uint64_t seed, uint64_t iteration, int d, int n);
  * nearest_dev i32[Ns] (optional) the correspondences under hypothesis 0. */
 int d3f_neighbor_grid_score(const void* grid, size_t grid_bytes, int Nt, const float* src, int Ns, const float* T, int V,
                             float radius, int* count_dev, uint64_t* sumd2_dev, int* nearest_dev, void* stream);
+
+/* Registration of P pairs of keypoint blocks in four launches, whatever P is (geometric_registration/evaluate.py:150-156: every
+ * pair id1 < id2 of a scene's fragments): for each pair what d3f_feature_nn (both directions) + d3f_mutual_matches +
+ * d3f_ransac_hypotheses + d3f_neighbor_grid_score compute through a host loop, bit for bit, with no host read-back and no
+ * host-side decision between the launches -- so the call can be captured in a HIP graph.
+ * kp f32[n_blocks, K, ld]: rows [xyz | C-d descriptor | score] in ascending score order (d3f_topk_records' blocks), ld >= C + 4,
+ * C in {16, 32, 64}; count_dev i32[n_blocks] rows written per block; pairs_dev i32[P, 2] block indices (source, target; equal
+ * indices allowed, an index outside [0, n_blocks) selects an empty block).  Pair (a, b) uses the LAST min(count, num_keypts) rows of
+ * each block (evaluate.py:45-50; num_keypts <= 0: all K), Ns source and Nt target rows; Kmax = min(K, num_keypts) <=
+ * D3F_PAIRS_KMAX, else D3F_ERR_ARG (larger blocks: the single-pair entry points above).
+ *   mutual_count i32[P], mutual (optional) i32[P, Kmax, 2]: the mutually closest descriptor pairs (i, j) in ascending i (evaluate.py:
+ *     21-26), padding -1; nearest descriptors are argmin of the fp32 chain of d3f_feature_nn, lowest index on ties.
+ *   gt (optional) f32[P, 12], row-major [R | t] taking the TARGET frame into the SOURCE frame; gt_inliers i32[P] (required with gt):
+ *     mutual pairs with |s_i - (R t_j + t)| < distance_threshold (evaluate.py:70-77), fp32, d3f_neighbor_grid_score's metric.
+ *   RANSAC exactly as d3f_ransac_hypotheses defines iteration it = 0, 1, ... for (seed, it) on the source rows, the target rows and
+ *     the source -> target nearest descriptors: the first max_validation valid iterations below max_iteration are scored as
+ *     d3f_neighbor_grid_score scores them (nearest target point strictly inside max_correspondence_distance, ties to the lowest
+ *     index); the winner has the largest count, then the smallest sumd2, then the smallest iteration.
+ *     T_out f32[P, 12], inliers i32[P], sumd2 u64[P] (2^-32 units), best_iteration i32[P] (-1: none), nearest i32[P, Kmax] (the
+ *     target row of every source row under the winner, -1 for none and for padding), validations i32[P] (hypotheses scored),
+ *     iterations i32[P] (the index after the max_validation-th valid iteration, else max_iteration).
+ *     Ns < ransac_n, Nt < ransac_n or max_correspondence_distance <= 0: identity, every count 0, best_iteration -1.
+ * 3 <= ransac_n <= 8, 0 <= max_iteration <= 2^30, 1 <= max_validation <= 2^20; every size is checked before the first launch
+ * (D3F_ERR_ARG), workspace >= d3f_register_pairs_workspace_bytes(P, K, num_keypts, max_validation), else D3F_ERR_WORKSPACE
+ * (64 bytes per pair and validation).  Asynchronous on `stream`, no allocation, no synchronisation. */
+size_t d3f_register_pairs_workspace_bytes(int P, int K, int num_keypts, int max_validation);
+int d3f_register_pairs(const float* kp, int n_blocks, int K, int ld, int C, const int* count_dev, const int* pairs_dev, int P,
+                       int num_keypts, float max_correspondence_distance, int ransac_n, float edge_similarity,
+                       float checker_distance, int max_iteration, int max_validation, uint64_t seed, const float* gt,
+                       float distance_threshold, float* T_out, int* inliers, uint64_t* sumd2, int* validations, int* iterations,
+                       int* best_iteration, int* mutual_count, int* nearest, int* mutual, int* gt_inliers, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

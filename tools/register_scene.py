@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Register every fragment pair of one 3DMatch scene on the GPU, as geometric_registration/evaluate.py does pair by pair on the host.
+
+Reads the `keypoints/<scene>/cloud_bin_<k>.npy` and `descriptors/<scene>/cloud_bin_<k>.D3Feat.npy` files that
+utils.results.save_3dmatch_keypoints / save_3dmatch_results wrote under --root (rows in ascending score order), takes the last
+--num-keypts rows of every fragment (evaluate.py:45-50), registers all pairs id1 < id2 with ONE registration.register_pairs call at
+registration.EVALUATE_3DMATCH (evaluate.py:93-99) and writes, under --out:
+
+    <desc_name>.log                               the .log blocks of evaluate.py:101-110 (inverse transforms), pairs of gt.log only
+    cloud_bin_<s>_cloud_bin_<t>.rt.txt            num_inliers, inlier_ratio, gt_flag of every pair (evaluate.py:113-115)
+
+and prints the recall line of evaluate.py:200-219.  Without --gt no pair has a ground truth (gt_flag 0 everywhere, as evaluate.py:
+60-65 treats a pair that gt.log does not list) and every pair goes into the .log.
+
+    python tools/register_scene.py --root RESULTS --scene sun3d-hotel_umd-maryland_hotel3 --gt gt.log --out OUT
+"""
+import argparse
+import json
+import os
+import re
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from d3feat_amd import registration as reg
+from d3feat_amd.utils import results
+
+
+def load_scene(root, scene, desc_name, num_keypts):
+    """-> list of f32[k, 3 + C + 1] record blocks, fragment k = cloud_bin_<k> (the score column is not stored with the keypoints:
+    it carries the row number, which is ascending as the scores are)."""
+    kdir, ddir = os.path.join(root, "keypoints", scene), os.path.join(root, "descriptors", scene)
+    ids = sorted(int(m.group(1)) for m in (re.fullmatch(r"cloud_bin_(\d+)\.npy", f) for f in os.listdir(kdir)) if m)
+    if ids != list(range(len(ids))) or not ids:
+        raise SystemExit("%s: fragments %s are not cloud_bin_0 .. cloud_bin_%d" % (kdir, ids[:5], len(ids) - 1))
+    blocks = []
+    for k in ids:
+        xyz = np.load(os.path.join(kdir, "cloud_bin_%d.npy" % k))[-num_keypts:]
+        desc = np.nan_to_num(np.load(os.path.join(ddir, "cloud_bin_%d.%s.npy" % (k, desc_name))))[-num_keypts:]   # evaluate.py:43-44
+        blocks.append(np.concatenate([xyz, desc, np.arange(len(xyz), dtype=np.float32)[:, None]], 1).astype(np.float32))
+    return blocks
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--root", required=True)
+    ap.add_argument("--scene", required=True)
+    ap.add_argument("--gt", default=None, help="the scene's gt.log (geometric_registration/gt_result/<scene>-evaluation/gt.log)")
+    ap.add_argument("--num-keypts", type=int, default=250)
+    ap.add_argument("--desc-name", default="D3Feat")
+    ap.add_argument("--inlier-ratio", type=float, default=0.05)
+    ap.add_argument("--distance-threshold", type=float, default=0.10)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    blocks = load_scene(a.root, a.scene, a.desc_name, a.num_keypts)
+    kp, count = reg.stack_keypoints(blocks, a.num_keypts, device=dev)
+    pairs = reg.scene_pairs(len(blocks), device=dev)
+    host_pairs = [tuple(p) for p in pairs.cpu().tolist()]
+    gt_log = results.read_gt_log(a.gt) if a.gt else {}
+    flag = np.array([1 if "%d_%d" % p in gt_log else 0 for p in host_pairs])
+    gt = np.tile(np.eye(4)[:3], (len(host_pairs), 1, 1))
+    for i, p in enumerate(host_pairs):
+        if flag[i]:
+            gt[i] = gt_log["%d_%d" % p][:3]
+    res = reg.register_pairs(kp, count, pairs, num_keypts=a.num_keypts, seed=a.seed, gt=torch.from_numpy(gt.astype(np.float32)).to(dev),
+                             distance_threshold=a.distance_threshold, **reg.EVALUATE_3DMATCH)
+    mutual, inl = res.mutual_count.cpu().numpy(), res.gt_inliers.cpu().numpy()
+    T = np.tile(np.eye(4), (len(host_pairs), 1, 1))
+    T[:, :3] = res.T.cpu().numpy().astype(np.float64)
+    # pairs that gt.log does not list: num_inliers = inlier_ratio = gt_flag = 0 and no .log block (evaluate.py:60-65)
+    num_inliers = np.where(flag == 1, inl, 0)
+    ratio = np.where((flag == 1) & (mutual > 0), inl / np.maximum(mutual, 1), 0.0)
+    os.makedirs(a.out, exist_ok=True)
+    logged = [i for i in range(len(host_pairs)) if flag[i] or not a.gt]
+    results.write_registration_log(os.path.join(a.out, "%s.log" % a.desc_name), [host_pairs[i] for i in logged], [T[i] for i in logged])
+    rows = results.write_pair_results(a.out, host_pairs, num_inliers, ratio, flag)
+    rec = results.feature_matching_recall(rows, a.inlier_ratio)
+    print(json.dumps(dict(scene=a.scene, fragments=len(blocks), pairs=len(host_pairs), **rec)))
+
+
+if __name__ == "__main__":
+    main()
