@@ -80,6 +80,62 @@ def KPConv_ops(query_points, support_points, neighbors_indices, features, K_poin
     return out
 
 
+def kpconv_f64(query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent,
+               KP_influence="linear", aggregation_mode="sum", Nq=None, Ns=None, col_scale=None, col_shift=None,
+               residual=None, leaky=False, alpha=0.2):
+    """kernels/convolution_ops.py:161-255 in plain float64 numpy, all rows at once, plus the inference epilogue that follows a
+    KPConv in models/network_blocks.py (batch-norm scale / shift, shortcut add, LeakyReLU) -- the reference of
+    tests/test_gpu_kpconv_branches.py.  Nq / Ns: the EFFECTIVE query / support counts (rows beyond them are never read).  A
+    neighbour index outside [0, Ns) is the shadow neighbour: zero feature row, no influence, not counted.
+    -> (wf [Nq, num_kp, Cin], count [Nq] (neighbours whose feature row sums to > 0, :250-251; not clamped),
+        out [Nq, Cout] = act((wf . K_values) / max(count, 1) * col_scale + col_shift (+ residual)), or None without K_values)."""
+    Nq = len(query_points) if Nq is None else int(Nq)
+    Ns = len(support_points) if Ns is None else int(Ns)
+    q = np.asarray(query_points, np.float64)[:Nq]
+    s = np.asarray(support_points, np.float64)[:Ns]
+    f = np.asarray(features, np.float64)[:Ns]
+    KP = np.asarray(K_points, np.float64)
+    idx = np.asarray(neighbors_indices, np.int64)[:Nq]
+    P, Cin, K = KP.shape[0], f.shape[1], idx.shape[1]
+    valid = (idx >= 0) & (idx < Ns)
+    if Ns == 0 or K == 0:
+        wf, count = np.zeros((Nq, P, Cin)), np.zeros(Nq, np.int64)
+    else:
+        safe = np.where(valid, idx, 0)
+        rel = s[safe] - q[:, None, :]                                          # :194-197  [Nq, K, 3]
+        d2 = ((rel[:, :, None, :] - KP[None, None]) ** 2).sum(-1)               # :200-205  [Nq, K, P]
+        if KP_influence == "constant":                                          # :208-211
+            h = np.ones_like(d2)
+        elif KP_influence == "linear":                                          # :213-216
+            h = np.maximum(1.0 - np.sqrt(d2 + 1e-10) / (2.0 * KP_extent), 0.0)
+        elif KP_influence == "gaussian":                                        # :218-222
+            h = np.exp(-d2 / (2.0 * (KP_extent * 0.3) ** 2 + 1e-9))
+        else:
+            raise ValueError("Unknown influence function type (config.KP_influence)")
+        if aggregation_mode == "closest":                                       # :227-229
+            h = h * (np.arange(P)[None, None, :] == d2.argmin(-1)[:, :, None])
+        elif aggregation_mode != "sum":
+            raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+        h = h * valid[:, :, None]                                               # :234 (the shadow's feature row is the zero row)
+        nf = f[safe]                                                            # :237  [Nq, K, Cin]
+        wf = np.matmul(h.transpose(0, 2, 1), nf)                                # :240  [Nq, P, Cin]
+        rowpos = np.asarray([math.fsum(r) > 0 for r in f])                      # :250 (the sign of the exact sum)
+        count = (rowpos[safe] & valid).sum(-1)                                  # :251
+    if K_values is None:
+        return wf, count, None
+    W = np.asarray(K_values, np.float64)
+    out = wf.reshape(Nq, P * Cin) @ W.reshape(P * Cin, -1) / np.maximum(count, 1)[:, None]      # :243-253
+    if col_scale is not None:
+        out = out * np.asarray(col_scale, np.float64)
+    if col_shift is not None:
+        out = out + np.asarray(col_shift, np.float64)
+    if residual is not None:
+        out = out + np.asarray(residual, np.float64)[:Nq]
+    if leaky:
+        out = np.where(out > 0, out, out * float(alpha))
+    return wf, count, out
+
+
 # --------------------------------------------------------------------------------------------------
 # models/network_blocks.py
 # --------------------------------------------------------------------------------------------------

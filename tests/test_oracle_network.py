@@ -153,3 +153,78 @@ def test_forward_structure_on_reference_geometry(coracle):
     assert np.abs(d[: len(c)] - d[len(c):]).max() < 1e-6 and np.abs(s[: len(c)] - s[len(c):]).max() < 1e-6
     assert trace["layer_0/simple_0"].shape[1] == 64 and trace["layer_4/resnetb_0"].shape[1] == 2048
     assert trace["uplayer_0/last_unary_1"].shape[1] == 32
+
+
+def test_kpconv_case_generator_conditions_hold_for_every_shape():
+    """oracle/kpconv_cases.py states two conditions on its inputs (row sums decided in any precision; no near-tie of the 'closest'
+    arg-min) and meets them by nudging / re-drawing, never by leaving a case out: every shape of tests/test_gpu_kpconv_branches.py
+    is generated here by the GPU tests' own helper (with 15 kernel points; the generator asserts both conditions itself on the
+    other variants) and both are asserted on it; the stated index patterns are present."""
+    from oracle import kpconv_cases as kc
+    shapes = kc.all_shapes()
+    assert len(shapes) >= 90
+    kinds = set()
+    for kernel, Cin, Nq, K in shapes:
+        for bf16 in ((False, True) if kc.has_bf16(kernel, Cin) or kernel == "errors" else (False,)):
+            c = kc.shape_case(kernel, Cin, Nq, K, bf16=bf16)
+            f = c.f[:c.Ns]
+            assert kc.row_sums_decided(f) and kc.closest_decided(c)
+            assert np.isnan(c.f[c.Ns:]).all() and np.isnan(c.q[c.Nq:]).all()
+            if bf16:
+                assert np.array_equal(f, kc.bf16_values(f))
+            sums = f.astype(np.float64).sum(1)
+            assert (sums < 0).any() and (sums > 0).any() and (np.abs(f).sum(1) == 0).any()
+            if Cin >= 2:
+                assert ((sums == 0) & (np.abs(f).sum(1) > 0)).any()
+            idx = c.idx[:Nq]
+            valid = (idx >= 0) & (idx < c.Ns)
+            if Nq >= 4 and K >= 1:
+                assert (~valid.any(1)).sum() >= 2
+            if Nq * K >= 300:
+                assert (idx == c.Ns).any() and (idx > c.Ns).any() and (idx < 0).any() and valid.any()
+                assert any(len(set(r[v])) < v.sum() for r, v in zip(idx, valid))          # duplicates within a row
+                kinds.add(kernel)
+    assert kinds == {"agg_vec4", "fused32", "fused", "c1_sum", "c1_closest", "agg_scalar", "errors"}
+    x, want = kc.rowpos_case(1, 77, 20)
+    assert 0 < want.sum() < 77 and want[2] == 1 and want[3] == 0 and want[5] == 1 and want[4] == 0 and want[1] == 0
+
+
+KPCONV_F64_SHAPES = [("agg_vec4", 4, 255, 2), ("agg_vec4", 16, 63, 5), ("agg_scalar", 6, 37, 9), ("fused32", 32, 31, 8),
+                     ("fused", 64, 53, 17), ("c1_sum", 1, 15, 65), ("c1_closest", 1, 31, 37), ("agg_vec4", 8, 127, 0)]
+
+
+@pytest.mark.parametrize("influence,mode", [("constant", "sum"), ("linear", "sum"), ("gaussian", "sum"),
+                                            ("constant", "closest"), ("linear", "closest"), ("gaussian", "closest")])
+def test_kpconv_f64_vs_restatement_and_scalar_loops(influence, mode):
+    """onp.kpconv_f64 (the reference of tests/test_gpu_kpconv_branches.py: float64, shadow = any index outside [0, Ns), epilogue)
+    against the float32 restatement of the reference's graph (onp.KPConv_ops, at its float32 rounding) and against the float64
+    scalar loops above (at float64 rounding), in all six modes, at the generator's shapes -- capacity rows and every shadow pattern
+    included, which the two older forms only take as the index Ns."""
+    from oracle import kpconv_cases as kc
+    from oracle import network_np as onp
+    assert (influence, mode) in kc.MODES and len(kc.MODES) == 6
+    shapes = set(kc.all_shapes())
+    for kernel, Cin, Nq, K in KPCONV_F64_SHAPES:
+        assert (kernel, Cin, Nq, K) in shapes
+        num_kp = 15 if Cin != 8 else 4
+        c = kc.kpconv_case(kc.shape_seed(kernel, Cin, Nq, K), Cin, K, Nq, num_kp=num_kp, cap_q=2, cap_s=4)
+        W = kc.weights(kc.shape_seed(kernel, Cin, Nq, K), num_kp, Cin, 5)
+        wf, count, out = onp.kpconv_f64(c.q, c.s, c.idx, c.f, c.KP, W, kc.EXTENT, influence, mode, Nq=c.Nq, Ns=c.Ns)
+        assert wf.shape == (Nq, num_kp, Cin) and count.shape == (Nq,) and out.shape == (Nq, 5)
+        q, s, f = c.q[:c.Nq], c.s[:c.Ns], c.f[:c.Ns]
+        idx = np.where((c.idx[:c.Nq] < 0) | (c.idx[:c.Nq] >= c.Ns), c.Ns, c.idx[:c.Nq])
+        loops = _kpconv_loops(q, s, idx, f, c.KP, W, kc.EXTENT, influence, mode)
+        scale = max(1.0, np.abs(loops).max())
+        assert np.abs(out - loops).max() <= 1e-12 * scale
+        o32 = onp.KPConv_ops(q, s, idx, f, c.KP, W, kc.EXTENT, influence, mode).numpy()
+        assert np.abs(o32 - out).max() <= 2e-5 * scale
+        # the epilogue, restated: act(out * scale + shift + residual)
+        rng = np.random.default_rng(K)
+        cs, ch, res = rng.random(5) + 0.5, rng.standard_normal(5), rng.standard_normal((Nq + 2, 5))
+        _, _, oe = onp.kpconv_f64(c.q, c.s, c.idx, c.f, c.KP, W, kc.EXTENT, influence, mode, Nq=c.Nq, Ns=c.Ns, col_scale=cs,
+                                  col_shift=ch, residual=res, leaky=True, alpha=0.125)
+        v = out * cs + ch + res[:Nq]
+        assert np.array_equal(oe, np.where(v > 0, v, 0.125 * v))
+        # the count differs from the number of valid slots (zero / negative rows are present, not counted)
+        if Nq * K >= 300:
+            assert (count < ((c.idx[:Nq] >= 0) & (c.idx[:Nq] < c.Ns)).sum(1)).any()
