@@ -647,3 +647,137 @@ extern "C" int d3f_register_pairs(const float* kp, int n_blocks, int K, int ld, 
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Keypoint repeatability of every pair at every keypoint count in one pass (d3f_repeatability_pairs)
+// ---------------------------------------------------------------------------------------------------------------------
+// repeatability/evaluate_3dmatch_our.py:30-41 and evaluate_kitti_our.py:12-23, for each count k: the last k rows of both blocks, one of
+// them moved with the ground truth in float64, cdist, and the number of TARGET keypoints whose nearest source keypoint is closer than
+// the threshold (distance.min(axis=0) < thr), over k.  The blocks are in ascending score order, so the sets for different k are
+// nested: with rank 0 the best row, the nearest-source distance of a target at count k is the running minimum over the sources of
+// rank < k, and the target is counted at k iff its own rank is < k.  One walk over the sources in rank order with a test at every
+// requested count gives all counts:
+//   rp_repeat_kernel      one workgroup per pair: the source xyz in LDS in DESCENDING score order as doubles (3 x D3F_PAIRS_KMAX x 8 B),
+//                         thread t owns the targets of rank t, t + 256, ... (moved coordinates and the running minimum d2 in
+//                         registers), the walk is an LDS broadcast read; hits per count: ballot + popcount, the four waves through LDS
+//   rp_repeat_sum_kernel  one workgroup: totals[c] = sum over the pairs of repeat[p, c], int64 (order independent)
+// Arithmetic: records widened f32 -> f64, q_r = ((R[r,0] x + R[r,1] y) + R[r,2] z) + t[r], d2 = (dx dx + dy dy) + dz dz, the test
+// d2 < thr * thr (the rounded product); every operation rounded on its own (no contraction), so a numpy restatement has the same bits.
+struct RpRepeatParams {
+    double thr2;
+    int k[D3F_REPEAT_COUNTS_MAX];   // strictly ascending
+    int n, moved;                   // moved 0: gt takes the target frame into the source frame (target rows moved); 1: the source rows
+};
+
+__device__ __forceinline__ void rp_apply_f64(const double* __restrict__ M, double x, double y, double z, double& qx, double& qy, double& qz) {
+    qx = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(M[0], x), __dmul_rn(M[1], y)), __dmul_rn(M[2], z)), M[3]);
+    qy = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(M[4], x), __dmul_rn(M[5], y)), __dmul_rn(M[6], z)), M[7]);
+    qz = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(M[8], x), __dmul_rn(M[9], y)), __dmul_rn(M[10], z)), M[11]);
+}
+
+// TS: target rows per thread (the largest requested count is at most 256 * TS)
+template <int TS>
+__global__ void __launch_bounds__(256) rp_repeat_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
+                                                        const int* __restrict__ count, const int* __restrict__ pairs,
+                                                        const double* __restrict__ gt, RpRepeatParams prm, int* __restrict__ repeat) {
+    __shared__ double sx[D3F_PAIRS_KMAX], sy[D3F_PAIRS_KMAX], sz[D3F_PAIRS_KMAX];
+    __shared__ double M[12];
+    __shared__ int wsum[4 * D3F_REPEAT_COUNTS_MAX];
+    const int p = blockIdx.x, nk = prm.k[prm.n - 1];
+    const RpRows a = rp_rows(count, pairs, p, 0, n_blocks, K, nk), b = rp_rows(count, pairs, p, 1, n_blocks, K, nk);
+    const float* S = kp + ((size_t)a.blk * K + a.r0) * ld;
+    const float* T = kp + ((size_t)b.blk * K + b.r0) * ld;
+    if (threadIdx.x < 12) M[threadIdx.x] = gt[(size_t)p * 12 + threadIdx.x];
+    __syncthreads();
+    // source of rank j = row a.n - 1 - j
+    for (int j = threadIdx.x; j < a.n; j += 256) {
+        const float* s = S + (size_t)(a.n - 1 - j) * ld;
+        double x = (double)s[0], y = (double)s[1], z = (double)s[2];
+        if (prm.moved) rp_apply_f64(M, x, y, z, x, y, z);
+        sx[j] = x; sy[j] = y; sz[j] = z;
+    }
+    double qx[TS], qy[TS], qz[TS], best[TS];
+#pragma unroll
+    for (int s = 0; s < TS; ++s) {
+        const int r = threadIdx.x + 256 * s;
+        qx[s] = qy[s] = qz[s] = 0.0;
+        best[s] = __longlong_as_double(0x7ff0000000000000ll);   // no source yet: nothing is closer than the threshold
+        if (r < b.n) {
+            const float* t = T + (size_t)(b.n - 1 - r) * ld;
+            qx[s] = (double)t[0]; qy[s] = (double)t[1]; qz[s] = (double)t[2];
+            if (!prm.moved) rp_apply_f64(M, qx[s], qy[s], qz[s], qx[s], qy[s], qz[s]);
+        }
+    }
+    __syncthreads();
+    int j = 0;
+    for (int c = 0; c < prm.n; ++c) {
+        const int kc = prm.k[c], je = min(kc, a.n), re = min(kc, b.n);   // a count beyond the source rows: the whole walk
+        for (; j < je; ++j) {
+            const double x = sx[j], y = sy[j], z = sz[j];
+#pragma unroll
+            for (int s = 0; s < TS; ++s) {
+                const double dx = __dsub_rn(qx[s], x), dy = __dsub_rn(qy[s], y), dz = __dsub_rn(qz[s], z);
+                const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+                best[s] = d2 < best[s] ? d2 : best[s];
+            }
+        }
+        int hits = 0;
+#pragma unroll
+        for (int s = 0; s < TS; ++s) hits += __popcll(__ballot((int)threadIdx.x + 256 * s < re && best[s] < prm.thr2));
+        if (d3f_lane() == 0) wsum[(threadIdx.x >> 6) * D3F_REPEAT_COUNTS_MAX + c] = hits;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < prm.n) {
+        const int c = threadIdx.x;
+        repeat[(size_t)p * prm.n + c] = (wsum[c] + wsum[D3F_REPEAT_COUNTS_MAX + c]) + (wsum[2 * D3F_REPEAT_COUNTS_MAX + c] + wsum[3 * D3F_REPEAT_COUNTS_MAX + c]);
+    }
+}
+
+__global__ void __launch_bounds__(256) rp_repeat_sum_kernel(const int* __restrict__ repeat, int P, int n, long long* __restrict__ totals) {
+    __shared__ long long red[256];
+    for (int c = 0; c < n; ++c) {
+        long long mine = 0;
+        for (int p = threadIdx.x; p < P; p += 256) mine += repeat[(size_t)p * n + c];
+        red[threadIdx.x] = mine;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) totals[c] = red[0];
+        __syncthreads();
+    }
+}
+
+extern "C" int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int ld, const int* count_dev, const int* pairs_dev, int P,
+                                       const double* gt_dev, int moved, const double* threshold_host, const int* num_keypts_host,
+                                       int n_counts, int* repeat_dev, int64_t* totals_dev, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (P < 0 || n_blocks < 1 || K < 1 || ld < 3 || n_counts < 1 || n_counts > D3F_REPEAT_COUNTS_MAX || (moved != 0 && moved != 1))
+        return D3F_ERR_ARG;
+    if (!threshold_host || !num_keypts_host) return D3F_ERR_ARG;
+    const double thr = *threshold_host;
+    if (!(thr > 0.0)) return D3F_ERR_ARG;   // NaN too
+    RpRepeatParams prm;
+    for (int c = 0; c < D3F_REPEAT_COUNTS_MAX; ++c) prm.k[c] = 0;
+    for (int c = 0; c < n_counts; ++c) {
+        const int k = num_keypts_host[c];
+        if (k < 1 || k > D3F_PAIRS_KMAX || (c > 0 && k <= num_keypts_host[c - 1])) return D3F_ERR_ARG;
+        prm.k[c] = k;
+    }
+    prm.thr2 = thr * thr;
+    prm.n = n_counts;
+    prm.moved = moved;
+    if (P == 0) return D3F_OK;
+    if (!kp || !count_dev || !pairs_dev || !gt_dev || !repeat_dev) return D3F_ERR_ARG;
+    const int rows = prm.k[n_counts - 1] < K ? prm.k[n_counts - 1] : K;   // most rows of a block any pair uses
+    switch (d3f_cdiv(rows, 256)) {
+        case 1: rp_repeat_kernel<1><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, gt_dev, prm, repeat_dev); break;
+        case 2: rp_repeat_kernel<2><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, gt_dev, prm, repeat_dev); break;
+        case 3: rp_repeat_kernel<3><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, gt_dev, prm, repeat_dev); break;
+        default: rp_repeat_kernel<4><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, gt_dev, prm, repeat_dev); break;
+    }
+    if (totals_dev) rp_repeat_sum_kernel<<<1, 256, 0, stream>>>(repeat_dev, P, n_counts, (long long*)totals_dev);
+    D3F_LAUNCH_CHECK();
+    return D3F_OK;
+}

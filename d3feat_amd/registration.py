@@ -9,6 +9,8 @@
     register_pairs(kp, count, pairs, ...)   register_keypoints for every pair of a scene's fragments in one call (evaluate.py:150-156):
                                             four launches, no read-back in between, capturable; scene_pairs, stack_keypoints,
                                             EVALUATE_3DMATCH go with it
+    repeatability_pairs(kp, count, pairs, gt) keypoint repeatability of every pair at every keypoint count in one launch
+                                            (repeatability/evaluate_3dmatch_our.py:30-41, evaluate_kitti_our.py:12-23; float64)
 
 Every computation is a kernel of libd3feat_amd.so (csrc/registration.hip, csrc/radius_neighbors.hip); numpy / torch only
 move data and run the host loop over batches of hypotheses.  Open3D's own random stream is unspecified, so results are
@@ -278,4 +280,102 @@ def register_pairs(kp, count, pairs, max_correspondence_distance, num_keypts=Non
             out.mutual_count[s].data_ptr(), out.nearest[s].data_ptr(), out.mutual[s].data_ptr() if correspondences else None,
             out.gt_inliers[s].data_ptr() if gt is not None else None, ws.data_ptr(), ws.numel(), st)
         _lib.check(rc, "register_pairs")
+    return out
+
+
+# ---- keypoint repeatability of every pair at every count in one call (repeatability/evaluate_*_our.py) -----------------------------
+REPEATABILITY_COUNTS = (4, 8, 16, 32, 64, 128, 256, 512)                       # num_list of both scripts
+REPEATABILITY_3DMATCH = dict(distance_threshold=0.1, moved="target")           # evaluate_3dmatch_our.py:36-40
+REPEATABILITY_KITTI = dict(distance_threshold=0.5, moved="source")             # evaluate_kitti_our.py:18-22,43
+
+
+class PairRepeatability:
+    """Result of repeatability_pairs: DEVICE tensors repeat i32[P, n] (target keypoints with a source keypoint inside the threshold,
+    per pair and count) and totals i64[n] (their sums over the pairs); num_keypts is the tuple of the n counts."""
+
+    def __init__(self, P, num_keypts, device):
+        self.P, self.num_keypts = P, tuple(num_keypts)
+        n, chunks = len(self.num_keypts), max(-(-P // PAIRS_PER_CALL), 1)
+        self.repeat = torch.empty((P, n), dtype=torch.int32, device=device)
+        self.totals = torch.zeros((n,), dtype=torch.int64, device=device)
+        # more than PAIRS_PER_CALL pairs: the totals of every call, added up in row order (integers)
+        self.chunk_totals = torch.empty((chunks, n), dtype=torch.int64, device=device) if chunks > 1 else None
+
+    _cache = None
+
+    def _host(self):
+        # one read-back of the whole result, kept until the next repeatability_pairs(out=self)
+        if self._cache is None:
+            self._cache = dict(repeat=self.repeat.cpu().numpy(), totals=self.totals.cpu().numpy())
+        return self._cache
+
+    def ratios(self):
+        """f64[P, n]: repeat / num_keypts, the figure the reference appends per pair (the count itself, whatever the blocks hold)."""
+        return self._host()["repeat"].astype(np.float64) / np.asarray(self.num_keypts, np.float64)
+
+    def scene(self):
+        """f64[n]: the average of the ratios over the P pairs, as totals / (num_keypts * P)."""
+        k = np.asarray(self.num_keypts, np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self._host()["totals"].astype(np.float64) / (k * self.P)
+
+
+def _gt_f64(gt, P, device):
+    """[P,3,4] or [P,4,4], float32 or float64, tensor or numpy -> f64[P,3,4] contiguous on the device (as it is when it is that already)."""
+    if not isinstance(gt, torch.Tensor):
+        gt = torch.from_numpy(np.ascontiguousarray(gt))
+    if gt.dtype not in (torch.float32, torch.float64) or gt.dim() != 3 or gt.shape[0] != P or tuple(gt.shape[1:]) not in ((3, 4), (4, 4)):
+        raise ValueError("repeatability_pairs: gt %s of shape %s for %d pairs" % (gt.dtype, tuple(gt.shape), P))
+    return gt[:, :3].to(device=device, dtype=torch.float64).contiguous()
+
+
+def repeatability_pairs(kp, count, pairs, gt, num_keypts=REPEATABILITY_COUNTS, distance_threshold=0.1, moved="target", out=None):
+    """Keypoint repeatability of P pairs of keypoint blocks at every count of `num_keypts` in one call (repeatability/
+    evaluate_3dmatch_our.py:30-41, evaluate_kitti_our.py:12-23): kp f32[n_blocks, K, ld >= 3] (rows [xyz | ...] in ascending score
+    order: keypoints.topk_records / stack_keypoints), count i32[n_blocks], pairs i32[P, 2] (source, target) block indices, all on the
+    device.  For each count k the last k rows of both blocks are taken, one block is moved with gt in float64 -- moved="target": gt
+    takes the target frame into the source frame (3DMatch, as register_pairs' gt); moved="source": gt takes the source into the
+    target frame (KITTI's trans) -- and the TARGET keypoints with a source keypoint strictly closer than distance_threshold are
+    counted.  The counts are nested prefixes in score rank, so one pass over the sources serves all of them: two launches per
+    PAIRS_PER_CALL pairs, no read-back and no host decision (capturable: pass the previous result as `out`, and gt as a device
+    f64[P,3,4] tensor so that it is read in place).  num_keypts: strictly ascending, 1 .. 1024, at most 16 of them.
+    -> PairRepeatability (device tensors; .ratios() / .scene() for the reference's figures)."""
+    lib = _lib.load()
+    kp = ops._req(kp, torch.float32, "kp", 3)
+    count = ops._req(count, torch.int32, "count", 1)
+    pairs = ops._req(pairs, torch.int32, "pairs", 2)
+    dev = kp.device
+    if not kp.is_contiguous() or not count.is_contiguous() or not pairs.is_contiguous() or pairs.shape[1] != 2:
+        raise ValueError("repeatability_pairs: kp, count and pairs must be contiguous, pairs [P, 2]")
+    n_blocks, K, ld = kp.shape
+    if count.shape[0] != n_blocks or n_blocks < 1 or K < 1 or ld < 3:
+        raise ValueError("repeatability_pairs: kp %s, count %s" % (tuple(kp.shape), tuple(count.shape)))
+    ks = [int(k) for k in num_keypts]
+    if (not 1 <= len(ks) <= _lib.REPEAT_COUNTS_MAX or any(not 1 <= k <= _lib.PAIRS_KMAX for k in ks)
+            or any(b <= a for a, b in zip(ks, ks[1:]))):
+        raise ValueError("repeatability_pairs: num_keypts %s must be 1 to %d strictly ascending counts in 1..%d"
+                         % (ks, _lib.REPEAT_COUNTS_MAX, _lib.PAIRS_KMAX))
+    if moved not in ("target", "source"):
+        raise ValueError("repeatability_pairs: moved=%r (\"target\" or \"source\")" % (moved,))
+    thr = float(distance_threshold)
+    if not thr > 0.0:
+        raise ValueError("repeatability_pairs: distance_threshold %r" % (distance_threshold,))
+    P = pairs.shape[0]
+    gt = _gt_f64(gt, P, dev)
+    if out is None:
+        out = PairRepeatability(P, ks, dev)
+    elif not isinstance(out, PairRepeatability) or (out.P, out.num_keypts) != (P, tuple(ks)) or out.repeat.device != dev:
+        raise ValueError("repeatability_pairs: out= was made for another call")
+    out._cache = None
+    st = ops._stream(dev)
+    c_thr, c_ks, n = _lib.C.c_double(thr), (_lib.C.c_int * len(ks))(*ks), len(ks)
+    for i, p0 in enumerate(range(0, P, PAIRS_PER_CALL)):
+        s = slice(p0, min(p0 + PAIRS_PER_CALL, P))
+        totals = out.totals if out.chunk_totals is None else out.chunk_totals[i]
+        rc = lib.d3f_repeatability_pairs(kp.data_ptr(), n_blocks, K, ld, count.data_ptr(), pairs[s].data_ptr(), s.stop - s.start,
+                                         gt[s].data_ptr(), 1 if moved == "source" else 0, _lib.C.addressof(c_thr),
+                                         _lib.C.addressof(c_ks), n, out.repeat[s].data_ptr(), totals.data_ptr(), st)
+        _lib.check(rc, "repeatability_pairs")
+    if out.chunk_totals is not None:
+        torch.sum(out.chunk_totals, 0, out=out.totals)          # (plumbing: int64 rows of the calls)
     return out

@@ -133,3 +133,14 @@ def feature_matching_recall(rows, inlier_ratio=0.05):
     return dict(correct=pred_results, gt=gt_results, recall=float(pred_results / gt_results) * 100 if gt_results else 0.0,
                 ave_num_inliers=div(np.sum(np.where(result[:, 2] == 1, result[:, 0], zeros))),
                 ave_inlier_ratio=div(np.sum(np.where(result[:, 2] == 1, result[:, 1], zeros))))
+
+
+# ---- the lines of repeatability/evaluate_3dmatch_our.py / evaluate_kitti_our.py -------------------------------------------------
+def repeatability_table(num_keypts, scene_values):
+    """The lines both scripts print, one per keypoint count (evaluate_3dmatch_our.py:66, evaluate_kitti_our.py:44), from values
+    computed elsewhere (registration.repeatability_pairs(...).scene(), or an average of several scenes' values): ->
+    (["Average Repeatability at num_keypts = K: v", ...], {K: v})."""
+    ks, vs = [int(k) for k in num_keypts], [float(v) for v in np.asarray(scene_values, dtype=np.float64).reshape(-1)]
+    if len(ks) != len(vs):
+        raise ValueError("repeatability_table: %d counts, %d values" % (len(ks), len(vs)))
+    return [f"Average Repeatability at num_keypts = {k}: {v}" for k, v in zip(ks, vs)], dict(zip(ks, vs))

@@ -44,6 +44,7 @@ extern "C" {
 #define D3F_NEIGHBOR_CAP 1024    /* max in-radius supports per query that can be ordered */
 #define D3F_TOPK_MAX 8192        /* most keypoints per cloud d3f_topk_records selects */
 #define D3F_PAIRS_KMAX 1024      /* most rows of one keypoint block d3f_register_pairs uses */
+#define D3F_REPEAT_COUNTS_MAX 16 /* most keypoint counts one d3f_repeatability_pairs call evaluates */
 #define D3F_NUM_KP_MAX 16        /* kernel points per KPConv (reference uses 15) */
 
 int d3f_version(void);
@@ -527,6 +528,32 @@ int d3f_register_pairs(const float* kp, int n_blocks, int K, int ld, int C, cons
                        float distance_threshold, float* T_out, int* inliers, uint64_t* sumd2, int* validations, int* iterations,
                        int* best_iteration, int* mutual_count, int* nearest, int* mutual, int* gt_inliers, void* workspace,
                        size_t workspace_bytes, void* stream);
+
+/* Keypoint repeatability of P pairs of keypoint blocks at n_counts keypoint counts in one launch (repeatability/
+ * evaluate_3dmatch_our.py:30-41, evaluate_kitti_our.py:12-23: for each count k the last k rows of both blocks, one block moved with
+ * the ground truth in float64, cdist, and the number of TARGET keypoints whose nearest source keypoint is closer than the threshold).
+ * kp / count_dev / pairs_dev as d3f_register_pairs takes them, ld >= 3 (only xyz is read; rows in ascending score order); K may
+ * exceed D3F_PAIRS_KMAX: only the largest requested count bounds the rows used.
+ *   gt_dev f64[P, 12], row-major [R | t].  moved 0: gt takes the TARGET frame into the SOURCE frame and the target rows are moved
+ *     (3DMatch, the convention of d3f_register_pairs' gt); moved 1: gt takes the source frame into the target frame and the source
+ *     rows are moved (KITTI's `trans`).  In both cases the count runs over the target rows.
+ *   threshold_host: ONE double on the host (a pointer, because 0.1f is not 0.1); num_keypts_host: n_counts ints on the host,
+ *     strictly ascending, each in 1 .. D3F_PAIRS_KMAX, 1 <= n_counts <= D3F_REPEAT_COUNTS_MAX.  Both are read before the call
+ *     returns and reach the kernel by value.
+ *   repeat_dev i32[P, n_counts]: with rank 0 the last (best) row of a block, repeat[p, c] = number of target rows of rank < k_c whose
+ *     nearest source row of rank < k_c is strictly closer than the threshold.  The blocks are in score order, so the row sets of the
+ *     counts are nested and one walk over the sources in rank order, with a test at every count, serves all of them.  A block
+ *     shorter than k_c contributes the rows it has, a pair without source rows counts 0, an index outside [0, n_blocks) selects
+ *     no rows.  The reference's ratio is repeat / k_c (k_c itself, whatever the blocks hold).
+ *   totals_dev (optional) i64[n_counts]: the sums of repeat over the P pairs (a second launch; integer, order independent).
+ * Arithmetic in float64 with every operation rounded on its own: rows widened f32 -> f64, q_r = ((R[r,0] x + R[r,1] y) + R[r,2] z)
+ * + t[r], d2 = (dx dx + dy dy) + dz dz, the test d2 < threshold * threshold (the rounded product).
+ * D3F_ERR_ARG before anything touches the device: P < 0, K < 1, ld < 3, n_counts or a count out of range, counts not strictly
+ * ascending, moved not 0 or 1, a NaN or non-positive threshold, a NULL pointer other than totals_dev; P == 0 is D3F_OK.
+ * Asynchronous on `stream`, no workspace, no allocation, no synchronisation, no memset: capturable. */
+int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int ld, const int* count_dev, const int* pairs_dev, int P,
+                            const double* gt_dev, int moved, const double* threshold_host, const int* num_keypts_host,
+                            int n_counts, int* repeat_dev, int64_t* totals_dev, void* stream);
 
 #ifdef __cplusplus
 }
