@@ -12,5 +12,6 @@ Layout (mirrors the reference's module paths for the hot path only):
   utils/config.py              Config (parameters.txt compatible)                       (reference: utils/config.py)
   parallel.py                  fragment sharding across GPUs + final RCCL gather
   keypoints.py                 the K highest-scoring records per cloud, on the device   (reference: utils/tester.py:208-213 + evaluate.py:45-50)
+  overlap.py                   overlap ratio and correspondences of every fragment pair (reference: datasets/cal_overlap.py:78-126)
 """
 __version__ = "0.1.0"

@@ -82,6 +82,7 @@ SIGNATURES = {
     "d3f_register_pairs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _i, _f, _f, _i, _i, C.c_uint64, _vp, _f] + [_vp] * 11
                            + [_sz, _vp]),
     "d3f_repeatability_pairs": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "d3f_overlap_pairs": (_i, [_vp, _sz, _i, _i, _vp, _i, _f, _vp, _vp, _i, _vp]),
     "d3f_gemm_pack_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_pack_f32t": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_f32t": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _sz,

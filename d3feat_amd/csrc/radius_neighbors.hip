@@ -452,6 +452,7 @@ nb_search_kernel(const float* __restrict__ q, int Nq, const int* __restrict__ ql
 
 #include "nb_cell_search.h"
 #include "nb_nearest.h"
+#include "nb_overlap.h"
 
 // ------------------------------------------------------------------------------------------------
 // cells the grid may use: 4 per support (surface clouds occupy ~0.3 cells per point at cell edge = radius; a sparser cloud gets
@@ -767,6 +768,32 @@ extern "C" int d3f_neighbor_grid_score(const void* grid, size_t grid_bytes, int 
     if (Ns == 0) return D3F_OK;
     nb_score_kernel<<<d3f_cdiv((long long)V * Ns, 256), 256, 0, stream>>>(g.el, g.cell_start, g.stmp, g.sorted, src, Ns, T, V,
                                                                          radius * radius, count_dev, (unsigned long long*)sumd2_dev, nearest_dev);
+    D3F_LAUNCH_CHECK();
+    return D3F_OK;
+}
+
+// ---- overlap of fragment pairs (nb_overlap.h) ---------------------------------------------------------------------------------
+// grid: built over the N stacked points of B fragments in one frame, radius >= threshold.  Two launches whatever P is: the fill
+// (counts 0, nearest -1) and the kernel; every length is read on the device.
+extern "C" int d3f_overlap_pairs(const void* grid, size_t grid_bytes, int N, int B, const int* pairs_dev, int P, float threshold,
+                                 int* count_dev, int* nearest_dev, int ld_nearest, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (N < 0 || P < 0 || ld_nearest < 0 || B < 1 || B > D3F_MAX_BATCH || !(threshold > 0.f) || !(threshold <= 3.4e38f)) return D3F_ERR_ARG;
+    if (P == 0) return D3F_OK;
+    if (!grid || !pairs_dev || !count_dev) return D3F_ERR_ARG;
+    NbGrid g = nb_carve((void*)grid, grid_bytes, N, B);
+    if (!g.ok) return D3F_ERR_WORKSPACE;
+    const D3fFill none{nullptr, 0ull, 0u};
+    const D3fFill rows{(unsigned*)nearest_dev, nearest_dev ? (unsigned long long)P * (unsigned long long)ld_nearest : 0ull, 0xFFFFFFFFu};
+    int rc;
+    if ((rc = d3f_begin_launch(nullptr, 0, nullptr, nullptr, nullptr, 0, D3fFill{(unsigned*)count_dev, (unsigned long long)P, 0u}, rows,
+                               none, none, stream)) != D3F_OK) return rc;
+    // workgroups per pair: enough for a fragment of average length, longer ones are strided over (the real lengths are on the device)
+    int gx = d3f_cdiv(d3f_cdiv(N > 0 ? N : 1, B), 256);
+    gx = gx < 1 ? 1 : (gx > 1024 ? 1024 : gx);
+    nb_overlap_kernel<<<dim3(gx, P < 65535 ? P : 65535), 256, 0, stream>>>(g.el, g.soffs, g.bbox, g.cell_start, g.stmp, g.sorted, B, pairs_dev,
+                                                                           P, threshold, threshold * threshold, count_dev, nearest_dev,
+                                                                           ld_nearest);
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }

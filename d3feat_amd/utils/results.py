@@ -144,3 +144,32 @@ def repeatability_table(num_keypts, scene_values):
     if len(ks) != len(vs):
         raise ValueError("repeatability_table: %d counts, %d values" % (len(ks), len(vs)))
     return [f"Average Repeatability at num_keypts = {k}: {v}" for k, v in zip(ks, vs)], dict(zip(ks, vs))
+
+
+# ---- the tables of datasets/cal_overlap.py ------------------------------------------------------------------------------------------
+def save_overlap_tables(savepath, ids, pairs, ratios, matches, split="train", downsample=0.025):
+    """The two pickles of cal_overlap.py:128-131 under `savepath`, by the reference's file names (:88-89): for every pair handed over --
+    the reference keeps those with a ratio above 0.30, :121-123 -- '<anc id>@<pos id>' -> overlap ratio (a Python float) in
+    3DMatch_<split>_<downsample>_overlap.pkl and -> int32[M, 2] rows [anchor index, positive index] in ..._keypts.pkl.  ids: the
+    fragments' id strings ('<scene>/<seq>/cloud_bin_<k>'); pairs: (anchor, positive) positions in ids; matches: one array per pair
+    (overlap.PairOverlap.matches).  Returns the two paths."""
+    import pickle
+    pairs, ratios, matches = list(pairs), list(ratios), list(matches)
+    if not len(pairs) == len(ratios) == len(matches):
+        raise ValueError("save_overlap_tables: %d pairs, %d ratios, %d match arrays" % (len(pairs), len(ratios), len(matches)))
+    overlap_ratio, keypts_pairs = {}, {}
+    for (a, b), r, m in zip(pairs, ratios, matches):
+        m = np.asarray(m)
+        if m.ndim != 2 or m.shape[1] != 2:
+            raise ValueError("save_overlap_tables: matches of shape %s for pair (%d, %d)" % (m.shape, a, b))
+        key = f'{ids[int(a)]}@{ids[int(b)]}'
+        keypts_pairs[key] = np.ascontiguousarray(m, dtype=np.int32)
+        overlap_ratio[key] = float(r)
+    os.makedirs(savepath, exist_ok=True)
+    out = []
+    for name, table in (("overlap", overlap_ratio), ("keypts", keypts_pairs)):
+        path = os.path.join(savepath, f'3DMatch_{split}_{downsample:.3f}_{name}.pkl')
+        with open(path, "wb") as f:
+            pickle.dump(table, f)
+        out.append(path)
+    return out

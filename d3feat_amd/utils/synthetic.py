@@ -89,3 +89,19 @@ def scene(seed, n_frag=8, K=250, edge=3.0, crop=1.1, noise=0.003, dnoise=0.05, o
         M = np.eye(4); M[:3, :3] = R; M[:3, 3] = t
         poses.append(M)
     return blocks, poses
+
+
+def overlap_scene(seed, n_frag=6, n_raw=12000, thr=0.05, edge=3.0, half_width=0.32, keep=0.55):
+    """n_frag fragments of ONE room, all in the room's frame, that overlap their neighbours along x (the input of overlap.overlap_pairs):
+    fragment f is the slab |x - c_f| < half_width * (x extent) of room_fragment(seed, n_raw, edge), c_f running from 15 % to 85 % of
+    the x extent; every point of the slab is kept with probability `keep` and moved by Gaussian noise of 0.3 thr / sqrt(3) per axis (a
+    surface sampled again, not the same points), then cast to float32.  -> list of f32[n_f, 3]."""
+    rng = np.random.default_rng(seed)
+    world = room_fragment(seed, n_raw=n_raw, edge=edge).astype(np.float64)
+    lo, ext = world[:, 0].min(), world[:, 0].max() - world[:, 0].min()
+    out = []
+    for c in lo + ext * np.linspace(0.15, 0.85, n_frag):
+        inside = np.nonzero(np.abs(world[:, 0] - c) < half_width * ext)[0]
+        sel = inside[rng.random(len(inside)) < keep]
+        out.append((world[sel] + rng.normal(scale=0.3 * thr / np.sqrt(3.0), size=(len(sel), 3))).astype(np.float32))
+    return out

@@ -555,6 +555,27 @@ int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int ld, const 
                             const double* gt_dev, int moved, const double* threshold_host, const int* num_keypts_host,
                             int n_counts, int* repeat_dev, int64_t* totals_dev, void* stream);
 
+/* Overlap of P pairs of a scene's fragments in two launches, whatever P is (datasets/cal_overlap.py:78-126: for every pair the
+ * nearest point of the second fragment for each point of the first, the matches closer than the voxel size, their share of the
+ * first fragment): what a host loop of one d3f_neighbor_grid_build per target and one d3f_neighbor_grid_score(V = 1, identity) per
+ * pair computes, bit for bit, with no host read-back and no host-side decision -- so the call can be captured in a HIP graph.
+ *   grid: built by d3f_neighbor_grid_build over the N stacked points of B fragments (s_lens_dev = their lengths), all in ONE common
+ *     frame, with radius >= threshold (the caller's contract, as for d3f_neighbor_grid_search).  It is the only point input: a built
+ *     grid holds every fragment's points in the fragment's own cell order with their indices, and those records are the queries.
+ *   pairs_dev i32[P, 2]: (source a, target b) fragment indices, read on the device; a == b and repeated pairs are allowed.
+ *   count_dev i32[P], OVERWRITTEN: points of a whose nearest point of b is strictly inside the threshold; -1 for a pair with an
+ *     index outside [0, B) (nothing is read for it, its nearest row is all -1).  The reference's ratio is count / len_a.
+ *   nearest_dev (optional) i32[P, ld_nearest]: entry [p, i] = index INSIDE fragment b (cv2's trainIdx) of the nearest point of b to
+ *     point i of a (i its index inside a, not the cell order), -1: none inside the threshold; entries from len_a on are -1; a row
+ *     shorter than its source fragment receives the first ld_nearest entries only (nothing is written past it).
+ * The metric of every search here: r2 = threshold * threshold in fp32, d2 = (dx*dx + dy*dy) + dz*dz with dx = q - s, every
+ * operation rounded to fp32 and never contracted, a match iff d2 < r2, the nearest point the minimum by (d2, index in b).
+ * D3F_ERR_ARG before anything touches the device: a negative size, B outside 1 .. D3F_MAX_BATCH, a threshold that is not positive
+ * and finite, grid / pairs_dev / count_dev NULL with P > 0; a grid_bytes below d3f_neighbor_grid_bytes(N, B): D3F_ERR_WORKSPACE;
+ * P == 0 is D3F_OK without a launch.  Asynchronous on `stream`, no workspace, no allocation, no synchronisation. */
+int d3f_overlap_pairs(const void* grid, size_t grid_bytes, int N, int B, const int* pairs_dev, int P, float threshold,
+                      int* count_dev, int* nearest_dev, int ld_nearest, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
