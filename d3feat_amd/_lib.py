@@ -19,6 +19,7 @@ MAX_BATCH = 255
 TOPK_MAX = 8192
 PAIRS_KMAX = 1024
 REPEAT_COUNTS_MAX = 16
+MATCH_KMAX = 8192
 
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
 
@@ -82,6 +83,8 @@ SIGNATURES = {
     "d3f_register_pairs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _f, _i, _f, _f, _i, _i, C.c_uint64, _vp, _f] + [_vp] * 11
                            + [_sz, _vp]),
     "d3f_repeatability_pairs": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "d3f_match_pairs_workspace_bytes": (_sz, [_i, _vp, _i]),
+    "d3f_match_pairs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _f, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "d3f_overlap_pairs": (_i, [_vp, _sz, _i, _i, _vp, _i, _f, _vp, _vp, _i, _vp]),
     "d3f_gemm_pack_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_pack_f32t": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -781,3 +781,8 @@ extern "C" int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Feature-matching recall of every pair at every keypoint count in two launches (d3f_match_pairs)
+// ---------------------------------------------------------------------------------------------------------------------
+#include "rp_matching.h"

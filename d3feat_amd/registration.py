@@ -11,6 +11,8 @@
                                             EVALUATE_3DMATCH go with it
     repeatability_pairs(kp, count, pairs, gt) keypoint repeatability of every pair at every keypoint count in one launch
                                             (repeatability/evaluate_3dmatch_our.py:30-41, evaluate_kitti_our.py:12-23; float64)
+    match_pairs(kp, count, pairs, gt)       feature-matching recall figures (mutual matches, inliers under gt) of every pair at every
+                                            keypoint count in two launches (evaluate.py:45-50,67-82), up to 8192 rows per block
 
 Every computation is a kernel of libd3feat_amd.so (csrc/registration.hip, csrc/radius_neighbors.hip); numpy / torch only
 move data and run the host loop over batches of hypotheses.  Open3D's own random stream is unspecified, so results are
@@ -378,4 +380,99 @@ def repeatability_pairs(kp, count, pairs, gt, num_keypts=REPEATABILITY_COUNTS, d
         _lib.check(rc, "repeatability_pairs")
     if out.chunk_totals is not None:
         torch.sum(out.chunk_totals, 0, out=out.totals)          # (plumbing: int64 rows of the calls)
+    return out
+
+
+# ---- feature-matching recall of every pair at every count in one call (geometric_registration/evaluate.py:45-50,67-82) -------------
+MATCHING_COUNTS = (250, 500, 1000, 2500, 5000)                                 # the sweep of evaluate.py:46's num_keypts
+
+
+class PairMatching:
+    """Result of match_pairs: DEVICE tensors mutual_count i32[P, n] (mutually nearest descriptor pairs, per pair and count) and
+    gt_inliers i32[P, n] (those inside the distance threshold under gt; None without gt); num_keypts is the tuple of the n counts."""
+
+    def __init__(self, P, num_keypts, device, gt):
+        self.P, self.num_keypts = P, tuple(num_keypts)
+        n = len(self.num_keypts)
+        self.mutual_count = torch.empty((P, n), dtype=torch.int32, device=device)
+        self.gt_inliers = torch.empty((P, n), dtype=torch.int32, device=device) if gt else None
+
+    _cache = None
+
+    def _host(self):
+        # one read-back of the whole result, kept until the next match_pairs(out=self)
+        if self._cache is None:
+            self._cache = {k: getattr(self, k).cpu().numpy() for k in ("mutual_count", "gt_inliers") if getattr(self, k) is not None}
+        return self._cache
+
+    def ratios(self):
+        """f64[P, n]: gt_inliers / mutual_count (evaluate.py:81), 0.0 for a pair without a mutual match (as PairRegistration.host)."""
+        h = self._host()
+        if "gt_inliers" not in h:
+            raise ValueError("PairMatching.ratios: match_pairs was called without gt")
+        m = h["mutual_count"].astype(np.float64)
+        return np.where(m > 0, h["gt_inliers"] / np.maximum(m, 1.0), 0.0)
+
+    def rows(self, c, gt_flag):
+        """The rows [num_inliers, inlier_ratio, gt_flag] of count num_keypts[c] as evaluate.py:203-204 reads them back from the result
+        files (the ratio at the 8 decimals of the file), one per pair: the input of results.feature_matching_recall /
+        matching_table.  gt_flag: P ints, 1 where gt.log lists the pair; the other pairs get zeros (evaluate.py:60-64)."""
+        flag = np.asarray(gt_flag)
+        if flag.ndim != 1 or flag.shape[0] != self.P or flag.dtype.kind not in "iub":
+            raise ValueError("PairMatching.rows: gt_flag of %d ints, one per pair" % self.P)
+        flag = (flag != 0).astype(np.int64)
+        inl, ratio = self._host()["gt_inliers"][:, c], self.ratios()[:, c]
+        return [[int(n) if g else 0, float("%.8f" % r) if g else 0.0, int(g)] for n, r, g in zip(inl, ratio, flag)]
+
+
+def match_pairs(kp, count, pairs, gt=None, num_keypts=MATCHING_COUNTS, distance_threshold=0.10, out=None):
+    """The feature-matching figures of P pairs of keypoint blocks at every count of `num_keypts` in one call (geometric_registration/
+    evaluate.py:45-50, 67-82, whose num_keypts = 250 is edited by hand for the sweep): kp f32[n_blocks, K, ld] ([xyz | desc | score]
+    rows in ascending score order: keypoints.topk_records / stack_keypoints), count i32[n_blocks], pairs i32[P, 2] (source, target)
+    block indices, all on the device.  For each count k the last min(count, k) rows of both blocks: mutual_count = the mutually nearest
+    descriptor pairs (build_correspondence), gt_inliers = those with |s - gt t| < distance_threshold, gt f32[P, 3, 4] (target ->
+    source) -- for k <= 1024 bit for bit what register_pairs(..., num_keypts=k, gt=gt) returns under these names, without its RANSAC
+    and for blocks of up to 8192 rows.  The counts are nested prefixes in score rank, so one pass over the largest count serves all of
+    them: two launches per PAIRS_PER_CALL pairs, no read-back and no host decision (capturable: pass the previous result as `out`).
+    num_keypts: strictly ascending, 1 .. 8192, at most 16 of them.  -> PairMatching (device tensors; .ratios() / .rows())."""
+    lib = _lib.load()
+    kp = ops._req(kp, torch.float32, "kp", 3)
+    count = ops._req(count, torch.int32, "count", 1)
+    pairs = ops._req(pairs, torch.int32, "pairs", 2)
+    dev = kp.device
+    if not kp.is_contiguous() or not count.is_contiguous() or not pairs.is_contiguous() or pairs.shape[1] != 2:
+        raise ValueError("match_pairs: kp, count and pairs must be contiguous, pairs [P, 2]")
+    n_blocks, K, ld = kp.shape
+    C = ld - 4
+    if count.shape[0] != n_blocks or n_blocks < 1 or K < 1 or C not in (16, 32, 64):
+        raise ValueError("match_pairs: kp %s (descriptors of 16, 32 or 64 floats), count %s" % (tuple(kp.shape), tuple(count.shape)))
+    ks = [int(k) for k in num_keypts]
+    if (not 1 <= len(ks) <= _lib.REPEAT_COUNTS_MAX or any(not 1 <= k <= _lib.MATCH_KMAX for k in ks)
+            or any(b <= a for a, b in zip(ks, ks[1:]))):
+        raise ValueError("match_pairs: num_keypts %s must be 1 to %d strictly ascending counts in 1..%d"
+                         % (ks, _lib.REPEAT_COUNTS_MAX, _lib.MATCH_KMAX))
+    thr = float(distance_threshold)
+    if thr != thr:
+        raise ValueError("match_pairs: distance_threshold %r" % (distance_threshold,))
+    P = pairs.shape[0]
+    if gt is not None:
+        gt = ops._req(gt, torch.float32, "gt", 3)
+        if tuple(gt.shape) != (P, 3, 4) or not gt.is_contiguous():
+            raise ValueError("match_pairs: gt of shape %s for %d pairs" % (tuple(gt.shape), P))
+    if out is None:
+        out = PairMatching(P, ks, dev, gt is not None)
+    elif (not isinstance(out, PairMatching) or (out.P, out.num_keypts, out.gt_inliers is not None) != (P, tuple(ks), gt is not None)
+          or out.mutual_count.device != dev):
+        raise ValueError("match_pairs: out= was made for another call")
+    out._cache = None
+    st = ops._stream(dev)
+    c_ks, n = (_lib.C.c_int * len(ks))(*ks), len(ks)
+    for p0 in range(0, P, PAIRS_PER_CALL):
+        s = slice(p0, min(p0 + PAIRS_PER_CALL, P))
+        ws = ops.workspace(lib.d3f_match_pairs_workspace_bytes(s.stop - s.start, _lib.C.addressof(c_ks), n), dev)
+        rc = lib.d3f_match_pairs(kp.data_ptr(), n_blocks, K, ld, C, count.data_ptr(), pairs[s].data_ptr(), s.stop - s.start,
+                                 gt[s].data_ptr() if gt is not None else None, thr, _lib.C.addressof(c_ks), n,
+                                 out.mutual_count[s].data_ptr(), out.gt_inliers[s].data_ptr() if gt is not None else None,
+                                 ws.data_ptr(), ws.numel(), st)
+        _lib.check(rc, "match_pairs")
     return out

@@ -135,6 +135,21 @@ def feature_matching_recall(rows, inlier_ratio=0.05):
                 ave_inlier_ratio=div(np.sum(np.where(result[:, 2] == 1, result[:, 1], zeros))))
 
 
+def matching_table(num_keypts, rows_per_count, inlier_ratio=0.05):
+    """The per-scene lines of evaluate.py:211-216 for a sweep of keypoint counts (evaluate.py:46 edited by hand, one run per count):
+    rows_per_count[c] = the rows [num_inliers, inlier_ratio, gt_flag] of count num_keypts[c] (registration.PairMatching.rows).
+    -> (lines, {K: feature_matching_recall dict})."""
+    ks, rows_per_count = [int(k) for k in num_keypts], list(rows_per_count)
+    if len(ks) != len(rows_per_count):
+        raise ValueError("matching_table: %d counts, %d row lists" % (len(ks), len(rows_per_count)))
+    lines, table = [], {}
+    for k, rows in zip(ks, rows_per_count):
+        r = table[k] = feature_matching_recall(rows, inlier_ratio)
+        lines += [f"num_keypts = {k}", f"Correct Match {r['correct']}, ground truth Match {r['gt']}", f"Recall {r['recall']}%",
+                  f"Average Num Inliners: {r['ave_num_inliers']}", f"Average Num Inliner Ratio: {r['ave_inlier_ratio']}"]
+    return lines, table
+
+
 # ---- the lines of repeatability/evaluate_3dmatch_our.py / evaluate_kitti_our.py -------------------------------------------------
 def repeatability_table(num_keypts, scene_values):
     """The lines both scripts print, one per keypoint count (evaluate_3dmatch_our.py:66, evaluate_kitti_our.py:44), from values

@@ -44,7 +44,8 @@ extern "C" {
 #define D3F_NEIGHBOR_CAP 1024    /* max in-radius supports per query that can be ordered */
 #define D3F_TOPK_MAX 8192        /* most keypoints per cloud d3f_topk_records selects */
 #define D3F_PAIRS_KMAX 1024      /* most rows of one keypoint block d3f_register_pairs uses */
-#define D3F_REPEAT_COUNTS_MAX 16 /* most keypoint counts one d3f_repeatability_pairs call evaluates */
+#define D3F_REPEAT_COUNTS_MAX 16 /* most keypoint counts one d3f_repeatability_pairs / d3f_match_pairs call evaluates */
+#define D3F_MATCH_KMAX 8192      /* largest keypoint count of d3f_match_pairs (= D3F_TOPK_MAX, the largest block the selection makes) */
 #define D3F_NUM_KP_MAX 16        /* kernel points per KPConv (reference uses 15) */
 
 int d3f_version(void);
@@ -554,6 +555,33 @@ int d3f_register_pairs(const float* kp, int n_blocks, int K, int ld, int C, cons
 int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int ld, const int* count_dev, const int* pairs_dev, int P,
                             const double* gt_dev, int moved, const double* threshold_host, const int* num_keypts_host,
                             int n_counts, int* repeat_dev, int64_t* totals_dev, void* stream);
+
+/* Feature-matching recall of P pairs of keypoint blocks at n_counts keypoint counts in two launches, whatever P and the counts are
+ * (geometric_registration/evaluate.py:45-50, 67-82, whose num_keypts is edited by hand to sweep 5000 / 2500 / 1000 / 500 / 250): per
+ * pair and count k what d3f_register_pairs returns as mutual_count and gt_inliers for num_keypts = k, bit for bit, without its
+ * RANSAC and without its limit of D3F_PAIRS_KMAX rows.  No memset, no atomics between workgroups, no read-back: capturable.
+ * kp / count_dev / pairs_dev as d3f_register_pairs takes them (rows [xyz | C-d descriptor | ...] in ascending score order, an index
+ * outside [0, n_blocks) selects no rows), C in {16, 32, 64}, ld >= C + 3; K may exceed every count.
+ *   num_keypts_host: n_counts ints on the host, strictly ascending, each in 1 .. D3F_MATCH_KMAX, 1 <= n_counts <=
+ *     D3F_REPEAT_COUNTS_MAX; read before the call returns.  Count k uses the LAST min(count, k) rows of each block.
+ *   nearest descriptors: argmin of the fp32 chain of d3f_feature_nn (d = a[c] - b[c]; d2 = fmaf(d, d, d2), c ascending), the lowest
+ *     row on ties, in both directions.  The blocks are in score order, so the rows of the counts are nested prefixes in rank (rank 0 =
+ *     the last row) and the nearest row at count k is a running minimum of one walk in rank order: one pass over the largest count
+ *     serves every count.
+ *   mutual_count i32[P, n_counts]: source rows i with nn_ts[nn_st[i]] == i (evaluate.py:21-26).
+ *   gt (optional) f32[P, 12], row-major [R | t] taking the TARGET frame into the SOURCE frame; gt_inliers i32[P, n_counts], NULL if
+ *     and only if gt is NULL: the mutual pairs with |s_i - (R t_j + t)|^2 < distance_threshold * distance_threshold (evaluate.py:
+ *     70-77), fp32, the metric of d3f_register_pairs.
+ * A block shorter than a count contributes the rows it has; a pair without rows on either side counts 0.
+ * workspace >= d3f_match_pairs_workspace_bytes(P, num_keypts_host, n_counts): 8 * sum of the counts bytes per pair (the nearest rank
+ * of every row of every count, both directions), else D3F_ERR_WORKSPACE; the function returns 0 for arguments d3f_match_pairs refuses.
+ * D3F_ERR_ARG before anything touches the device: P < 0, n_blocks or K < 1, C not 16 / 32 / 64, ld < C + 3, n_counts or a count out of
+ * range, counts not strictly ascending, a NaN threshold, exactly one of gt / gt_inliers NULL, another NULL pointer with P > 0; P == 0
+ * is D3F_OK without a launch.  Asynchronous on `stream`, no allocation, no synchronisation. */
+size_t d3f_match_pairs_workspace_bytes(int P, const int* num_keypts_host, int n_counts);
+int d3f_match_pairs(const float* kp, int n_blocks, int K, int ld, int C, const int* count_dev, const int* pairs_dev, int P,
+                    const float* gt, float distance_threshold, const int* num_keypts_host, int n_counts, int* mutual_count,
+                    int* gt_inliers, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Overlap of P pairs of a scene's fragments in two launches, whatever P is (datasets/cal_overlap.py:78-126: for every pair the
  * nearest point of the second fragment for each point of the first, the matches closer than the voxel size, their share of the
