@@ -30,7 +30,21 @@ struct GemmEpi {
     int ldr;
     int leaky;
     float alpha;
+    // Optional row gather of the residual operand (gemm_x3_kernel's direct epilogue and gemm_splitk_reduce_kernel only): row m adds
+    // residual[ridx[m * ld_ridx]] instead of residual[m]; an index outside [0, res_rows) -- the shadow index of an upsampling
+    // matrix, a negative one -- adds exact zeros (the zero row of closest_pool).  NULL: the residual row is m, as ever.
+    const int* ridx;
+    int ld_ridx;
+    int res_rows;             // rows of the residual tensor (upper bound) and, optionally, its device-resident value
+    const int* res_rows_dev;
 };
+
+// the residual row of output row m, or NULL when it is a zero row (see GemmEpi::ridx)
+__device__ __forceinline__ const float* gemm_residual_row(const GemmEpi& E, int m) {
+    if (!E.ridx) return E.residual + (size_t)m * E.ldr;
+    const int r = E.ridx[(size_t)m * E.ld_ridx];
+    return (r >= 0 && r < d3f_dyn(E.res_rows, E.res_rows_dev)) ? E.residual + (size_t)r * E.ldr : nullptr;
+}
 
 __device__ __forceinline__ float gemm_epilogue(float v, int m, int n, const GemmEpi& E) {
     if (E.row_scale) v *= E.row_scale[m];
@@ -85,6 +99,13 @@ gemm_splitk_reduce_kernel(const float* __restrict__ slab, int S, int M, int N, f
         E2.residual = nullptr;
         E2.leaky = 0;
         v = gemm_epilogue(v, m, n, E2) + r;
+        if (E.leaky) v = v > 0.f ? v : v * E.alpha;
+    } else if (E.ridx && E.residual) {
+        const float* rrow = gemm_residual_row(E, m);
+        GemmEpi E2 = E;
+        E2.residual = nullptr;
+        E2.leaky = 0;
+        v = gemm_epilogue(v, m, n, E2) + (rrow ? rrow[n] : 0.f);
         if (E.leaky) v = v > 0.f ? v : v * E.alpha;
     } else {
         v = gemm_epilogue(v, m, n, E);

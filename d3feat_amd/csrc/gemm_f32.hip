@@ -9,6 +9,8 @@
 // kernel (file)                  entry point                       picked when
 // gemm_x3_kernel (gemm_x3.h)     d3f_gemm_x3                       ops._route: float4-addressable operands, K (and C1 of a
 //                                                                  concatenation) multiples of 32, N > 32: most of the network
+// gemm_x3_kernel (gemm_x3.h)     d3f_gemm_x3_gres                  ops.gemm_upsample_split: the fine-level half of a decoder block,
+//                                                                  the coarse level's product gathered as residual rows
 // gemm_x3r_kernel (gemm_x3.h)    d3f_gemm_x3                       inside it, when d3f_gemm_x3_resident: tall, W fits the LDS
 // gemm_dma_kernel (gemm_dma.h)   d3f_gemm_f32t                     ops._route: float4-addressable operands that x3 does not
 //                                                                  take (D3F_GEMM_X3=0, K % 32, 32-column layers, row cap)
@@ -822,24 +824,27 @@ extern "C" int d3f_gemm_x3_resident(int M, int N, int K, int M_hint) {
     return (NG == 1 || NG == 2 || NG == 4) && gemm_x3r_lds_bytes(K / GX_BK, NG) <= 160 * 1024 && m_eff >= 65536;
 }
 
-// Same operator and argument meaning as d3f_gemm_f32t; Wx = d3f_gemm_pack_x3(W [K,N]).  On top of d3f_gemm_f32t's addressing rules:
-// K = C1 + C2 a multiple of 32 and, for a concatenated operand, C1 a multiple of 32 too (else D3F_ERR_ARG: use d3f_gemm_f32t).
-// workspace >= d3f_gemm_x3_workspace_bytes(M, N, K, M_hint).
-extern "C" int d3f_gemm_x3(const float* A, int N1, int lda, int C1, const int* idx, int ld_idx, const float* skip, int lds, int C2,
-                           const void* Wx, float* C, int ldc, int M, int N, const float* row_scale, const float* col_scale,
-                           const float* col_shift, const float* residual, int ldr, int leaky, float alpha, void* workspace,
-                           size_t workspace_bytes, const int* M_dev, const int* N1_dev, int M_hint, void* stream_) {
+// The one launcher of d3f_gemm_x3 / d3f_gemm_x3_gres.  res_idx != NULL: the residual row of output row m is residual[res_idx[m *
+// ld_res_idx]] (GemmEpi::ridx) -- an operand only the tile kernel's epilogue and the K-split reduction know, so such a call takes the
+// tile form whatever d3f_gemm_x3_resident answers.
+static int gemm_x3_run(const float* A, int N1, int lda, int C1, const int* idx, int ld_idx, const float* skip, int lds, int C2,
+                       const void* Wx, float* C, int ldc, int M, int N, const float* row_scale, const float* col_scale,
+                       const float* col_shift, const float* residual, int ldr, const int* res_idx, int ld_res_idx, int res_rows,
+                       const int* res_rows_dev, int leaky, float alpha, void* workspace, size_t workspace_bytes, const int* M_dev,
+                       const int* N1_dev, int M_hint, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const int K = C1 + C2;
     bool empty;
     if (int rc = gemm_check_composite(true, GX_BK, 15, M, N, N1, C1, C2, lda, ldc, lds, ldr, ld_idx, A, Wx, C, idx, skip, residual,
                                       col_scale, col_shift, empty))
         return rc;
+    if (res_idx && (ld_res_idx < 1 || res_rows < 0)) return D3F_ERR_ARG;
     if (empty) return D3F_OK;
-    GemmEpi E{row_scale, col_scale, col_shift, residual, ldr, leaky, alpha};
+    if (res_idx && !residual) return D3F_ERR_ARG;
+    GemmEpi E{row_scale, col_scale, col_shift, residual, ldr, leaky, alpha, res_idx, ld_res_idx, res_rows, res_rows_dev};
     GemmGather G{idx, ld_idx, N1, N1_dev, C2 > 0 ? skip : nullptr, lds, C1};
     const int nkt = K / GX_BK, NG = d3f_cdiv(N, 32);
-    if (d3f_gemm_x3_resident(M, N, K, M_hint)) {   // ---- the resident-W persistent form (gemm_x3.h) ----
+    if (!res_idx && d3f_gemm_x3_resident(M, N, K, M_hint)) {   // ---- the resident-W persistent form (gemm_x3.h) ----
         // CU count of the CURRENT device (cached per device ordinal: a process may drive several)
         static std::atomic<int> cus_of[64];
         int dev = 0;
@@ -877,4 +882,28 @@ extern "C" int d3f_gemm_x3(const float* A, int N1, int lda, int C1, const int* i
     gemm_reduce(slab, S, M, N, C, ldc, E, M_dev, stream);
     D3F_LAUNCH_CHECK();
     return D3F_OK;
+}
+
+// Same operator and argument meaning as d3f_gemm_f32t; Wx = d3f_gemm_pack_x3(W [K,N]).  On top of d3f_gemm_f32t's addressing rules:
+// K = C1 + C2 a multiple of 32 and, for a concatenated operand, C1 a multiple of 32 too (else D3F_ERR_ARG: use d3f_gemm_f32t).
+// workspace >= d3f_gemm_x3_workspace_bytes(M, N, K, M_hint).
+extern "C" int d3f_gemm_x3(const float* A, int N1, int lda, int C1, const int* idx, int ld_idx, const float* skip, int lds, int C2,
+                           const void* Wx, float* C, int ldc, int M, int N, const float* row_scale, const float* col_scale,
+                           const float* col_shift, const float* residual, int ldr, int leaky, float alpha, void* workspace,
+                           size_t workspace_bytes, const int* M_dev, const int* N1_dev, int M_hint, void* stream_) {
+    return gemm_x3_run(A, N1, lda, C1, idx, ld_idx, skip, lds, C2, Wx, C, ldc, M, N, row_scale, col_scale, col_shift, residual, ldr,
+                       nullptr, 0, 0, nullptr, leaky, alpha, workspace, workspace_bytes, M_dev, N1_dev, M_hint, stream_);
+}
+
+// d3f_gemm_x3 with a GATHERED residual: row m adds residual[res_idx[m * ld_res_idx]] (res_idx int32, ld_res_idx >= 1; the residual
+// tensor has res_rows rows, *res_rows_dev of them when that pointer is given; an index outside [0, rows) adds zeros).  The decoder's
+// fine-level half: leaky(skip @ W2 + t + Y[up[m, 0]]) with Y = x @ W1 contracted once per COARSE row.  res_idx == NULL: d3f_gemm_x3.
+extern "C" int d3f_gemm_x3_gres(const float* A, int N1, int lda, int C1, const int* idx, int ld_idx, const float* skip, int lds, int C2,
+                                const void* Wx, float* C, int ldc, int M, int N, const float* row_scale, const float* col_scale,
+                                const float* col_shift, const float* residual, int ldr, const int* res_idx, int ld_res_idx,
+                                int res_rows, const int* res_rows_dev, int leaky, float alpha, void* workspace, size_t workspace_bytes,
+                                const int* M_dev, const int* N1_dev, int M_hint, void* stream_) {
+    return gemm_x3_run(A, N1, lda, C1, idx, ld_idx, skip, lds, C2, Wx, C, ldc, M, N, row_scale, col_scale, col_shift, residual, ldr,
+                       res_idx, ld_res_idx, res_rows, res_rows_dev, leaky, alpha, workspace, workspace_bytes, M_dev, N1_dev, M_hint,
+                       stream_);
 }

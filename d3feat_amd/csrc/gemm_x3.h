@@ -334,6 +334,9 @@ gemm_x3_kernel(const float* __restrict__ A, int lda, const unsigned short* __res
     float rs = 1.f;
     if (!slab && E.row_scale && mok) rs = E.row_scale[gm_a];
     float* dst = slab ? slab + ((size_t)by * Mcap + (mok ? gm_a : 0)) * N : C + (size_t)(mok ? gm_a : 0) * ldc;
+    // the lane's residual row: its own, or the gathered one (GemmEpi::ridx: one index per lane, requested only here, after the
+    // loop's final vmcnt(0) -- nothing of the compiler's is in flight beside the hand-counted requests); NULL adds zeros
+    const float* rrow = (!slab && E.residual && mok) ? gemm_residual_row(E, gm_a) : nullptr;
     // (round 5) final results leave as full 128-byte lines through a 32 x 36-float patch of the (now free) ring that belongs to the
     // wave, as in gemm_x3r_kernel::finish_tile: sixteen bytes per lane into 64 different places per store instruction were a
     // request-rate problem next to the loads (r05 g1); K slices still go to their slab directly
@@ -349,7 +352,7 @@ gemm_x3_kernel(const float* __restrict__ A, int lda, const unsigned short* __res
                 if (mok && gn < N) {
                     const float4 c4 = E.col_scale ? *(const float4*)&E.col_scale[gn] : make_float4(1.f, 1.f, 1.f, 1.f);
                     const float4 h4 = E.col_shift ? *(const float4*)&E.col_shift[gn] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    const float4 r4 = E.residual ? *(const float4*)&E.residual[(size_t)gm_a * E.ldr + gn] : make_float4(0.f, 0.f, 0.f, 0.f);
+                    const float4 r4 = rrow ? *(const float4*)&rrow[gn] : make_float4(0.f, 0.f, 0.f, 0.f);
                     const float c[4] = {c4.x, c4.y, c4.z, c4.w}, h[4] = {h4.x, h4.y, h4.z, h4.w}, rr[4] = {r4.x, r4.y, r4.z, r4.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -382,7 +385,7 @@ gemm_x3_kernel(const float* __restrict__ A, int lda, const unsigned short* __res
             if (!slab) {
                 const float4 c4 = E.col_scale ? *(const float4*)&E.col_scale[gn] : make_float4(1.f, 1.f, 1.f, 1.f);
                 const float4 h4 = E.col_shift ? *(const float4*)&E.col_shift[gn] : make_float4(0.f, 0.f, 0.f, 0.f);
-                const float4 r4 = E.residual ? *(const float4*)&E.residual[(size_t)gm_a * E.ldr + gn] : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 r4 = rrow ? *(const float4*)&rrow[gn] : make_float4(0.f, 0.f, 0.f, 0.f);
                 const float c[4] = {c4.x, c4.y, c4.z, c4.w}, h[4] = {h4.x, h4.y, h4.z, h4.w}, rr[4] = {r4.x, r4.y, r4.z, r4.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {

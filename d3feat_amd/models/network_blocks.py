@@ -123,11 +123,20 @@ def last_unary_block(layer_ind, inputs, features, radius, fdim, config, training
 def unary_block(layer_ind, inputs, features, radius, fdim, config, training):
     """:207-219."""
     _check_inference(training)
-    w = weight_variable([int(features.shape[1]), fdim])
     if isinstance(features, ops.UpsampleCat):
         # decoder: nearest upsampling + skip concatenation (models/D3Feat.py:55-63) fused into this contraction
+        vs = _vs()
+        w = vs.weight_variable([int(features.shape[1]), fdim])
+        if ops.upsample_split_ok(features, fdim):
+            # ... with the upsampled half contracted once per COARSE row and gathered in the fine level's epilogue
+            if config.use_batch_norm:
+                w1, w2, shift = vs.split_decoder(w, vs.batch_norm_variables(fdim), int(features.x.shape[1]))
+            else:
+                (w1, w2, _), shift = vs.split_decoder(w, None, int(features.x.shape[1])), _bn(fdim, False)[1]
+            return ops.gemm_upsample_split(features, w1, w2, col_shift=shift, leaky=True, alpha=0.2)
         e = _epilogue(fdim, config, True)
-        return ops.gemm_upsample_cat(features, w, col_scale=e['col_scale'], col_shift=e['col_shift'], leaky=True, alpha=0.2)
+        return ops.gemm_upsample_cat(features, vs.tensor(w), col_scale=e['col_scale'], col_shift=e['col_shift'], leaky=True, alpha=0.2)
+    w = weight_variable([int(features.shape[1]), fdim])
     return conv_ops.unary_convolution(features, w, epilogue=_epilogue(fdim, config, True))
 
 

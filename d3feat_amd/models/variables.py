@@ -116,10 +116,31 @@ class VariableStore:
             self._recipes[key] = (lambda: self._stack_host(w1, bn1, w2, bn2, eps))
         return t
 
+    def _split_host(self, w, bn, c1, eps):
+        s, t = self._bn_host(bn, eps)
+        W = (self.values[w] * s[None, :]).astype(np.float32)
+        return np.ascontiguousarray(W[:c1]), np.ascontiguousarray(W[c1:]), t
+
+    def split_decoder(self, w, bn, c1, eps=1e-6):
+        """A decoder block leaky(bn([ up(x) | skip ] @ W)) whose upsampled half is contracted at the coarse level (ops.
+        gemm_upsample_split): -> (W[:c1] * s, W[c1:] * s, t) on the device, the inference batch-norm scale folded into both halves
+        (s = gamma * rsqrt(var + eps), t = beta - mean * s).  bn None (no batch norm): the plain halves -- views of the weight's own
+        device copy -- and None; the caller adds its `offset` vector."""
+        if bn is None:
+            W = self.tensor(w)
+            return W[:c1], W[c1:], None
+        key = ('split', w, int(c1))
+        t = self._dev.get(key)
+        if t is None:
+            t = tuple(torch.from_numpy(a).to(self.device) for a in self._split_host(w, bn, c1, eps))
+            self._dev[key] = t
+            self._recipes[key] = (lambda: self._split_host(w, bn, c1, eps))
+        return t
+
     def update_in_place(self, values):
         """New values for some variables of a model whose device copies may already be captured BY ADDRESS in HIP graphs
         (d3feat_amd.engine): the host masters are replaced and every device tensor made from them -- the plain copies, the folded
-        batch-norm vectors, the stacked branch weights -- is rewritten IN PLACE, so a replayed graph reads the new values at the
+        batch-norm vectors, the stacked branch weights, the decoder's split halves -- is rewritten IN PLACE, so a replayed graph reads the new values at the
         old addresses.  -> the device tensors that were rewritten (ops.refresh_packed_weights re-packs their packed copies, also
         in place).  Shapes cannot change; kernel points ride in the launch arguments of a captured graph and cannot change."""
         for name, v in values.items():

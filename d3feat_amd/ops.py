@@ -716,6 +716,69 @@ def gemm_upsample_cat(u, W, col_scale=None, col_shift=None, leaky=False, alpha=0
     return _tag(out, inds)
 
 
+# The decoder's unary blocks in split form (D3F_DECODER_SPLIT=0: the one-launch form above throughout).  The upsampled half of
+# [ x'[inds[:,0]] | skip ] is a nearest-neighbour gather from a level with about a quarter of the rows, so the one-launch form
+# multiplies -- and splits into bf16 planes -- every coarse row about four times.  The split form contracts it ONCE per coarse row,
+# Y = x @ W[:C1], and the fine level computes skip @ W[C1:] and adds the gathered row Y[inds[m, 0]] in its epilogue (d3f_gemm_x3_gres).
+DECODER_SPLIT = os.environ.get("D3F_DECODER_SPLIT", "1") != "0"
+
+
+def _split_ok(M, C1, C2, N, hint=0, f32=True, f32t_ok=True):
+    """Is a decoder contraction of M rows ([C1 gathered | C2 skip] columns -> N) taken in the split form?  fp32 only, with a skip
+    operand, both parts whole k-tiles, and only where the one-launch call would run gemm_x3_kernel: the resident form's launch (level
+    0) is bound by HBM, and halving its K does not change its bytes."""
+    if not DECODER_SPLIT or BF16_CONTRACTION or not f32 or C2 <= 0 or C1 <= 0 or C1 % 32 or C2 % 32:
+        return False
+    resident = _x3_resident(M, N, C1 + C2, hint)
+    entry, _ = _route(M, False, False, False, f32t_ok, _x3_ok(C1, C2, N, hint if 0 < hint < M else M), resident)
+    return entry == "d3f_gemm_x3" and not resident
+
+
+def upsample_split_ok(u, N):
+    """_split_ok of the decoder block that consumes the UpsampleCat `u` with N output columns."""
+    if u.skip is None or u.x.dim() != 2 or u.skip.dim() != 2 or u.inds.dim() != 2:
+        return False
+    f32 = u.x.dtype == torch.float32 and u.skip.dtype == torch.float32
+    aligned = all(t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 for t in (u.x, u.skip))
+    return _split_ok(u.inds.shape[0], u.x.shape[1], u.skip.shape[1], N, int(getattr(u.inds, "n_hint", 0) or 0), f32, aligned and N % 4 == 0)
+
+
+def gemm_upsample_split(u, W1, W2, col_shift=None, leaky=False, alpha=0.2, out=None):
+    """out = act(x'[inds[:,0]] @ W1 + skip @ W2 + col_shift) in two launches: Y = x @ W1 over the COARSE rows, then
+    act(skip @ W2 + col_shift + Y[inds[:,0]]) over the fine ones (an index outside x's rows adds zeros: the zero row of x').  A
+    per-column scale is folded into W1 / W2 by the caller (VariableStore.split_decoder).  Only where upsample_split_ok holds."""
+    lib = _lib.load()
+    x, _ = _rows(_req(u.x, torch.float32, "x"), "x")
+    inds, ldi = _rows(_req(u.inds, torch.int32, "inds"), "inds")
+    if u.skip is None:
+        raise ValueError("gemm_upsample_split: no skip operand (use gemm_upsample_cat)")
+    skip, lds = _rows(_req(u.skip, torch.float32, "skip"), "skip")
+    W1, _ = _rows(_req(W1, torch.float32, "W1"), "W1")
+    W2, _ = _rows(_req(W2, torch.float32, "W2"), "W2")
+    C1, C2, M, N = x.shape[1], skip.shape[1], inds.shape[0], W2.shape[1]
+    if W1.shape != (C1, N) or W2.shape[0] != C2 or skip.shape[0] != M or not (W1.is_contiguous() and W2.is_contiguous()):
+        raise ValueError("gemm_upsample_split: operands %s | %s, W1 %s, W2 %s" % (tuple(x.shape), tuple(skip.shape), tuple(W1.shape),
+                                                                                   tuple(W2.shape)))
+    if not upsample_split_ok(u, N):
+        raise ValueError("gemm_upsample_split: not a call of the split form (ops.upsample_split_ok): use gemm_upsample_cat")
+    Y = gemm(x, W1)
+    dev, hint = x.device, int(getattr(inds, "n_hint", 0) or 0)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or not out.is_contiguous() or out.data_ptr() % 16:
+        raise ValueError("gemm_upsample_split: out must be a contiguous, 16-byte aligned float32 [%d, %d]" % (M, N))
+    if col_shift is not None and (col_shift.data_ptr() % 16 or col_shift.numel() != N):
+        raise ValueError("gemm_upsample_split: col_shift must be a 16-byte aligned vector of %d" % N)
+    Wp = packed_x3_weights(W2)
+    ws = workspace(lib.d3f_gemm_x3_workspace_bytes(M, N, C2, hint), dev)
+    with _timed("gemm_x3", dict(M=M, N=N, K=C2), dev):
+        rc = lib.d3f_gemm_x3_gres(skip.data_ptr(), M, lds, C2, None, 0, None, 0, 0, Wp.data_ptr(), out.data_ptr(), N, M, N, None, None,
+                                  _ptr(col_shift), Y.data_ptr(), N, inds.data_ptr(), ldi, x.shape[0], _nd(x), 1 if leaky else 0,
+                                  float(alpha), ws.data_ptr(), ws.numel(), _nd(inds), None, hint, _stream(dev))
+    _lib.check(rc, "gemm_x3_gres")
+    return _tag(out, inds)
+
+
 def gemm_cat2(A1, A2, W, col_scale=None, col_shift=None, leaky=False, alpha=0.2):
     """out = act(([A1 | A2] @ W) * col_scale + col_shift) without building the concatenation (same rows in A1 and A2)."""
     A1, ld1 = _rows(_feat(A1, "A1"), "A1")

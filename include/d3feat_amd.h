@@ -436,6 +436,17 @@ int d3f_gemm_x3(const float* A, int N1, int lda, int C1, const int* idx, int ld_
                 const void* Wx, float* C, int ldc, int M, int N, const float* row_scale, const float* col_scale,
                 const float* col_shift, const float* residual, int ldr, int leaky, float alpha, void* workspace,
                 size_t workspace_bytes, const int* M_dev, const int* N1_dev, int M_hint, void* stream);
+/* d3f_gemm_x3 with a GATHERED residual operand: output row m adds residual[res_idx[m * ld_res_idx]] (int32 indices, ld_res_idx >= 1)
+ * instead of residual[m].  The residual tensor has res_rows rows (*res_rows_dev of them when that pointer is given); an index outside
+ * [0, rows) -- the shadow index of an upsampling matrix, a negative one -- adds exact zeros.  It is the fine-level half of a decoder
+ * block whose upsampled half Y = x @ W[:C1] was contracted once per coarse row: leaky(skip @ W[C1:] + shift + Y[up[m, 0]]).  Always
+ * the tile form (d3f_gemm_x3_plan), whatever d3f_gemm_x3_resident answers; res_idx == NULL is d3f_gemm_x3 itself.  D3F_ERR_ARG on top
+ * of d3f_gemm_x3's rules: res_idx without a residual, ld_res_idx < 1, res_rows < 0. */
+int d3f_gemm_x3_gres(const float* A, int N1, int lda, int C1, const int* idx, int ld_idx, const float* skip, int lds, int C2,
+                     const void* Wx, float* C, int ldc, int M, int N, const float* row_scale, const float* col_scale,
+                     const float* col_shift, const float* residual, int ldr, const int* res_idx, int ld_res_idx, int res_rows,
+                     const int* res_rows_dev, int leaky, float alpha, void* workspace, size_t workspace_bytes, const int* M_dev,
+                     const int* N1_dev, int M_hint, void* stream);
 
 /* bf16-operand form of the contractions (BASELINE.json configs[4]: batched inference, bf16 MFMA contraction): the operator of
  * d3f_gemm_f32 / d3f_gemm_upsample_cat_f32 -- A f32[M, C1] (rows in place when idx == NULL, else the gathered rows
