@@ -711,6 +711,7 @@ __global__ void __launch_bounds__(256) gs_emit_kernel(int* __restrict__ status, 
                                                       float* __restrict__ out_p, int out_cap) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= status[0]) return;
+    if (status[1] & (D3F_ST_OUT_OVERFLOW | D3F_ST_KEY_WIDTH)) return;   // reported empty: no row is written (as the one-workgroup form)
     const int b = d3f_find_elem(moffs, B, v);
     const size_t dest = (size_t)moffs[b] + (size_t)vpos[v];
     if (dest >= (size_t)out_cap) {   // (cannot happen once the epilogue has checked M: kept as the last line of defence)
@@ -844,7 +845,7 @@ static int gs_run_small(const float* points, int N, const int* lens_dev, int B, 
     A.mcount = ar.take<int>(B);
     A.cflags = ar.take<int>(B);
     if (!ar.ok) return D3F_ERR_WORKSPACE;
-    A.pts = points; A.lens = lens_dev; A.B = B; A.dl = dl; A.elem_cap = elem_cap; A.out_cap = M_cap;
+    A.pts = points; A.lens = lens_dev; A.B = B; A.dl = dl; A.elem_cap = elem_cap; A.pc = pc; A.out_cap = M_cap;
     // the largest iteration-order round that has to fit the workgroup's LDS: the first chain value >= the voxel capacity
     A.nbmax = GSS_NB_MAX;
     for (int j = 0; j < D3F_NCHAIN; ++j)

@@ -13,7 +13,7 @@
 // a second, trivial launch packs the B blocks into the contiguous [M, 3] output and writes lengths / status (the offsets need
 // every cloud's voxel count).  Same results, bit for bit, as the other two forms (tests/gs_sort_path_check.py).
 // Limits, checked on the device and reported like every other capacity (D3F_ST_OUT_OVERFLOW -> empty result, the caller's eager
-// path recomputes): a cloud of more than T * R points, more than `nbmax` voxels in a cloud, a grid of more than 2^32 cells.
+// path recomputes): a cloud of more than elem_points_cap (<= T * R) points, more than `nbmax` voxels in a cloud, a grid of more than 2^32 cells.
 #pragma once
 
 #define GSS_NB_MAX 5087
@@ -26,6 +26,7 @@ struct GsSmallArgs {
     float* stage;          // [B][elem_cap][3]   barycentres by iteration-order position
     float* recs;           // [B][elem_cap][4]   scratch: {barycentre, key} by voxel id (16-byte aligned)
     int elem_cap;
+    int pc;                // the caller's point capacity of one cloud (<= T * R of the launch)
     int out_cap;           // rows of the final output
     int nbmax;             // largest bucket count whose round fits the LDS of this launch (a chain value)
     int* mcount;           // [B] voxels per cloud (0 when the cloud could not be processed)
@@ -82,7 +83,9 @@ __global__ void __launch_bounds__(T) gs_small_kernel(GsSmallArgs A) {
     const int len = A.lens[b];
     int* sFlag = sScr + 127;
     if (tid == 0) { A.mcount[b] = 0; *sFlag = 0; }
-    if (len <= 0 || len > NI) {     // (an empty cloud is UB in the reference, cloud.cpp:30,51; a cloud beyond T * R points: capacity)
+    // (an empty cloud is UB in the reference, cloud.cpp:30,51; a cloud above the caller's point capacity is reported as the header
+    // says, also where the T * R points of this launch would still hold it: the forms report alike)
+    if (len <= 0 || len > NI || len > A.pc) {
         if (tid == 0) A.cflags[b] = len <= 0 ? D3F_ST_EMPTY_ELEMENT : D3F_ST_OUT_OVERFLOW;
         return;
     }

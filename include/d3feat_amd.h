@@ -93,7 +93,8 @@ size_t d3f_grid_subsample_workspace_bytes(int N, int B, int fdim, int ldim);
  * are launched for that size, so a stack of B similar clouds should pass its per-cloud capacity; elem_points_cap bounds the
  * POINTS of any one batch element (0: N_cap): when it is at most 16384 every cloud is subsampled by ONE workgroup out of LDS
  * (two launches per call instead of ~25: the coarse pyramid levels); status_dev i32[2] (DEVICE) = [M, OR of D3F_ST_* flags];
- * M > M_cap, an element above elem_cap or above elem_points_cap raises D3F_ST_OUT_OVERFLOW (empty result).
+ * M > M_cap, an element above elem_cap or above elem_points_cap raises D3F_ST_OUT_OVERFLOW (empty result: status_dev[0] = 0, every
+ * length 0, no row of sub_points written -- by every form alike).
  * Workspace: d3f_grid_subsample_workspace_bytes(N_cap, B, 0, 0). */
 int d3f_batch_grid_subsample_async(const float* points, int N_cap, const int* lens_dev, int B, float dl,
                                    float* sub_points, int M_cap, int elem_cap, int elem_points_cap, int* sub_lens_dev,

@@ -1,8 +1,20 @@
-"""Run as a subprocess (tests/test_gpu_preprocess.py): the capacity-mode subsampler's SORT form (csrc/radix_sort.h + the
-gs_sortkey / gs_heads / gs_runs / gs_emit kernels) and its ONE-WORKGROUP-PER-CLOUD form (csrc/gs_small.h, clouds of at most
-16384 points: elem_points) must return bit for bit what the ORACLE (oracle/d3f_oracle.c, pinned to the reference's C++) and the
-synchronous call (hash form) return: ragged stacks, duplicates, one-point clouds, sizes around the 4096-item sort tile, 100 clouds per stack, a grid that
-needs 4 digit passes, a capacity tail -- and a grid too wide for the 32-bit sort key is REPORTED (D3F_ST_KEY_WIDTH), empty."""
+"""Run as a subprocess (tests/test_gpu_preprocess.py): the capacity-mode subsampler must return bit for bit what the ORACLE
+(oracle/d3f_oracle.c, pinned to the reference's C++) and the synchronous call (hash form) return, on 19 seeded random stacks: ragged
+stacks, duplicates, one-point clouds, 100 clouds per stack, a grid that needs 4 digit passes, a capacity tail -- and a grid too
+wide for the 32-bit sort key is REPORTED (D3F_ST_KEY_WIDTH), empty.
+
+What runs (the dispatcher's arithmetic, gs_run / gs_run_small, redone on the host by oracle/subsample_cases.form for these seeds;
+N_cap = N + 1000 everywhere):
+  * the first entry of a case (elem_points = 0, elem_cap = the largest cloud) takes the SORT form (csrc/radix_sort.h + the
+    gs_sortkey / gs_heads / gs_runs / gs_emit kernels) in ten cases -- N = 13656 .. 919709, 2 digit passes twice, 3 seven times,
+    4 once -- and the ONE-WORKGROUP form (csrc/gs_small.h) in the other nine, where N_cap <= 16384 and the largest cloud <= 5087:
+    among them (1, 4096) and (1, 4097), whose clouds of 3543 and 3877 points are one workgroup's work, not a sort tile's edge
+    (RS_TILE is 8192; no case puts a sort-form size on it);
+  * the second entry (elem_points = the largest cloud, elem_cap = the largest voxel count; only where the cloud fits) always takes
+    the one-workgroup form: gs_small_kernel<256,8>, <512,8>, <1024,8> and, through N_cap = N + 1000 falling into its band, <1024,12>;
+    <1024,16> is never launched and the largest cloud any one-workgroup call holds has 3980 points.
+Every branch by design -- tile edges, all five instantiations, 1-pass keys, kb == 32, the order-round boundaries -- is in
+tests/test_gpu_subsample_branches.py; this script stays as the check at workload sizes."""
 import os
 import sys
 

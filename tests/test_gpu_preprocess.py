@@ -146,10 +146,13 @@ def test_full_size_properties(device):
 
 
 def test_capacity_mode_forms_of_the_subsampler_equal_the_oracle():
-    """The capacity-mode subsampler (no hash table: stable radix sort, csrc/radix_sort.h; clouds of at most 16384 points: one
-    workgroup per cloud out of LDS, csrc/gs_small.h) against the ORACLE and the synchronous (hash) call, bit for bit: ragged
-    stacks, duplicates, one-point clouds, sizes around the sort tile, 100 clouds per stack, 4-pass keys, capacity tails, and the
-    reported limits (key wider than 32 bits, cloud above its point capacity, more voxels than the LDS rounds hold)."""
+    """The capacity-mode subsampler against the ORACLE and the synchronous (hash) call, bit for bit, on the 19 seeded random stacks
+    of tests/gs_sort_path_check.py: ragged stacks, duplicates, one-point clouds, 100 clouds per stack, 4-pass keys, capacity tails,
+    and the reported limits (key wider than 32 bits, cloud above its point capacity, more voxels than the LDS rounds hold).  Which
+    form a call takes follows from its capacities, not from its label: ten cases run the sort form (csrc/radix_sort.h; 13656 to
+    919709 rows, 2 to 4 digit passes) on their first entry, the other nine -- the 4096- and 4097-point cases among them -- and every
+    second entry run one workgroup per cloud out of LDS (csrc/gs_small.h; clouds of at most 3980 points, never <1024,16>).  The
+    script's docstring has the list; tests/test_gpu_subsample_branches.py has the branches by design."""
     import os
     import subprocess
     import sys
