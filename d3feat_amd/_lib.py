@@ -85,6 +85,9 @@ SIGNATURES = {
     "d3f_repeatability_pairs": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "d3f_match_pairs_workspace_bytes": (_sz, [_i, _vp, _i]),
     "d3f_match_pairs": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _f, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "d3f_register_pairs_counts_workspace_bytes": (_sz, [_i, _i, _i, _vp, _i, _i]),
+    "d3f_register_pairs_counts": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _f, _i, _f, _f, _i, _i, C.c_uint64, _vp, _f] + [_vp] * 10
+                                  + [_sz, _vp]),
     "d3f_overlap_pairs": (_i, [_vp, _sz, _i, _i, _vp, _i, _f, _vp, _vp, _i, _vp]),
     "d3f_gemm_pack_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_pack_f32t": (_i, [_vp, _i, _i, _i, _vp, _vp]),

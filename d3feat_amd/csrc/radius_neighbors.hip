@@ -819,3 +819,6 @@ extern "C" int d3f_batch_radius_neighbors(const float* queries, int Nq, const fl
     return d3f_neighbor_grid_search(workspace, gb, Ns, queries, Nq, q_lens_dev, B, radius, 0, out, ld, width, pad_value,
                                     D3F_NEIGHBOR_CAP, 0, 0.f, 1, status_dev, stream_);
 }
+
+// ---- RANSAC registration of every pair at every keypoint count: the stack, the grid, scoring and selection (nb_register_counts.h) --
+#include "nb_register_counts.h"

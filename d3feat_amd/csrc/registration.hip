@@ -453,25 +453,17 @@ __global__ void __launch_bounds__(256) rp_match_kernel(const float* __restrict__
     }
 }
 
-__global__ void __launch_bounds__(256) rp_hypotheses_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
-                                                            const int* __restrict__ count, const int* __restrict__ pairs, int nk, int Kmax,
-                                                            const int* __restrict__ nn_st, int n, float radius, float edge_sim,
-                                                            float dist_thr, unsigned long long seed, int max_iteration,
-                                                            int max_validation, float* __restrict__ Tlist, int* __restrict__ itlist,
-                                                            int* __restrict__ validations, int* __restrict__ iterations) {
-    __shared__ int wsum[4];
-    __shared__ int cand[RP_CHUNK];
-    const int p = blockIdx.x;
-    const RpRows a = rp_rows(count, pairs, p, 0, n_blocks, K, nk), b = rp_rows(count, pairs, p, 1, n_blocks, K, nk);
-    if (a.n < n || b.n < n || radius <= 0.f) {   // registration.py: nothing is tried
-        if (threadIdx.x == 0) { validations[p] = 0; iterations[p] = 0; }
+// The walk of one pair: S / T the rows it uses (ns / nt of them, ld floats apart), nn the nearest target FEATURE of every source row in
+// that numbering; Tl / il its lists of max_validation entries, nval_out / iter_out its two counts.  The whole workgroup.
+__device__ __forceinline__ void rp_hypotheses_walk(const float* __restrict__ S, int ns, const float* __restrict__ T, int nt, int ld,
+                                                   const int* __restrict__ nn, int n, float radius, float edge_sim, float dist_thr,
+                                                   unsigned long long seed, int max_iteration, int max_validation,
+                                                   float* __restrict__ Tl, int* __restrict__ il, int* __restrict__ nval_out,
+                                                   int* __restrict__ iter_out, int* wsum, int* cand) {
+    if (ns < n || nt < n || radius <= 0.f) {   // registration.py: nothing is tried
+        if (threadIdx.x == 0) { *nval_out = 0; *iter_out = 0; }
         return;
     }
-    const float* S = kp + ((size_t)a.blk * K + a.r0) * ld;
-    const float* T = kp + ((size_t)b.blk * K + b.r0) * ld;
-    const int* nn = nn_st + (size_t)p * Kmax;
-    float* Tl = Tlist + (size_t)p * max_validation * 12;
-    int* il = itlist + (size_t)p * max_validation;
     int nval = 0;
     for (int it0 = 0; it0 < max_iteration && nval < max_validation; it0 += RP_CHUNK) {
         // the cheap step for RP_CHUNK iterations: the ones whose sample passes, in iteration order
@@ -479,7 +471,7 @@ __global__ void __launch_bounds__(256) rp_hypotheses_kernel(const float* __restr
         for (int k = 0; k < RP_CHUNK; k += 256) {
             const int it = it0 + k + threadIdx.x;
             RgSample q;
-            const bool pass = it < max_iteration && rg_sample(S, ld, a.n, T, ld, b.n, nn, n, edge_sim, seed, (unsigned long long)it, q);
+            const bool pass = it < max_iteration && rg_sample(S, ld, ns, T, ld, nt, nn, n, edge_sim, seed, (unsigned long long)it, q);
             const int slot = ncand + rp_block_prefix(pass, wsum, total);
             if (pass) cand[slot] = it;
             ncand += total;
@@ -492,22 +484,37 @@ __global__ void __launch_bounds__(256) rp_hypotheses_kernel(const float* __restr
             bool ok = false;
             if (c < ncand) {
                 RgSample q;
-                rg_sample(S, ld, a.n, T, ld, b.n, nn, n, edge_sim, seed, (unsigned long long)it, q);
+                rg_sample(S, ld, ns, T, ld, nt, nn, n, edge_sim, seed, (unsigned long long)it, q);
                 ok = rg_fit(q, n, dist_thr, out);
             }
             const int slot = nval + rp_block_prefix(ok, wsum, total);
             if (ok && slot < max_validation) {
                 for (int k = 0; k < 12; ++k) Tl[(size_t)slot * 12 + k] = out[k];
                 il[slot] = it;
-                if (slot == max_validation - 1) iterations[p] = it + 1;
+                if (slot == max_validation - 1) *iter_out = it + 1;
             }
             nval += total;
         }
     }
     if (threadIdx.x == 0) {
-        validations[p] = min(nval, max_validation);
-        if (nval < max_validation) iterations[p] = max_iteration;
+        *nval_out = min(nval, max_validation);
+        if (nval < max_validation) *iter_out = max_iteration;
     }
+}
+
+__global__ void __launch_bounds__(256) rp_hypotheses_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
+                                                            const int* __restrict__ count, const int* __restrict__ pairs, int nk, int Kmax,
+                                                            const int* __restrict__ nn_st, int n, float radius, float edge_sim,
+                                                            float dist_thr, unsigned long long seed, int max_iteration,
+                                                            int max_validation, float* __restrict__ Tlist, int* __restrict__ itlist,
+                                                            int* __restrict__ validations, int* __restrict__ iterations) {
+    __shared__ int wsum[4];
+    __shared__ int cand[RP_CHUNK];
+    const int p = blockIdx.x;
+    const RpRows a = rp_rows(count, pairs, p, 0, n_blocks, K, nk), b = rp_rows(count, pairs, p, 1, n_blocks, K, nk);
+    rp_hypotheses_walk(kp + ((size_t)a.blk * K + a.r0) * ld, a.n, kp + ((size_t)b.blk * K + b.r0) * ld, b.n, ld, nn_st + (size_t)p * Kmax, n,
+                       radius, edge_sim, dist_thr, seed, max_iteration, max_validation, Tlist + (size_t)p * max_validation * 12,
+                       itlist + (size_t)p * max_validation, validations + p, iterations + p, wsum, cand);
 }
 
 // grid (P, slices of RP_SLICE hypotheses).  cnt / sd2 [P, max_validation]: every (pair, hypothesis) has exactly one writer.
@@ -786,3 +793,8 @@ extern "C" int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int
 // Feature-matching recall of every pair at every keypoint count in two launches (d3f_match_pairs)
 // ---------------------------------------------------------------------------------------------------------------------
 #include "rp_matching.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// RANSAC registration of every pair at every keypoint count in one call (d3f_register_pairs_counts)
+// ---------------------------------------------------------------------------------------------------------------------
+#include "rp_register_counts.h"

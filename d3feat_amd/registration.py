@@ -13,6 +13,8 @@
                                             (repeatability/evaluate_3dmatch_our.py:30-41, evaluate_kitti_our.py:12-23; float64)
     match_pairs(kp, count, pairs, gt)       feature-matching recall figures (mutual matches, inliers under gt) of every pair at every
                                             keypoint count in two launches (evaluate.py:45-50,67-82), up to 8192 rows per block
+    register_pairs_counts(kp, count, pairs, ...) register_pairs AND match_pairs for every pair at every keypoint count in one call
+                                            (evaluate.py:45-50,67-99 swept over num_keypts), up to 8192 rows per block
 
 Every computation is a kernel of libd3feat_amd.so (csrc/registration.hip, csrc/radius_neighbors.hip); numpy / torch only
 move data and run the host loop over batches of hypotheses.  Open3D's own random stream is unspecified, so results are
@@ -475,4 +477,130 @@ def match_pairs(kp, count, pairs, gt=None, num_keypts=MATCHING_COUNTS, distance_
                                  out.mutual_count[s].data_ptr(), out.gt_inliers[s].data_ptr() if gt is not None else None,
                                  ws.data_ptr(), ws.numel(), st)
         _lib.check(rc, "match_pairs")
+    return out
+
+
+# ---- RANSAC registration of every pair at every count in one call (geometric_registration/evaluate.py:45-50,67-99) -----------------
+class PairRegistrationCounts:
+    """Result of register_pairs_counts: DEVICE tensors, one row per pair and count (num_keypts is the tuple of the n counts).
+    T f32[P,n,3,4] ([R | t] of the winner, identity without one), inliers / validations / iterations / best_iteration (-1: none) /
+    mutual_count i32[P,n], sumd2 i64[P,n] (2^-32 units), gt_inliers i32[P,n] when gt was given, nearest i32[P, sum of the counts] when
+    asked for: entries offsets[c] .. offsets[c] + num_keypts[c] - 1 are the target rows of the source rows under the winner of count c
+    (-1: none).  Rows are numbered inside the rows a pair uses at that count (the last min(count, num_keypts[c]) of a block)."""
+    FIELDS = ("T", "inliers", "sumd2", "validations", "iterations", "best_iteration", "mutual_count", "gt_inliers", "nearest")
+
+    def __init__(self, P, num_keypts, device, gt, nearest):
+        i32 = dict(dtype=torch.int32, device=device)
+        self.P, self.num_keypts = P, tuple(num_keypts)
+        n = len(self.num_keypts)
+        self.offsets = tuple(int(x) for x in np.concatenate([[0], np.cumsum(self.num_keypts)[:-1]]))
+        self.T = torch.empty((P, n, 3, 4), dtype=torch.float32, device=device)
+        self.inliers, self.validations, self.iterations = (torch.empty((P, n), **i32) for _ in range(3))
+        self.best_iteration, self.mutual_count = torch.empty((P, n), **i32), torch.empty((P, n), **i32)
+        self.sumd2 = torch.empty((P, n), dtype=torch.int64, device=device)
+        self.gt_inliers = torch.empty((P, n), **i32) if gt else None
+        self.nearest = torch.empty((P, sum(self.num_keypts)), **i32) if nearest else None
+        self.ns = self.nt = None
+
+    _cache = None
+
+    def _host(self):
+        # one read-back of the whole result, kept until the next register_pairs_counts(out=self)
+        if self._cache is None:
+            self._cache = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS + ("ns", "nt") if getattr(self, k) is not None}
+        return self._cache
+
+    def at(self, c):
+        """The device tensors of count num_keypts[c], shaped as PairRegistration's: a dict name -> tensor ([P, ...] views)."""
+        k, o = self.num_keypts[c], self.offsets[c]
+        out = {f: getattr(self, f)[:, c] for f in self.FIELDS[:-1] if getattr(self, f) is not None}
+        if self.nearest is not None:
+            out["nearest"] = self.nearest[:, o:o + k]
+        return out
+
+    def host(self, p, c):
+        """The dict PairRegistration.host(p) returns, for pair p at count num_keypts[c] (`correspondences` needs register_pairs;
+        `correspondence_set` needs nearest=True)."""
+        h = self._host()
+        Ns, cnt = int(h["ns"][p, c]), np.int64(h["inliers"][p, c])
+        sd2 = np.float64(h["sumd2"][p, c]) / 4294967296.0
+        M = np.eye(4)
+        M[:3, :4] = h["T"][p, c].astype(np.float64)
+        out = dict(transformation=M, fitness=float(cnt) / Ns if Ns else 0.0, inlier_rmse=float(np.sqrt(sd2 / np.maximum(cnt, 1))),
+                   iterations=int(h["iterations"][p, c]), validations=int(h["validations"][p, c]),
+                   best_iteration=int(h["best_iteration"][p, c]), mutual_count=int(h["mutual_count"][p, c]))
+        if "nearest" in h:
+            near = h["nearest"][p, self.offsets[c]:self.offsets[c] + Ns]
+            sel = np.nonzero(near >= 0)[0]
+            out["correspondence_set"] = np.stack([sel, near[sel]], 1).astype(np.int64)
+        if "gt_inliers" in h:
+            k = out["mutual_count"]
+            out["gt_inliers"] = int(h["gt_inliers"][p, c])
+            out["inlier_ratio"] = out["gt_inliers"] / k if k else 0.0
+        return out
+
+
+def register_pairs_counts(kp, count, pairs, max_correspondence_distance, num_keypts=MATCHING_COUNTS, ransac_n=4, edge_similarity=0.9,
+                          checker_distance=None, max_iteration=100000, max_validation=100, seed=0, gt=None, distance_threshold=0.10,
+                          nearest=False, out=None):
+    """register_keypoints for P pairs of keypoint blocks at every count of `num_keypts` in one call (geometric_registration/evaluate.py:
+    45-50, 67-99, whose num_keypts = 250 is edited by hand for the sweep): kp f32[n_blocks, K, ld] ([xyz | desc | score] rows in
+    ascending score order, keypoints.topk_records / stack_keypoints; at most 255 blocks), count i32[n_blocks], pairs i32[P, 2] (source,
+    target) block indices, all on the device.  Count k uses the last min(count, k) rows of both blocks; per pair and count the result
+    is bit-identical to register_keypoints(kp[a, :count[a]], kp[b, :count[b]], num_keypts=k, ...) -- the keywords are
+    ransac_feature_matching's -- and, for k <= 1024, to register_pairs(num_keypts=k); mutual_count / gt_inliers are match_pairs'.  No
+    block is kept in LDS (blocks of up to 8192 rows), the nearest target point of every hypothesis comes from ONE cell grid over all
+    blocks.  Twelve launches per entry-point call, PAIRS_PER_CALL (pair, count) results each, no read-back and no host decision in
+    between (capturable: pass the previous result as `out`).  gt f32[P, 3, 4] (target -> source) adds gt_inliers; nearest=True adds
+    the winner's correspondences.  num_keypts: strictly ascending, 1 .. 8192, at most 16 of them.
+    -> PairRegistrationCounts (device tensors; .host(p, c) for a dict, .at(c) for the tensors of one count)."""
+    lib = _lib.load()
+    kp = ops._req(kp, torch.float32, "kp", 3)
+    count = ops._req(count, torch.int32, "count", 1)
+    pairs = ops._req(pairs, torch.int32, "pairs", 2)
+    dev = kp.device
+    if not kp.is_contiguous() or not count.is_contiguous() or not pairs.is_contiguous() or pairs.shape[1] != 2:
+        raise ValueError("register_pairs_counts: kp, count and pairs must be contiguous, pairs [P, 2]")
+    n_blocks, K, ld = kp.shape
+    C = ld - 4
+    if count.shape[0] != n_blocks or not 1 <= n_blocks <= _lib.MAX_BATCH or K < 1 or C not in (16, 32, 64) or not 3 <= int(ransac_n) <= 8:
+        raise ValueError("register_pairs_counts takes 1 to %d blocks, descriptors of 16, 32 or 64 floats and ransac_n in 3..8 (got kp %s, "
+                         "count %s, ransac_n %s)" % (_lib.MAX_BATCH, tuple(kp.shape), tuple(count.shape), ransac_n))
+    ks = [int(k) for k in num_keypts]
+    if (not 1 <= len(ks) <= _lib.REPEAT_COUNTS_MAX or any(not 1 <= k <= _lib.MATCH_KMAX for k in ks)
+            or any(b <= a for a, b in zip(ks, ks[1:]))):
+        raise ValueError("register_pairs_counts: num_keypts %s must be 1 to %d strictly ascending counts in 1..%d"
+                         % (ks, _lib.REPEAT_COUNTS_MAX, _lib.MATCH_KMAX))
+    P = pairs.shape[0]
+    if gt is not None:
+        gt = ops._req(gt, torch.float32, "gt", 3)
+        if tuple(gt.shape) != (P, 3, 4) or not gt.is_contiguous():
+            raise ValueError("register_pairs_counts: gt of shape %s for %d pairs" % (tuple(gt.shape), P))
+    if out is None:
+        out = PairRegistrationCounts(P, ks, dev, gt is not None, nearest)
+    elif (not isinstance(out, PairRegistrationCounts) or out.T.device != dev
+          or (out.P, out.num_keypts, out.gt_inliers is not None, out.nearest is not None) != (P, tuple(ks), gt is not None, bool(nearest))):
+        raise ValueError("register_pairs_counts: out= was made for another call")
+    out._cache = None
+    # rows each pair uses at each count (plumbing for host(): fitness = inliers / Ns)
+    used = torch.stack([count.clamp(0, min(K, k)) for k in ks], 1)                  # (device only: nothing to copy under capture)
+    valid = (pairs >= 0) & (pairs < n_blocks)
+    rows = used[pairs.clamp(0, n_blocks - 1).long()] * valid[:, :, None]           # [P, 2, n]
+    out.ns, out.nt = rows[:, 0], rows[:, 1]
+    st = ops._stream(dev)
+    c_ks, n, mv = (_lib.C.c_int * len(ks))(*ks), len(ks), int(max_validation)
+    per_call = max(PAIRS_PER_CALL // n, 1)
+    for p0 in range(0, P, per_call):
+        s = slice(p0, min(p0 + per_call, P))
+        m = s.stop - s.start
+        ws = ops.workspace(lib.d3f_register_pairs_counts_workspace_bytes(m, n_blocks, K, _lib.C.addressof(c_ks), n, mv), dev)
+        rc = lib.d3f_register_pairs_counts(
+            kp.data_ptr(), n_blocks, K, ld, C, count.data_ptr(), pairs[s].data_ptr(), m, _lib.C.addressof(c_ks), n,
+            float(max_correspondence_distance), int(ransac_n), float(edge_similarity or 0.0), float(checker_distance or 0.0),
+            int(max_iteration), mv, int(seed), gt[s].data_ptr() if gt is not None else None, float(distance_threshold),
+            out.T[s].data_ptr(), out.inliers[s].data_ptr(), out.sumd2[s].data_ptr(), out.validations[s].data_ptr(),
+            out.iterations[s].data_ptr(), out.best_iteration[s].data_ptr(), out.mutual_count[s].data_ptr(),
+            out.gt_inliers[s].data_ptr() if gt is not None else None, out.nearest[s].data_ptr() if nearest else None,
+            ws.data_ptr(), ws.numel(), st)
+        _lib.check(rc, "register_pairs_counts")
     return out

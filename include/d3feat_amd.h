@@ -595,6 +595,45 @@ int d3f_match_pairs(const float* kp, int n_blocks, int K, int ld, int C, const i
                     const float* gt, float distance_threshold, const int* num_keypts_host, int n_counts, int* mutual_count,
                     int* gt_inliers, void* workspace, size_t workspace_bytes, void* stream);
 
+/* RANSAC registration of P pairs of keypoint blocks at n_counts keypoint counts in one call (geometric_registration/evaluate.py:45-50,
+ * 67-99, whose num_keypts is edited by hand to sweep 5000 / 2500 / 1000 / 500 / 250): per pair p and count k_c everything
+ * d3f_register_pairs computes for num_keypts = k_c, bit for bit, without its limit of D3F_PAIRS_KMAX rows -- no kernel of this call
+ * keeps a block in LDS, the nearest target POINT comes from one cell grid over all blocks.  Twelve launches whatever P and the
+ * counts are, no allocation, no read-back, no host decision between the launches, no memset: capturable on one stream.
+ * kp / count_dev / pairs_dev as d3f_register_pairs takes them (rows [xyz | C-d descriptor | score] in ascending score order, C in
+ * {16, 32, 64}, ld >= C + 4, an index outside [0, n_blocks) selects an empty block), n_blocks <= D3F_MAX_BATCH; K may exceed every count.
+ *   num_keypts_host: n_counts ints on the host, strictly ascending, each in 1 .. D3F_MATCH_KMAX, 1 <= n_counts <=
+ *     D3F_REPEAT_COUNTS_MAX; read before the call returns.  Count k_c uses the LAST min(count, k_c) rows of each block, Ns source and
+ *     Nt target rows, numbered from 0 inside those rows (the numbering of d3f_register_pairs at num_keypts = k_c).
+ *   mutual_count, gt_inliers i32[P, n_counts]: what d3f_match_pairs writes for the same counts; gt (optional) f32[P, 12] row-major
+ *     [R | t] taking the TARGET frame into the SOURCE frame, distance_threshold as there; gt_inliers is required with gt.
+ *   RANSAC per (pair, count) exactly as d3f_ransac_hypotheses defines iteration it = 0, 1, ... for (seed, it) on the Ns source rows,
+ *     the Nt target rows and the source -> target nearest descriptors of that count (the draws of d3f_ransac_draw run over Ns): the
+ *     first max_validation valid iterations below max_iteration are scored as d3f_neighbor_grid_score scores them (nearest target
+ *     row strictly inside max_correspondence_distance by (d2, row), the metric never contracted); the winner has the largest count,
+ *     then the smallest sumd2, then the smallest iteration.
+ *     T_out f32[P, n_counts, 12], inliers / validations / iterations / best_iteration i32[P, n_counts] (best_iteration -1: none),
+ *     sumd2 u64[P, n_counts] (2^-32 units), nearest (optional) i32[P, sum of the counts]: entry off_c + i, off_c = k_0 + ... + k_{c-1},
+ *     is the target row of source row i under the winner of count c, -1 for none and for padding (i >= Ns).
+ *     Ns < ransac_n, Nt < ransac_n or max_correspondence_distance <= 0: identity, every count 0, best_iteration -1.
+ * ONE GRID FOR EVERY COUNT: the grid holds the last min(count, k_max) rows of every block, k_max the largest count.  At count k_c the
+ * rows of a block are the records with index >= min(count, k_max) - min(count, k_c); the others are skipped, and a constant shift of
+ * the index keeps the (d2, index) order, so the minimum over the kept records is the row d3f_register_pairs finds.
+ * D3F_ERR_ARG before anything touches the device: n_blocks > D3F_MAX_BATCH, n_counts or a count out of range, counts not strictly
+ * ascending, and every size d3f_register_pairs refuses (P < 0, n_blocks or K < 1, C not 16 / 32 / 64, ld < C + 4, ransac_n outside
+ * 3 .. 8, max_iteration outside 0 .. 2^30, max_validation outside 1 .. 2^20, a NaN distance, a NULL pointer other than gt, gt_inliers
+ * without gt and nearest); P == 0 is D3F_OK without a launch.  workspace >= d3f_register_pairs_counts_workspace_bytes(...), else
+ * D3F_ERR_WORKSPACE: 64 bytes per pair, count and validation, 12 bytes per pair and row of every count, and the stack and grid of
+ * n_blocks * min(K, k_max) points; the function returns 0 for sizes the call refuses.  Asynchronous on `stream`. */
+size_t d3f_register_pairs_counts_workspace_bytes(int P, int n_blocks, int K, const int* num_keypts_host, int n_counts,
+                                                 int max_validation);
+int d3f_register_pairs_counts(const float* kp, int n_blocks, int K, int ld, int C, const int* count_dev, const int* pairs_dev, int P,
+                              const int* num_keypts_host, int n_counts, float max_correspondence_distance, int ransac_n,
+                              float edge_similarity, float checker_distance, int max_iteration, int max_validation, uint64_t seed,
+                              const float* gt, float distance_threshold, float* T_out, int* inliers, uint64_t* sumd2,
+                              int* validations, int* iterations, int* best_iteration, int* mutual_count, int* gt_inliers,
+                              int* nearest, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Overlap of P pairs of a scene's fragments in two launches, whatever P is (datasets/cal_overlap.py:78-126: for every pair the
  * nearest point of the second fragment for each point of the first, the matches closer than the voxel size, their share of the
  * first fragment): what a host loop of one d3f_neighbor_grid_build per target and one d3f_neighbor_grid_score(V = 1, identity) per

@@ -12,7 +12,12 @@ registration.EVALUATE_3DMATCH (evaluate.py:93-99) and writes, under --out:
 and prints the recall line of evaluate.py:200-219.  Without --gt no pair has a ground truth (gt_flag 0 everywhere, as evaluate.py:
 60-65 treats a pair that gt.log does not list) and every pair goes into the .log.
 
+--counts 250,500,1000,2500,5000 runs the sweep of evaluate.py:46 instead (ascending counts, up to 8192): ONE
+registration.register_pairs_counts call for all pairs at all counts, the same files per count under --out/num_keypts_<k>/ and one
+recall line per count (with its num_keypts).
+
     python tools/register_scene.py --root RESULTS --scene sun3d-hotel_umd-maryland_hotel3 --gt gt.log --out OUT
+    python tools/register_scene.py --root RESULTS --scene sun3d-hotel_umd-maryland_hotel3 --gt gt.log --out OUT --counts 250,500,1000,2500,5000
 """
 import argparse
 import json
@@ -49,6 +54,7 @@ def main():
     ap.add_argument("--scene", required=True)
     ap.add_argument("--gt", default=None, help="the scene's gt.log (geometric_registration/gt_result/<scene>-evaluation/gt.log)")
     ap.add_argument("--num-keypts", type=int, default=250)
+    ap.add_argument("--counts", default=None, help="comma-separated ascending keypoint counts: all of them in one call, files per count")
     ap.add_argument("--desc-name", default="D3Feat")
     ap.add_argument("--inlier-ratio", type=float, default=0.05)
     ap.add_argument("--distance-threshold", type=float, default=0.10)
@@ -56,8 +62,10 @@ def main():
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    blocks = load_scene(a.root, a.scene, a.desc_name, a.num_keypts)
-    kp, count = reg.stack_keypoints(blocks, a.num_keypts, device=dev)
+    counts = [int(k) for k in a.counts.split(",")] if a.counts else None
+    rows_kept = max(counts) if counts else a.num_keypts
+    blocks = load_scene(a.root, a.scene, a.desc_name, rows_kept)
+    kp, count = reg.stack_keypoints(blocks, rows_kept, device=dev)
     pairs = reg.scene_pairs(len(blocks), device=dev)
     host_pairs = [tuple(p) for p in pairs.cpu().tolist()]
     gt_log = results.read_gt_log(a.gt) if a.gt else {}
@@ -66,20 +74,31 @@ def main():
     for i, p in enumerate(host_pairs):
         if flag[i]:
             gt[i] = gt_log["%d_%d" % p][:3]
-    res = reg.register_pairs(kp, count, pairs, num_keypts=a.num_keypts, seed=a.seed, gt=torch.from_numpy(gt.astype(np.float32)).to(dev),
-                             distance_threshold=a.distance_threshold, **reg.EVALUATE_3DMATCH)
-    mutual, inl = res.mutual_count.cpu().numpy(), res.gt_inliers.cpu().numpy()
-    T = np.tile(np.eye(4), (len(host_pairs), 1, 1))
-    T[:, :3] = res.T.cpu().numpy().astype(np.float64)
-    # pairs that gt.log does not list: num_inliers = inlier_ratio = gt_flag = 0 and no .log block (evaluate.py:60-65)
-    num_inliers = np.where(flag == 1, inl, 0)
-    ratio = np.where((flag == 1) & (mutual > 0), inl / np.maximum(mutual, 1), 0.0)
-    os.makedirs(a.out, exist_ok=True)
-    logged = [i for i in range(len(host_pairs)) if flag[i] or not a.gt]
-    results.write_registration_log(os.path.join(a.out, "%s.log" % a.desc_name), [host_pairs[i] for i in logged], [T[i] for i in logged])
-    rows = results.write_pair_results(a.out, host_pairs, num_inliers, ratio, flag)
-    rec = results.feature_matching_recall(rows, a.inlier_ratio)
-    print(json.dumps(dict(scene=a.scene, fragments=len(blocks), pairs=len(host_pairs), **rec)))
+    gt = torch.from_numpy(gt.astype(np.float32)).to(dev)
+
+    def write(out_dir, mutual, inl, T34, extra):
+        T = np.tile(np.eye(4), (len(host_pairs), 1, 1))
+        T[:, :3] = T34.astype(np.float64)
+        # pairs that gt.log does not list: num_inliers = inlier_ratio = gt_flag = 0 and no .log block (evaluate.py:60-65)
+        num_inliers = np.where(flag == 1, inl, 0)
+        ratio = np.where((flag == 1) & (mutual > 0), inl / np.maximum(mutual, 1), 0.0)
+        os.makedirs(out_dir, exist_ok=True)
+        logged = [i for i in range(len(host_pairs)) if flag[i] or not a.gt]
+        results.write_registration_log(os.path.join(out_dir, "%s.log" % a.desc_name), [host_pairs[i] for i in logged], [T[i] for i in logged])
+        rows = results.write_pair_results(out_dir, host_pairs, num_inliers, ratio, flag)
+        rec = results.feature_matching_recall(rows, a.inlier_ratio)
+        print(json.dumps(dict(scene=a.scene, fragments=len(blocks), pairs=len(host_pairs), **extra, **rec)))
+
+    if counts is None:
+        res = reg.register_pairs(kp, count, pairs, num_keypts=a.num_keypts, seed=a.seed, gt=gt, distance_threshold=a.distance_threshold,
+                                 **reg.EVALUATE_3DMATCH)
+        write(a.out, res.mutual_count.cpu().numpy(), res.gt_inliers.cpu().numpy(), res.T.cpu().numpy(), {})
+        return
+    res = reg.register_pairs_counts(kp, count, pairs, num_keypts=counts, seed=a.seed, gt=gt, distance_threshold=a.distance_threshold,
+                                    **reg.EVALUATE_3DMATCH)
+    mutual, inl, T = res.mutual_count.cpu().numpy(), res.gt_inliers.cpu().numpy(), res.T.cpu().numpy()
+    for c, k in enumerate(counts):
+        write(os.path.join(a.out, "num_keypts_%d" % k), mutual[:, c], inl[:, c], T[:, c], {"num_keypts": k})
 
 
 if __name__ == "__main__":
