@@ -20,6 +20,8 @@ TOPK_MAX = 8192
 PAIRS_KMAX = 1024
 REPEAT_COUNTS_MAX = 16
 MATCH_KMAX = 8192
+VALIDATION_NMAX = 1024
+VP_INDEX_RANGE, VP_COUNT_RANGE = 1, 2           # status of a pair of d3f_validation_pairs
 
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
 
@@ -89,6 +91,9 @@ SIGNATURES = {
     "d3f_register_pairs_counts": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _f, _i, _f, _f, _i, _i, C.c_uint64, _vp, _f] + [_vp] * 10
                                   + [_sz, _vp]),
     "d3f_overlap_pairs": (_i, [_vp, _sz, _i, _i, _vp, _i, _f, _vp, _vp, _i, _vp]),
+    "d3f_validation_pairs_workspace_bytes": (_sz, [_i, _i]),
+    "d3f_validation_pairs": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _f, _f, _f, _f] + [_vp] * 5
+                             + [_sz, _vp]),
     "d3f_gemm_pack_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_pack_f32t": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_f32t": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _sz,

@@ -798,3 +798,8 @@ extern "C" int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int
 // RANSAC registration of every pair at every keypoint count in one call (d3f_register_pairs_counts)
 // ---------------------------------------------------------------------------------------------------------------------
 #include "rp_register_counts.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Validation figures of every pair in three launches (d3f_validation_pairs)
+// ---------------------------------------------------------------------------------------------------------------------
+#include "rp_validation.h"

@@ -78,7 +78,9 @@ class FragmentEngine:
         every row's arithmetic is unchanged); reference_order_flat(slot) renumbers the slot's pyramid back for parity checks.
         stage0=False: the submitted clouds are ALREADY at the first subsampling resolution (the reference's scripts subsample
         before the dataset sees a cloud: demo_registration.py:24, datasets/ThreeDMatch.py:349) -- no stage-0 voxelisation, the
-        cloud is stacked with itself as it is; raw_cap is then the voxel capacity n0_cap.
+        cloud is stacked with itself as it is; raw_cap is then the voxel capacity n0_cap.  With two_clouds the stack is the pair
+        [cloud_a; cloud_b] as fed (a validation pair, whose keypoint indices address exactly those rows: datasets/ThreeDMatch.py:
+        222-229), n0_cap bounding the sum of the two.
         keypoints=K: the replay additionally selects, per kept cloud, the K records with the highest detection scores in ascending
         score order (keypoints.topk: what the reference's testers and consumers do on the host, utils/tester.py:208-213 +
         geometric_registration/evaluate.py:45-50) -- one more launch after the record packing, a static f32[F * keep_clouds, K, 36]
@@ -104,8 +106,8 @@ class FragmentEngine:
             raise ValueError("keypoints = %s outside 1..%d" % (keypoints, _lib.TOPK_MAX))
         self.keypoints = int(keypoints) if keypoints is not None else None
         if not self.stage0:
-            if self.mirror or self.two:
-                raise ValueError("stage0=False is implemented for stacked self-pairs only")
+            if self.mirror:
+                raise ValueError("stage0=False is implemented for stacked self-pairs and for pairs of two clouds")
             self.raw_cap = self.n0_cap
         self.F = int(batch)
         self.bf16 = bool(bf16) or bool(bf16_features)
@@ -168,6 +170,11 @@ class FragmentEngine:
         else:
             sub, sub_l = sl.raw, sl.raw_len            # already at first_subsampling_dl: the stack is made of the clouds as fed
             sub.n_hint = self.F * self.n0_hint
+            if self.two:
+                # the stack IS the slot's buffer: its real row count, which stack_self_pair delivers for self-pairs, is the sum of
+                # the fed lengths (plumbing: one reduction over 2 F ints into a static word of the slot)
+                torch.sum(sub_l, 0, keepdim=True, dtype=torch.int32, out=sl.raw_total)
+                sub.n_dev = sl.raw_total
         if self.mirror or self.two:
             pts, lens = sub, sub_l     # the stack as subsampled: lens = [m_1 .. m_F] (mirror) or [m_a1, m_b1, ...] (two clouds)
         else:
@@ -217,6 +224,7 @@ class FragmentEngine:
         sl.host_dst = sl.meta_host[2 * self.nin: nw].view(torch.int64)
         sl.host_n = sl.meta_host[nw:]
         sl.status0 = torch.zeros((2,), dtype=torch.int32, device=dev)
+        sl.raw_total = torch.zeros((1,), dtype=torch.int32, device=dev)
         if self.keypoints:
             sl.kp = torch.zeros((self.F * self.keep_clouds, self.keypoints, 36), dtype=torch.float32, device=dev)
             sl.kp_count = torch.zeros((self.F * self.keep_clouds,), dtype=torch.int32, device=dev)
@@ -506,7 +514,9 @@ class FragmentEngine:
         elif isinstance(raw, (tuple, list)):
             raw = tuple(r.decode(self.device) if isinstance(r, ops.RawRecords) else r for r in raw)
         if self.two:
-            subs = [tfo.grid_subsampling(p if p.is_cuda else p.to(self.device), self.cfg.first_subsampling_dl) for p in raw]
+            subs = [p if p.is_cuda else p.to(self.device) for p in raw]
+            if self.stage0:
+                subs = [tfo.grid_subsampling(p, self.cfg.first_subsampling_dl) for p in subs]
             pts = torch.cat(subs, 0)
             lens = ops.as_lens([int(x.shape[0]) for x in subs], self.device)
         else:

@@ -46,6 +46,7 @@ extern "C" {
 #define D3F_PAIRS_KMAX 1024      /* most rows of one keypoint block d3f_register_pairs uses */
 #define D3F_REPEAT_COUNTS_MAX 16 /* most keypoint counts one d3f_repeatability_pairs / d3f_match_pairs call evaluates */
 #define D3F_MATCH_KMAX 8192      /* largest keypoint count of d3f_match_pairs (= D3F_TOPK_MAX, the largest block the selection makes) */
+#define D3F_VALIDATION_NMAX 1024 /* most index pairs (keypoint correspondences) of one pair d3f_validation_pairs takes */
 #define D3F_NUM_KP_MAX 16        /* kernel points per KPConv (reference uses 15) */
 
 int d3f_version(void);
@@ -654,6 +655,45 @@ int d3f_register_pairs_counts(const float* kp, int n_blocks, int K, int ld, int 
  * P == 0 is D3F_OK without a launch.  Asynchronous on `stream`, no workspace, no allocation, no synchronisation. */
 int d3f_overlap_pairs(const void* grid, size_t grid_bytes, int N, int B, const int* pairs_dev, int P, float threshold,
                       int* count_dev, int* nearest_dev, int ld_nearest, void* stream);
+
+/* Validation figures of P pairs in three launches, whatever P is (models/KPFCNN_model.py:131-186 with utils/loss.py of the reference:
+ * what its model class evaluates per validation pair, and utils/trainer.py:442-452, 467-471: the means over a split).  Forward only.
+ * Pair p is the stack [anchor; positive] held by rows row0_dev[p] .. row0_dev[p + 1] of three row arrays, each a base pointer and a
+ * leading dimension in floats, so that column views of one block of [xyz | descriptor | score] records need no copy:
+ *   desc f32[n_rows, ldd] (C = 16 / 32 / 64 columns read), score f32[n_rows, lds] (one column), points f32[n_rows, ldp] (three).
+ *   row0_dev i32[P + 1], anc_dev / pos_dev i32[P, ld_idx]: n_dev[p] index pairs (ai, pi) into the pair's rows, the positive's already
+ *   shifted by the anchor's length as the reference feeds them; repeated indices are allowed.  All read on the device.
+ * With m = neg_margin, q = pos_margin, L = log_scale, r = safe_radius, n = n_dev[p], in fp32:
+ *   D[i,j]  = sqrt(sum_c (f[ai[i],c] - f[pi[j],c])^2 + 1e-12), the sum an fmaf chain over ascending c of the differences (loss.cdist;
+ *             one arithmetic for every entry: equal index pairs give equal bits);
+ *   KD[i,j] = sqrt(((dx dx + dy dy) + dz dz) + 1e-12) between the points of ai[i] and ai[j], never contracted (KPFCNN_model.py:131-132);
+ *   FN[i,j] = KD[i,j] < r and i != j;   fp_i = D[i,i];   cn_i = min_j (D[i,j] + 1e5 [i == j]) (FN not applied: loss.py:151);
+ *   z[i,j]  = 0 if (i == j or FN[i,j] or D[i,j] >= m) else (L (m - D[i,j])) (m - D[i,j]);   lse_i = log sum_j exp z[i,j] -- a masked
+ *             entry contributes exp(0), as the reference's 1e8 terms make it.
+ * values f32[P, 8]: [0] circle = mean_i softplus(L (fp_i - q) + lse_i) / L (softplus with the shortcuts of d3f_detect_head),
+ *   [1] contrastive = mean_i (max(fp_i - q, 0) + max(m - cn_i, 0)), [2] det = det_loss_weight * mean_i (fp_i - cn_i) ((s[ai[i]] +
+ *   s[pi[i]]) + 1e-6), constant 0 for a zero weight, [3] accuracy = #{i: fp_i - cn_i <= 0} / n, [4] d_pos = mean_i fp_i,
+ *   [5] d_neg = (mean over all n n entries of D [i != j and not FN]) n / (n - 1) -- NaN at n = 1, as the reference --,
+ *   [6] the number of accurate rows, [7] n.  D, KD and the exponentials are fp32; the per-row terms and the means are float64
+ *   in a fixed order and each figure is rounded to fp32 once.
+ * A pair with n == 0 or 2 n < keypts_num (KPFCNN_model.py:172-186) gets (0, 0, 0, -1, 0, 0 | 0, n).  So does one with n outside
+ * 0 .. min(ld_idx, D3F_VALIDATION_NMAX) (status_dev[p] = 2) or with an index outside its rows, or offsets outside 0 .. n_rows
+ * (status_dev[p] = 1): nothing is read through such an index.  status_dev[p] = 0 otherwise.
+ * sums_dev f64[6] / counts_dev i64[6]: per figure [0..5] the sum over the pairs where it is != 0 (accuracy: > 0) and their number --
+ * the lists the trainer averages.
+ * No memset, no atomics, no read-back, fixed summation orders (two calls give equal bits): capturable.
+ * workspace >= d3f_validation_pairs_workspace_bytes(P, ld_idx): 32 bytes per pair and index of min(ld_idx, D3F_VALIDATION_NMAX)
+ * rounded up to 64, else D3F_ERR_WORKSPACE; the function returns 0 for sizes the call refuses.
+ * D3F_ERR_ARG before anything touches the device: P < 0, C not 16 / 32 / 64, ldd < C, lds < 1, ldp < 3, n_rows < 0, ld_idx < 1,
+ * keypts_num < 0, a NaN parameter, neg_margin or log_scale not positive, log_scale * neg_margin^2 > 80 (exp would leave fp32 without
+ * a running maximum), a NULL pointer (with P == 0 only sums_dev and counts_dev are needed: they are zeroed by one launch).
+ * Asynchronous on `stream`, no allocation, no synchronisation. */
+size_t d3f_validation_pairs_workspace_bytes(int P, int ld_idx);
+int d3f_validation_pairs(const float* desc, int ldd, int C, const float* score, int lds, const float* points, int ldp, int n_rows,
+                         const int* row0_dev, const int* anc_dev, const int* pos_dev, int ld_idx, const int* n_dev, int P,
+                         float safe_radius, int keypts_num, float det_loss_weight, float pos_margin, float neg_margin,
+                         float log_scale, float* values, int* status_dev, double* sums_dev, int64_t* counts_dev, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
