@@ -65,7 +65,8 @@ __global__ void __launch_bounds__(256) rg_unpack_kernel(const unsigned long long
 
 extern "C" size_t d3f_feature_nn_workspace_bytes(int Na) { return d3f_align((size_t)(Na > 0 ? Na : 1) * 8) + 256; }
 
-// idx[i] = argmin_j ||A_i - B_j||^2 (lowest j on ties; -1 when Nb == 0), d2_out[i] (optional) the minimum.  C in {16, 32, 64}.
+// idx[i] = argmin_j ||A_i - B_j||^2 (lowest j on ties), d2_out[i] (optional) the minimum.  C in {16, 32, 64}.  A row without a
+// distance below FLT_MAX (Nb == 0, a NaN row, every d2 overflowing) posts no key: idx -1, d2 FLT_MAX; a NaN column is never chosen.
 extern "C" int d3f_feature_nn(const float* A, int Na, int lda, const float* B, int Nb, int ldb, int C, int* idx, float* d2_out,
                               void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
@@ -119,13 +120,13 @@ extern "C" size_t d3f_mutual_matches_workspace_bytes(int Na) {
     return d3f_align((size_t)(Na > 0 ? Na : 1) * 4) + d3f_align(d3f_scan_base_ints(Na) * 4) + 512;
 }
 
-// pairs i32[<= Na, 2], count_dev i32[1] (device).  ab i32[Na] (A -> B nearest), ba i32[Nb] (B -> A nearest).
+// pairs i32[<= Na, 2], count_dev i32[1] (device).  ab i32[Na] (A -> B nearest), ba i32[Nb] (B -> A nearest; may be NULL when Nb == 0).
 extern "C" int d3f_mutual_matches(const int* ab, int Na, const int* ba, int Nb, int* pairs, int* count_dev, void* workspace,
                                   size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (Na < 0 || Nb < 0 || !count_dev) return D3F_ERR_ARG;
     if (Na == 0) return d3f_fill_u32(count_dev, 1, 0u, stream);
-    if (!ab || !ba || !pairs) return D3F_ERR_ARG;
+    if (!ab || (Nb > 0 && !ba) || !pairs) return D3F_ERR_ARG;   // Nb == 0: ba is never read (RgMutualIn tests j < Nb first)
     D3fArena ar(workspace, workspace_bytes);
     int* local = ar.take<int>(Na);
     int* base = ar.take<int>(d3f_scan_base_ints(Na));

@@ -479,7 +479,10 @@ int d3f_decode_xyz_records(const void* raw, int n, int stride, int off_x, int of
  * Downstream matching -- what the reference does with the descriptors after the hot path.
  * ============================================================================================= */
 
-/* Nearest descriptor: idx[i] = argmin_j ||A_i - B_j||^2 (lowest j on ties, -1 when Nb == 0); d2_out (optional) the minimum.
+/* Nearest descriptor: idx[i] = argmin_j ||A_i - B_j||^2 (lowest j on ties); d2_out (optional) the minimum.
+ * No match: a row i without ANY distance below FLT_MAX in the fp32 chain (d = a[c] - b[c]; d2 = fmaf(d, d, d2), c ascending) --
+ * Nb == 0, a NaN in A_i, every d2 overflowing -- gets idx[i] = -1 and d2_out[i] = FLT_MAX; a row of B whose distance is NaN or
+ * not below FLT_MAX is never the answer.  -1 is what d3f_mutual_matches and d3f_ransac_hypotheses read as "no match".
  * Replaces the argmin over the dense distance matrix of geometric_registration/evaluate.py:17-21 (one direction per call)
  * and the KD-tree feature lookup inside open3d.registration_ransac_based_on_feature_matching (evaluate.py:93-99).
  * A f32[Na,C] (lda), B f32[Nb,C] (ldb), C in {16, 32, 64}. */
@@ -488,7 +491,8 @@ int d3f_feature_nn(const float* A, int Na, int lda, const float* B, int Nb, int 
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* Mutually closest pairs (evaluate.py:21-26 build_correspondence): pairs (i, ab[i]) with ba[ab[i]] == i, ascending i.
- * pairs i32[<= Na, 2]; count_dev i32[1] on the device. */
+ * pairs i32[<= Na, 2]; count_dev i32[1] on the device.  Entries of ab outside [0, Nb) (the -1 of d3f_feature_nn) match nothing;
+ * ba may be NULL when Nb == 0.  Rows of pairs from the count on are not written. */
 size_t d3f_mutual_matches_workspace_bytes(int Na);
 int d3f_mutual_matches(const int* ab, int Na, const int* ba, int Nb, int* pairs, int* count_dev, void* workspace,
                        size_t workspace_bytes, void* stream);

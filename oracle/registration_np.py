@@ -64,23 +64,53 @@ def kabsch(s, t):
     return R, mt - R @ ms
 
 
-def hypothesis(src, tgt, nn, n, edge_sim, dist_thr, seed, it):
+STAGES = ("repeat", "no match", "edge", "distance", "ok")
+
+
+def hypothesis_trace(src, tgt, nn, n, edge_sim, dist_thr, seed, it):
+    """hypothesis() with the stage at which it ended: dict(stage = one of STAGES, si, ti (None before the matches are known), s, t
+    (float64 samples, None for a repeat / no match), edge = the smallest min(ds, dt) / max(ds, dt) over the sample's edges (None with
+    the checker off), R, tr (None unless the fit was reached), dist = the largest aligned distance (None with the checker off)).
+    A draw that repeats is reported before a missing match (nn[i] outside [0, len(tgt))); both end the hypothesis before any
+    point is read."""
     si = [draw(seed, it, d, len(src)) for d in range(n)]
+    out = dict(stage="repeat", si=si, ti=None, s=None, t=None, edge=None, R=None, tr=None, dist=None)
     if len(set(si)) < n:
-        return None
+        return out
     ti = [int(nn[i]) for i in si]
+    out["ti"] = ti
+    if any(j < 0 or j >= len(tgt) for j in ti):
+        out["stage"] = "no match"
+        return out
     s, t = src[si].astype(np.float64), tgt[ti].astype(np.float64)
+    out["s"], out["t"] = s, t
     if edge_sim and edge_sim > 0:
+        failed, ratio = False, 1.0
         for a in range(n):
             for b in range(a + 1, n):
                 ds, dt = np.linalg.norm(s[a] - s[b]), np.linalg.norm(t[a] - t[b])
                 if ds < dt * edge_sim or dt < ds * edge_sim:
-                    return None
+                    failed = True
+                if max(ds, dt) > 0:
+                    ratio = min(ratio, min(ds, dt) / max(ds, dt))
+        out["edge"] = ratio
+        if failed:
+            out["stage"] = "edge"
+            return out
     R, tr = kabsch(s, t)
+    out["R"], out["tr"] = R, tr
+    out["stage"] = "ok"
     if dist_thr and dist_thr > 0:
-        if (np.linalg.norm(s @ R.T + tr - t, axis=1) > dist_thr).any():
-            return None
-    return R, tr
+        d = np.linalg.norm(s @ R.T + tr - t, axis=1)
+        out["dist"] = float(d.max())
+        if (d > dist_thr).any():
+            out["stage"] = "distance"
+    return out
+
+
+def hypothesis(src, tgt, nn, n, edge_sim, dist_thr, seed, it):
+    h = hypothesis_trace(src, tgt, nn, n, edge_sim, dist_thr, seed, it)
+    return (h["R"], h["tr"]) if h["stage"] == "ok" else None
 
 
 def evaluate(src, tgt, R, tr, radius):

@@ -101,6 +101,22 @@ def test_host_side_argument_checks_need_no_gpu(lib):
     assert lib.d3f_kpconv_fused32(*args(1 << 24, 100, 8, 32)) == -3
 
 
+def test_registration_entry_points_refuse_bad_arguments_without_a_gpu(lib):
+    """d3f_feature_nn, d3f_ransac_hypotheses, d3f_neighbor_grid_score and d3f_mutual_matches check their arguments on the host before
+    anything touches the device."""
+    buf = ctypes.create_string_buffer(4096)
+    p = ctypes.addressof(buf)
+    assert lib.d3f_feature_nn(p, 4, 48, p, 4, 48, 48, p, None, p, 4096, None) == -3            # C = 48
+    assert lib.d3f_feature_nn(p, 4, 31, p, 4, 32, 32, p, None, p, 4096, None) == -3            # lda < C
+    assert lib.d3f_feature_nn(p, 4, 32, p, 4, 31, 32, p, None, p, 4096, None) == -3            # ldb < C
+    for n in (2, 9):
+        assert lib.d3f_ransac_hypotheses(p, 10, p, 10, p, n, 0.9, 0.05, 1, 0, 8, p, p, None) == -3
+    assert lib.d3f_ransac_hypotheses(p, 0, p, 10, p, 4, 0.9, 0.05, 1, 0, 8, p, p, None) == -3  # Ns = 0
+    assert lib.d3f_neighbor_grid_score(p, 4096, 10, p, 10, p, 1, float("nan"), p, p, None, None) == -3
+    assert lib.d3f_neighbor_grid_score(p, 4096, 10, p, 10, p, -1, 0.05, p, p, None, None) == -3
+    assert lib.d3f_mutual_matches(p, 10, p, 10, p, None, p, 4096, None) == -3                  # count_dev == NULL
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from d3feat_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
