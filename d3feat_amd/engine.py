@@ -71,7 +71,7 @@ class FragmentEngine:
         BASELINE configs[4]) -- NOT the parity path: results differ from fp32 by the operand rounding.
         bf16_features=True (implies bf16): the activations between the layers are additionally STORED as bfloat16 -- "bf16
         features with MFMA contraction"; arithmetic inside every kernel stays fp32.
-        internal_order (default: on; D3F_INTERNAL_ORDER=0 switches it off): inside a replay every level is kept in the cell order of
+        internal_order (default: on, off for an architecture with a deformable block; D3F_INTERNAL_ORDER=0 switches it off): inside a replay every level is kept in the cell order of
         its own neighbour grid -- index matrices, point arrays and activations (datasets/common.py: _descriptor_input_internal) --
         so that the rows a workgroup gathers are neighbours in memory too; the last kernel of the sequence writes the records
         back in the reference's row order.  Results are those of the reference numbering (bit for bit in this implementation:
@@ -99,7 +99,10 @@ class FragmentEngine:
         self.two = bool(two_clouds)
         if internal_order is None:
             import os
-            internal_order = os.environ.get("D3F_INTERNAL_ORDER", "1") != "0"
+            # the internal numbering has no deformable form (datasets/common.py: _descriptor_input_internal raises): an architecture
+            # with a deformable block runs in the reference numbering, whose pyramid already widens that level's search radius
+            internal_order = os.environ.get("D3F_INTERNAL_ORDER", "1") != "0" and \
+                not any("deformable" in b for b in config.architecture)
         self.internal = bool(internal_order)
         self.stage0 = bool(stage0)
         if keypoints is not None and not 1 <= int(keypoints) <= _lib.TOPK_MAX:
@@ -138,6 +141,10 @@ class FragmentEngine:
         # one HIP stream per slot (pass `streams` to share them between engines: the runtime multiplexes every stream of the
         # process onto a few hardware queues, so idle extra streams still cost concurrency)
         self.neighbor_cap = 192            # hits a query can order in LDS on the fast path (sticky upgrade, see fetch)
+        if any("deformable" in b for b in config.architecture):
+            # a layer with a deformable block searches density_parameter / 2.5 times the rigid radius (datasets/common.py:204-216):
+            # up to eight times the supports per query at the shipped settings -- the full ordering budget from the first capture
+            self.neighbor_cap = self._eager_ds._neighbor_cap = _lib.NEIGHBOR_CAP
         self.slots = [self._build_slot(streams[i] if streams else None) for i in range(int(slots))]
         self.fallbacks = 0             # fragments that took the eager path
         self.isolated = 0              # flagged multi-fragment replays that were split into single-fragment replays

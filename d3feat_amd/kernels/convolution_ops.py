@@ -1,17 +1,23 @@
 """KPConv operators, same names / argument order as the reference's kernels/convolution_ops.py, running as two
-HIP kernels on the MI355X: the fused gather + kernel-point-influence + aggregation (csrc/kpconv.hip) and the
-(num_kp*Cin) x Cout contraction on the matrix cores (csrc/gemm_f32.hip).
+HIP kernels on the MI355X: the fused gather + kernel-point-influence + aggregation (csrc/kpconv.hip, csrc/kpconv_deform.hip) and
+the (num_kp*Cin) x Cout contraction on the matrix cores (csrc/gemm_f32.hip).
 
     unary_convolution(features, K_values)                                       convolution_ops.py:90-99
     KPConv(query_points, support_points, neighbors_indices, features, K_values,
            fixed='center', KP_extent=1.0, KP_influence='linear', aggregation_mode='sum')     :102-158
     KPConv_ops(query_points, support_points, neighbors_indices, features, K_points, K_values,
                KP_extent, KP_influence, aggregation_mode)                                     :161-255
+    KPConv_deformable(query_points, support_points, neighbors_indices, features, K_values,
+                      fixed='center', KP_extent=1.0, KP_influence='linear', aggregation_mode='sum', modulated=False)    :258-376
+    KPConv_deform_ops(query_points, support_points, neighbors_indices, features, K_points, offsets, modulations, K_values,
+                      KP_extent, KP_influence, mode)                                          :379-499
 
 Extra keyword (not in the reference, defaults keep its behaviour): `epilogue`, a dict of
 {col_scale, col_shift, residual, leaky, alpha} fused into the contraction's epilogue -- the inference
 batch-norm / LeakyReLU / shortcut-add that always follow a KPConv in models/network_blocks.py.
-The deformable variants (:258-627) are not part of any shipped architecture and are not provided.
+In the reference KPConv_deformable CREATES its `offset_conv_weights` / `offset_conv_bias` variables (zeros); here they are passed
+in (`offset_weights`, `offset_bias`; default: zeros, the reference's initial values).  The development variant KPConv_deformable_v2
+(:507-627) is not provided.
 """
 import numpy as np
 import torch
@@ -75,3 +81,44 @@ def KPConv_ops(query_points, support_points, neighbors_indices, features, K_poin
     wf, inv_cnt = ops.kpconv_aggregate(query_points, support_points, neighbors_indices, features, K_points, KP_extent,
                                        KP_influence, aggregation_mode)
     return ops.gemm(wf, K_values.reshape(num_kp * cin, cout), row_scale=inv_cnt, **(epilogue or {}))
+
+
+def KPConv_deformable(query_points, support_points, neighbors_indices, features, K_values, fixed='center', KP_extent=1.0,
+                      KP_influence='linear', aggregation_mode='sum', modulated=False, K_points=None, offset_weights=None,
+                      offset_bias=None, epilogue=None):
+    """convolution_ops.py:258-376: a rigid KPConv_ops with its own weights [num_kp, Cin, 3 num_kp (4 num_kp: modulated)] and a bias
+    gives every query its kernel-point offsets (x KP_extent) and modulations (2 sigmoid); then KPConv_deform_ops."""
+    if KP_influence not in ('constant', 'linear', 'gaussian'):
+        raise ValueError('Unknown influence function type (config.KP_influence)')
+    if aggregation_mode not in ('closest', 'sum'):
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    K_radius = 1.5 * KP_extent
+    num_kpoints, cin = int(K_values.shape[0]), int(K_values.shape[1])
+    points_dim = int(query_points.shape[1])
+    if K_points is None:
+        K_points = create_kernel_points(K_radius, num_kpoints, num_kernels=1, dimension=points_dim, fixed=fixed)
+        K_points = K_points.reshape((num_kpoints, points_dim)).astype(np.float32)
+    offset_dim = (points_dim + 1 if modulated else points_dim) * num_kpoints
+    if offset_weights is None:
+        offset_weights = torch.zeros((num_kpoints, cin, offset_dim), dtype=torch.float32, device=features.device)
+    if offset_bias is None:
+        offset_bias = torch.zeros((offset_dim,), dtype=torch.float32, device=features.device)
+    return ops.kpconv_deformable(query_points, support_points, neighbors_indices, features, K_points, K_values, offset_weights,
+                                 offset_bias, KP_extent, KP_influence, aggregation_mode, modulated, **(epilogue or {}))
+
+
+def KPConv_deform_ops(query_points, support_points, neighbors_indices, features, K_points, offsets, modulations, K_values, KP_extent,
+                      KP_influence, mode, epilogue=None):
+    """convolution_ops.py:379-499.  offsets [n, num_kp, 3] (already in the units of the points); modulations [n, num_kp] or None.
+    Against KPConv_ops: a neighbour counts only if it is within KP_extent of a deformed kernel point, the linear influence divides
+    by KP_extent (not 2 KP_extent), 'constant' is that same range test per kernel point, and nothing is normalised."""
+    if KP_influence not in ('constant', 'linear', 'gaussian'):
+        raise ValueError('Unknown influence function type (config.KP_influence)')
+    if mode not in ('closest', 'sum'):
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    num_kp, cin, cout = K_values.shape
+    if features.shape[1] != cin:
+        raise ValueError('KPConv_deformable: features have %d channels, K_values expects %d' % (features.shape[1], cin))
+    wf = ops.kpconv_deform_aggregate(query_points, support_points, neighbors_indices, features, K_points, offsets, KP_extent,
+                                     KP_influence, mode, modulations=modulations)
+    return ops.gemm(wf, K_values.reshape(num_kp * cin, cout), **(epilogue or {}))

@@ -106,6 +106,22 @@ def KPConv(query_points, support_points, neighbors_indices, features, K_values, 
                            epilogue=epilogue)
 
 
+def KPConv_deformable(query_points, support_points, neighbors_indices, features, K_values, radius, config, epilogue=None):
+    """:106-124: as KPConv, with the `offset_conv_weights` / `offset_conv_bias` variables of the current scope (created after
+    `kernel_points`, zeros: kernels/convolution_ops.py:327-328) and config.modulated."""
+    extent = config.KP_extent * radius / config.density_parameter
+    K_points = _kernel_points(config, extent)
+    vs = _vs()
+    k, cin = int(K_values.shape[0]), int(K_values.shape[1])
+    offset_dim = (4 if config.modulated else 3) * k
+    w0 = vs.tensor(vs.get('offset_conv_weights', (k, cin, offset_dim), lambda: np.zeros((k, cin, offset_dim))))
+    b0 = vs.tensor(vs.get('offset_conv_bias', (offset_dim,), lambda: np.zeros(offset_dim)))
+    return conv_ops.KPConv_deformable(query_points, support_points, neighbors_indices, features, K_values,
+                                      fixed=config.fixed_kernel_points, KP_extent=extent, KP_influence=config.KP_influence,
+                                      aggregation_mode=config.convolution_mode, modulated=config.modulated, K_points=K_points,
+                                      offset_weights=w0, offset_bias=b0, epilogue=epilogue)
+
+
 def _check_inference(training):
     if training:
         raise NotImplementedError('d3feat_amd implements the inference path only (training=False)')
@@ -148,7 +164,7 @@ def simple_block(layer_ind, inputs, features, radius, fdim, config, training):
                   radius, config, epilogue=_epilogue(fdim, config, True))
 
 
-def _resnetb(layer_ind, inputs, features, radius, fdim, config, strided):
+def _resnetb(layer_ind, inputs, features, radius, fdim, config, strided, deformable=False):
     cin = int(features.shape[1])
     with variable_scope('conv1'):
         w = weight_variable([cin, fdim // 2])
@@ -159,7 +175,7 @@ def _resnetb(layer_ind, inputs, features, radius, fdim, config, strided):
             q, s, nb = inputs['points'][layer_ind + 1], inputs['points'][layer_ind], inputs['pools'][layer_ind]
         else:
             q, s, nb = inputs['points'][layer_ind], inputs['points'][layer_ind], inputs['neighbors'][layer_ind]
-        x = KPConv(q, s, nb, x, w, radius, config, epilogue=_epilogue(fdim // 2, config, True))
+        x = (KPConv_deformable if deformable else KPConv)(q, s, nb, x, w, radius, config, epilogue=_epilogue(fdim // 2, config, True))
     # variables are created in the reference's order (conv3 before shortcut, :342-356 / :585-600) so that lazily created
     # random weights equal build_variables(seed)'s; the compute order below is free
     with variable_scope('conv3'):
@@ -202,6 +218,18 @@ def resnetb_strided_block(layer_ind, inputs, features, radius, fdim, config, tra
     return _resnetb(layer_ind, inputs, features, radius, fdim, config, True)
 
 
+def resnetb_deformable_block(layer_ind, inputs, features, radius, fdim, config, training):
+    """:424-471: resnetb with a deformable KPConv as conv2."""
+    _check_inference(training)
+    return _resnetb(layer_ind, inputs, features, radius, fdim, config, False, deformable=True)
+
+
+def resnetb_deformable_strided_block(layer_ind, inputs, features, radius, fdim, config, training):
+    """:672-723: resnetb_strided with a deformable KPConv as conv2."""
+    _check_inference(training)
+    return _resnetb(layer_ind, inputs, features, radius, fdim, config, True, deformable=True)
+
+
 def nearest_upsample_block(layer_ind, inputs, features, radius, fdim, config, training):
     """:971-979."""
     with variable_scope('nearest_upsample'):
@@ -220,13 +248,15 @@ def _materialized(block_fn):
 
 
 def get_block_ops(block_name):
-    """:982-1042 for the block types of the shipped architectures (results/*/parameters.txt:19)."""
+    """:982-1042 for the block types of the shipped architectures (results/*/parameters.txt:19) and the deformable resnet
+    bottlenecks of the KPConv backbone."""
     table = {'unary': unary_block, 'last_unary': last_unary_block, 'simple': simple_block, 'resnetb': resnetb_block,
-             'resnetb_strided': resnetb_strided_block, 'nearest_upsample': nearest_upsample_block}
+             'resnetb_strided': resnetb_strided_block, 'resnetb_deformable': resnetb_deformable_block,
+             'resnetb_deformable_strided': resnetb_deformable_strided_block, 'nearest_upsample': nearest_upsample_block}
     if block_name in table:
         return table[block_name] if block_name == 'unary' else _materialized(table[block_name])
-    known_unsupported = ('simple_strided', 'resnet', 'resnetb_light', 'resnetb_deformable', 'inception_deformable',
-                         'resnetb_light_strided', 'resnetb_deformable_strided', 'inception_deformable_strided', 'vgg',
+    known_unsupported = ('simple_strided', 'resnet', 'resnetb_light', 'inception_deformable',
+                         'resnetb_light_strided', 'inception_deformable_strided', 'vgg',
                          'max_pool', 'max_pool_wide', 'global_average', 'simple_upsample', 'resnetb_upsample')
     if block_name in known_unsupported:
         raise NotImplementedError('block "%s" is not used by any released D3Feat model and is not implemented'

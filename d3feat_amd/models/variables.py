@@ -169,13 +169,18 @@ class VariableStore:
         self._recipes = {}
 
 
-def build_variables(config, seed=42, in_features_dim=None, randomize_bn=False, device=None):
+def build_variables(config, seed=42, in_features_dim=None, randomize_bn=False, device=None, randomize_offsets=False):
     """Create every variable of the network on the host without running it: a shape-only walk of
     models/network_blocks.py:1052-1118 (encoder) and models/D3Feat.py:19-63 (decoder).  The result has exactly the
     variable names / shapes of the reference's checkpoints (tests/test_host_logic.py checks
     it against the table decoded from results/Log_contraloss/snapshots/snap-54.index).
 
-    randomize_bn: draw non-trivial batch-norm statistics (for parity tests; identity statistics hide bugs)."""
+    randomize_bn: draw non-trivial batch-norm statistics (for parity tests; identity statistics hide bugs).
+    randomize_offsets: draw non-zero `offset_conv_weights` / `offset_conv_bias` for the deformable blocks (for parity tests: the
+    reference's zero initialisers make a deformable block a rigid one with another influence radius).  The offset
+    convolution's output is in units of KP_extent: it contracts num_kp * Cin neighbourhood averages of order-1 activations, so
+    weights N(0, 0.25 / sqrt(num_kp * Cin)) and a bias N(0, 0.05) move a kernel point by a few tenths of KP_extent at the
+    coarse levels, where the activations are largest."""
     from ..kernels.kernel_points import create_kernel_points
     vs = VariableStore(seed=seed, device=device)
     K = config.num_kernel_points
@@ -195,6 +200,15 @@ def build_variables(config, seed=42, in_features_dim=None, randomize_bn=False, d
         vs.get('kernel_points', (K, 3), lambda: create_kernel_points(1.5 * extent, K, 1, 3, config.fixed_kernel_points,
                                                                      rng=vs.rng).reshape(K, 3))
 
+    def offset_conv(ci):
+        # kernels/convolution_ops.py:321-328: created after `kernel_points`, zeros
+        D = (4 if config.modulated else 3) * K
+        w = vs.get('offset_conv_weights', (K, ci, D), lambda: np.zeros((K, ci, D)))
+        b = vs.get('offset_conv_bias', (D,), lambda: np.zeros(D))
+        if randomize_offsets:
+            vs.values[w] = (vs.rng.standard_normal((K, ci, D)) * (0.25 / np.sqrt(K * ci))).astype(np.float32)
+            vs.values[b] = (0.05 * vs.rng.standard_normal(D)).astype(np.float32)
+
     layer, fdim, F, bil = 0, config.first_features_dim, [], 0
     start_i = len(config.architecture)
     for block_i, block in enumerate(config.architecture):
@@ -208,11 +222,14 @@ def build_variables(config, seed=42, in_features_dim=None, randomize_bn=False, d
                 kpconv(cin, fdim, layer)
                 bn(fdim)
                 cin = fdim
-            elif block in ('resnetb', 'resnetb_strided'):
+            elif block in ('resnetb', 'resnetb_strided', 'resnetb_deformable', 'resnetb_deformable_strided'):
                 with vs.variable_scope('conv1'):
                     vs.weight_variable([cin, fdim // 2]); bn(fdim // 2)
                 with vs.variable_scope('conv2'):
-                    kpconv(fdim // 2, fdim // 2, layer); bn(fdim // 2)
+                    kpconv(fdim // 2, fdim // 2, layer)
+                    if 'deformable' in block:
+                        offset_conv(fdim // 2)
+                    bn(fdim // 2)
                 with vs.variable_scope('conv3'):
                     vs.weight_variable([fdim // 2, 2 * fdim]); bn(2 * fdim)
                 if cin != 2 * fdim:

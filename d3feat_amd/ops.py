@@ -856,6 +856,75 @@ def kpconv_aggregate(query_points, support_points, neighbors_indices, features, 
     return _tag(wf, query_points), _tag(inv_cnt, query_points)
 
 
+def kpconv_deform_aggregate(query_points, support_points, neighbors_indices, features, K_points, offsets, KP_extent,
+                            KP_influence="linear", aggregation_mode="sum", modulations=None, raw=False):
+    """Phase 1 of KPConv_deform_ops (kernels/convolution_ops.py:379-490) -> wf f32[Nq, num_kp*Cin], modulations applied.
+    raw=False: the operator's own arguments -- offsets f32[Nq, num_kp, 3] (or [Nq, 3*num_kp]) in the units of the points,
+    modulations f32[Nq, num_kp] or None.
+    raw=True: offsets f32[Nq, 3*num_kp] or [Nq, 4*num_kp] is the RAW output of the offset convolution (:331-339) -- the kernel scales
+    the first 3*num_kp columns by KP_extent and turns the remaining num_kp, if any, into 2*sigmoid modulations (:344-359)."""
+    lib = _lib.load()
+    if neighbors_indices.shape[0] != query_points.shape[0] or features.shape[0] != support_points.shape[0]:
+        raise ValueError("KPConv_deformable: %d queries / %d index rows, %d supports / %d feature rows" %
+                         (query_points.shape[0], neighbors_indices.shape[0], support_points.shape[0], features.shape[0]))
+    if isinstance(features, torch.Tensor) and features.dtype == torch.bfloat16:
+        raise TypeError("KPConv_deformable reads float32 feature rows only: d3f_kpconv_deform_aggregate has no bfloat16 "
+                        "feature-storage form")
+    gather, kpar, _, _, tail, f = _kp_front("KPConv_deformable", query_points, support_points, neighbors_indices, features, K_points,
+                                            None, KP_extent, KP_influence, aggregation_mode, row_pos=False,
+                                            feat=lambda t, name: _req(t, torch.float32, name))
+    Nq, Ns, K, Cin, num_kp = gather[1], gather[3], gather[6], f.shape[1], kpar[1]
+    _req(offsets, torch.float32, "offsets")
+    if offsets.dim() == 3:
+        offsets = offsets.reshape(offsets.shape[0], -1)
+    off, ld_off = _rows(offsets, "offsets")
+    mod, ld_mod = None, 0
+    if raw:
+        if modulations is not None or tuple(off.shape) not in ((Nq, 3 * num_kp), (Nq, 4 * num_kp)):
+            raise ValueError("KPConv_deformable: raw offsets are %s, expected (%d, %d) or (%d, %d) and no modulations"
+                             % (tuple(off.shape), Nq, 3 * num_kp, Nq, 4 * num_kp))
+        if off.shape[1] == 4 * num_kp:
+            mod, ld_mod = off[:, 3 * num_kp:], ld_off
+    else:
+        if tuple(off.shape) != (Nq, 3 * num_kp):
+            raise ValueError("KPConv_deformable: offsets are %s, expected (%d, %d, 3)" % (tuple(offsets.shape), Nq, num_kp))
+        if modulations is not None:
+            mod, ld_mod = _rows(_req(modulations, torch.float32, "modulations"), "modulations")
+            if tuple(mod.shape) != (Nq, num_kp):
+                raise ValueError("KPConv_deformable: modulations are %s, expected (%d, %d)" % (tuple(mod.shape), Nq, num_kp))
+    wf = torch.empty((Nq, num_kp * Cin), dtype=torch.float32, device=f.device)
+    with _timed("kpconv_deform_aggregate", dict(Nq=Nq, Ns=Ns, K=K, Cin=Cin), f.device):
+        rc = lib.d3f_kpconv_deform_aggregate(*map(_arg, (*gather, Cin, off, ld_off, float(KP_extent) if raw else 1.0, mod, ld_mod,
+                                                         1 if raw else 0, *kpar, wf, *tail, 0, _stream(f.device))))
+    _lib.check(rc, "kpconv_deform_aggregate")
+    return _tag(wf, query_points)
+
+
+def kpconv_deformable(query_points, support_points, neighbors_indices, features, K_points, K_values, offset_weights, offset_bias,
+                      KP_extent, KP_influence="linear", aggregation_mode="sum", modulated=False, col_scale=None, col_shift=None,
+                      residual=None, leaky=False, alpha=0.2):
+    """Whole deformable KPConv (kernels/convolution_ops.py:258-499) + epilogue, four launches and the row flags:
+      1. the offset convolution: the rigid operator (aggregation, neighbour-count normalisation, contraction) with
+         offset_weights f32[num_kp, Cin, D] and col_shift = offset_bias f32[D], D = 3*num_kp (4*num_kp when modulated);
+      2. kpconv_deform_aggregate with its raw output (raw=True: the scaling by KP_extent and the sigmoid happen in the kernel);
+      3. the contraction with K_values f32[num_kp, Cin, Cout] and the caller's epilogue (no row_scale: no normalisation)."""
+    num_kp, cin, cout = K_values.shape
+    D = (4 if modulated else 3) * num_kp
+    if tuple(offset_weights.shape) != (num_kp, cin, D) or tuple(offset_bias.shape) != (D,):
+        raise ValueError("KPConv_deformable: offset_conv_weights %s / offset_conv_bias %s, expected (%d, %d, %d) / (%d,)" %
+                         (tuple(offset_weights.shape), tuple(offset_bias.shape), num_kp, cin, D, D))
+    if features.shape[1] != cin:
+        raise ValueError("KPConv_deformable: features have %d channels, K_values expects %d" % (features.shape[1], cin))
+    with f32_output():
+        wf0, inv_cnt = kpconv_aggregate(query_points, support_points, neighbors_indices, features, K_points, KP_extent, KP_influence,
+                                        aggregation_mode)
+        offsets = gemm(wf0, offset_weights.reshape(num_kp * cin, D), row_scale=inv_cnt, col_shift=offset_bias)
+    wf = kpconv_deform_aggregate(query_points, support_points, neighbors_indices, features, K_points, offsets, KP_extent,
+                                 KP_influence, aggregation_mode, raw=True)
+    return gemm(wf, K_values.reshape(num_kp * cin, cout), col_scale=col_scale, col_shift=col_shift, residual=residual, leaky=leaky,
+                alpha=alpha)
+
+
 def kpconv_fused_supported(cin, cout, num_kp, KP_influence, aggregation_mode, available=False):
     """Should KPConv_ops use the one-kernel form for this shape?  available=True: does the form exist at all (Cin = 256 exists
     but measured no faster than aggregation + contraction: see d3f_kpconv_fused_supported)."""

@@ -164,7 +164,8 @@ def is_model_variable(name):
     if not name.startswith(ROOT_SCOPE):
         return False
     tail = name.rsplit('/', 1)[-1]
-    return tail in ('weights', 'kernel_points', 'gamma', 'beta', 'moving_mean', 'moving_variance', 'offset', 'biases')
+    return tail in ('weights', 'kernel_points', 'gamma', 'beta', 'moving_mean', 'moving_variance', 'offset', 'biases',
+                    'offset_conv_weights', 'offset_conv_bias')
 
 
 def load_checkpoint(prefix, verify_crc=False):

@@ -225,6 +225,31 @@ int d3f_kpconv_aggregate(const float* q, int Nq, const float* s, int Ns, const i
                          int num_kp, float KP_extent, int influence, int aggregation, float* wf, float* inv_cnt,
                          const int* Nq_dev, const int* Ns_dev, const int* q_order, int feat_bf16, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Deformable KPConv, phase 1: the first half of kernels/convolution_ops.py:379-499 (KPConv_deform_ops), the kernel points of
+ * every query moved by its own offsets:
+ *   KP'[n,p]  = kp[p] + offsets[n, 3p .. 3p+2] * offset_scale
+ *   mod[n,p]  = modulations ? (mod_logits ? 2 * sigmoid(modulations[n,p]) : modulations[n,p]) : 1
+ *   in[n,k]   = any_p || (s[idx[n,k]] - q[n]) - KP'[n,p] ||^2 < KP_extent^2
+ *   wf[n,p,c] = mod[n,p] * sum_{k : in[n,k]}  h(|| (s[idx[n,k]] - q[n]) - KP'[n,p] ||) * f[idx[n,k], c]
+ * influence: 0 constant  h = (d2 < KP_extent^2), 1 linear  h = max(1 - sqrt(d2+1e-10)/KP_extent, 0)  (KP_extent, not 2*KP_extent
+ * as in d3f_kpconv_aggregate), 2 gaussian (sigma = 0.3*KP_extent); aggregation: 0 sum, 1 closest (arg-min over the DEFORMED points).
+ * A neighbour within KP_extent of no deformed point contributes nothing, for any influence; shadow neighbours (idx outside
+ * [0, Ns)) neither.  There is no neighbour count: the reference does not normalise this operator.
+ *   offsets f32[Nq, ld_off] (3*num_kp columns used)   modulations f32[Nq, ld_mod] (num_kp columns used) or NULL
+ *   other operands as d3f_kpconv_aggregate; wf f32[Nq, num_kp*Cin]
+ * KPConv_deformable (:258-376) passes the RAW output x f32[Nq, 4*num_kp] of its offset convolution: offsets = x, offset_scale =
+ * KP_extent, modulations = x + 3*num_kp, ld_mod = ld_off, mod_logits = 1 -- the scaling and the sigmoid cost no launch of their own.
+ * KPConv_deform_ops' own arguments are offset_scale = 1, mod_logits = 0.
+ * Phase 2 is d3f_gemm_f32(wf, K_values reshaped [num_kp*Cin, Cout]) without row_scale.
+ * fp32 feature rows only: feat_bf16 != 0 is D3F_ERR_ARG.  Ns == 0 with Nq > 0 is D3F_ERR_ARG.
+ * ------------------------------------------------------------------------------------------- */
+int d3f_kpconv_deform_aggregate(const float* q, int Nq, const float* s, int Ns, const int* idx, int ld_idx, int K,
+                                const void* f, int ldf, int Cin, const float* offsets, int ld_off, float offset_scale,
+                                const float* modulations, int ld_mod, int mod_logits, const float* kp_host, int num_kp,
+                                float KP_extent, int influence, int aggregation, float* wf, const int* Nq_dev, const int* Ns_dev,
+                                const int* q_order, int feat_bf16, void* stream);
+
 /* Whole KPConv_ops (kernels/convolution_ops.py:161-255) + the fused inference epilogue for Cin = 1 -- the input
  * layer of every shipped model (`simple` block on the all-ones features, models/network_blocks.py:222-244):
  *   out[n,o] = act( (sum_p wf[n,p] * W[p,o]) / max(#{k : f[idx[n,k]] > 0}, 1) * col_scale[o] + col_shift[o] + residual[n,o] )
