@@ -24,6 +24,9 @@
 // gemm_splitk_reduce_kernel      all of them                       the launcher split K (skinny problems: few output tiles,
 //   (gemm_common.h)                                                long K): slabs reduced in a fixed order (deterministic)
 //
+// Every instance of every kernel above, and every branch of their pipelines, is compared bit for bit with integer / float64
+// expectations in tests/test_gpu_gemm_branches.py (its docstring holds the branch -> test table; cases: oracle/gemm_cases.py).
+//
 // The fp32 kernels multiply with v_mfma_f32_32x32x2_f32 (f32 in / f32 accumulate, 64 cycles per SIMD, exact fp32 products and
 // sums): the 1e-4 parity bar is an fp32 bar.  The x3 form reaches the same bar on the bf16 pipe by exact operand splitting.
 #include "gemm_common.h"

@@ -151,3 +151,64 @@ def test_gemm_x3_plans():
     assert _plan(300000, 64, 256, 171000)[:2] == (128, 64)
     from d3feat_amd import _lib
     assert _lib.load().d3f_gemm_x3_plan(100, 64, 48, 0, None, None, None) == -3
+
+
+def _gemm_call(lib, entry, A, W, Cp, M=100, N=64, C1=64, skip=None, C2=0, res=None, cs=None, ws=None, wsb=0, res_idx=None, ld_res_idx=1,
+               a_bf16=0):
+    """one call of a composite-operand contraction entry point (d3f_gemm_f32t / _x3 / _x3_gres / _bf16) with host-side arguments only"""
+    head = [A, M, C1, C1, None, 0, skip, C2, C2, W, Cp, N, M, N, None, cs, None, res, N if res else 0]
+    tail = [0, 0.2, ws, wsb, None, None, 0]
+    if entry == "d3f_gemm_x3_gres":
+        head += [res_idx, ld_res_idx, 50, None]
+    if entry == "d3f_gemm_bf16":
+        tail += [a_bf16, 0]
+    return getattr(lib, entry)(*(head + tail + [None]))
+
+
+def test_gemm_entry_points_refuse_bad_arguments_without_a_gpu(lib):
+    """The six contraction entry points check addressing rules, the gathered-residual arguments and the workspace of a K-split plan on
+    the host, before anything is launched; M = 0 is D3F_OK whatever the pointers are (tests/test_gpu_gemm_branches.py runs what they
+    accept)."""
+    buf = ctypes.create_string_buffer(1 << 12)
+    p = (ctypes.addressof(buf) + 255) // 256 * 256
+    composite = ("d3f_gemm_f32t", "d3f_gemm_x3", "d3f_gemm_x3_gres", "d3f_gemm_bf16")
+    for e in composite:
+        # misaligned bases: A, the packed weights, the skip operand
+        assert _gemm_call(lib, e, p + 4, p, p) == -3, e
+        assert _gemm_call(lib, e, p, p + 8, p) == -3, e
+        assert _gemm_call(lib, e, p, p, p, C1=32, skip=p + 4, C2=32) == -3, e
+        assert _gemm_call(lib, e, None, p, p) == -3 and _gemm_call(lib, e, p, None, p) == -3 and _gemm_call(lib, e, p, p, None) == -3, e
+        if e != "d3f_gemm_bf16":                        # fp32 in and out: the output, the residual and the column vectors too
+            assert _gemm_call(lib, e, p, p, p + 4) == -3, e
+            assert _gemm_call(lib, e, p, p, p, res=p + 8) == -3, e
+            assert _gemm_call(lib, e, p, p, p, cs=p + 4) == -3, e
+        # M = 0: nothing to launch, pointers are not looked at
+        assert _gemm_call(lib, e, None, None, None, M=0) == 0, e
+    assert _gemm_call(lib, "d3f_gemm_bf16", p + 4, p, p, a_bf16=1) == -3          # bfloat16 features: 8-byte aligned rows
+    # x3: a concatenation whose first part is no whole k-tile (K = 64 itself is fine), K no multiple of 32
+    for e in ("d3f_gemm_x3", "d3f_gemm_x3_gres"):
+        assert _gemm_call(lib, e, p, p, p, C1=48, skip=p, C2=16) == -3, e
+        assert _gemm_call(lib, e, p, p, p, C1=48) == -3, e
+    # the gathered residual: an index without a residual, a leading dimension below 1
+    assert _gemm_call(lib, "d3f_gemm_x3_gres", p, p, p, res=None, res_idx=p) == -3
+    assert _gemm_call(lib, "d3f_gemm_x3_gres", p, p, p, res=p, res_idx=p, ld_res_idx=0) == -3
+    # a K-split plan (S = 2 at these shapes) with a workspace one byte short, or none
+    for e, M, K in (("d3f_gemm_f32t", 100, 544), ("d3f_gemm_bf16", 100, 544), ("d3f_gemm_x3", 200, 352), ("d3f_gemm_x3_gres", 200, 352)):
+        ws_fn = {"d3f_gemm_f32t": lib.d3f_gemm_workspace_bytes, "d3f_gemm_bf16": lib.d3f_gemm_bf16_workspace_bytes}.get(e, lib.d3f_gemm_x3_workspace_bytes)
+        need = 2 * M * 64 * 4
+        assert ws_fn(M, 64, K, 0) == need + 256, e
+        assert _gemm_call(lib, e, p, p, p, M=M, C1=K, ws=p, wsb=need - 1) == -2, e
+        assert _gemm_call(lib, e, p, p, p, M=M, C1=K, ws=None, wsb=need) == -2, e
+    # d3f_gemm_f32 / d3f_gemm_upsample_cat_f32 take any alignment; what they refuse: short leading dimensions, a skip operand that is
+    # not float4-addressable, a short workspace
+    f32 = lambda M=100, N=64, K=544, lda=544, ldb=64, ldc=64, ws=None, wsb=0, A=p: lib.d3f_gemm_f32(
+        A, lda, p, ldb, p, ldc, M, N, K, None, None, None, None, 0, 0, 0.2, ws, wsb, None, 0, None)
+    assert f32(lda=543) == -3 and f32(ldb=63) == -3 and f32(ldc=63) == -3 and f32(A=None) == -3
+    assert f32(ws=p, wsb=2 * 100 * 64 * 4 - 1) == -2 and f32(ws=None, wsb=1 << 20) == -2
+    assert lib.d3f_gemm_f32(None, 64, None, 64, None, 64, 0, 64, 64, None, None, None, None, 0, 0, 0.2, None, 0, None, 0, None) == 0
+    cat = lambda M=100, skip=p, lds=508, C1=36, C2=508, idx=p, ld_idx=1, ws=None, wsb=0: lib.d3f_gemm_upsample_cat_f32(
+        p, 50, C1, C1, idx, ld_idx, skip, lds, C2, p, 64, p, 64, M, 64, None, None, 0, 0.2, ws, wsb, None, None, 0, None)
+    assert cat(skip=p + 4) == -3 and cat(lds=509) == -3 and cat(C1=34, C2=510, lds=512) == -3 and cat(ld_idx=0) == -3
+    assert cat(idx=None) == -3                                                    # rows in place need N1 >= M
+    assert cat(ws=p, wsb=2 * 100 * 64 * 4 - 1) == -2
+    assert cat(M=0, skip=None, idx=None) == 0
