@@ -7,6 +7,8 @@ d3feat_amd.  NOT Open3D.
     registration.Feature                       :226,235
     registration_ransac_based_on_feature_matching, TransformationEstimationPointToPoint,
     CorrespondenceCheckerBasedOnEdgeLength / Distance, RANSACConvergenceCriteria      :184-192, evaluate.py:93-99
+    geometry.PointCloud, registration.* of the above, registration.registration_icp (refused) / ICPConvergenceCriteria
+                                               utils/tester.py:292-314, datasets/KITTI.py:20-32, 293-297 (test_kitti.py)
     estimate_normals, draw_geometries, geometry.create_mesh_sphere, set_verbosity_level, VerbosityLevel   (display: no-ops)
 
 voxel_down_sample: Open3D's voxel grid (origin at min - voxel/2, hash-map order) is third-party arithmetic that nothing in
@@ -136,6 +138,16 @@ class RANSACConvergenceCriteria:
         self.max_iteration, self.max_validation = int(max_iteration), int(max_validation)
 
 
+class ICPConvergenceCriteria:
+    def __init__(self, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30):
+        self.relative_fitness, self.relative_rmse, self.max_iteration = relative_fitness, relative_rmse, int(max_iteration)
+
+
+def registration_icp(*a, **kw):
+    # datasets/KITTI.py:295 refines the KITTI ground truth with it; the refined transforms come from the reference's cache files here
+    raise NotImplementedError("registration_icp is not part of d3feat_amd: use the cached data/kitti/icp/*.npy ground truth")
+
+
 class RegistrationResult:
     def __init__(self, transformation, fitness, inlier_rmse, correspondence_set):
         self.transformation, self.fitness, self.inlier_rmse = transformation, fitness, inlier_rmse
@@ -173,6 +185,8 @@ registration.TransformationEstimationPointToPoint = TransformationEstimationPoin
 registration.CorrespondenceCheckerBasedOnEdgeLength = CorrespondenceCheckerBasedOnEdgeLength
 registration.CorrespondenceCheckerBasedOnDistance = CorrespondenceCheckerBasedOnDistance
 registration.RANSACConvergenceCriteria = RANSACConvergenceCriteria
+registration.ICPConvergenceCriteria = ICPConvergenceCriteria
+registration.registration_icp = registration_icp
 Feature = _Feature
 
 utility = _Namespace()

@@ -804,3 +804,8 @@ extern "C" int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int
 // Validation figures of every pair in three launches (d3f_validation_pairs)
 // ---------------------------------------------------------------------------------------------------------------------
 #include "rp_validation.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// KITTI test metric (RTE, RRE, success, the running meters) of every estimate in two launches (d3f_pose_errors)
+// ---------------------------------------------------------------------------------------------------------------------
+#include "rp_pose_errors.h"

@@ -15,6 +15,9 @@
                                             keypoint count in two launches (evaluate.py:45-50,67-82), up to 8192 rows per block
     register_pairs_counts(kp, count, pairs, ...) register_pairs AND match_pairs for every pair at every keypoint count in one call
                                             (evaluate.py:45-50,67-99 swept over num_keypts), up to 8192 rows per block
+    pose_errors(T, gt)                      the KITTI test metric (RTE, RRE, success, the running meters) of every estimate in two
+                                            launches (utils/tester.py:326-344; float64); register_kitti_pairs(kp, count, gt, voxel)
+                                            is register_pairs + pose_errors as ModelTester.test_kitti pairs them (:292-344)
 
 Every computation is a kernel of libd3feat_amd.so (csrc/registration.hip, csrc/radius_neighbors.hip); numpy / torch only
 move data and run the host loop over batches of hypotheses.  Open3D's own random stream is unspecified, so results are
@@ -24,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .utils import results
 
 
 def _dev(device=None):
@@ -604,3 +608,126 @@ def register_pairs_counts(kp, count, pairs, max_correspondence_distance, num_key
             ws.data_ptr(), ws.numel(), st)
         _lib.check(rc, "register_pairs_counts")
     return out
+
+
+# ---- the KITTI test metric of every pair in one call (utils/tester.py:235-360) ------------------------------------------------------
+KITTI_SUCCESS = dict(rte_threshold=2.0, rre_threshold=np.pi / 180 * 5)         # tester.py:332-338
+
+
+def EVALUATE_KITTI(voxel_size):
+    """tester.py:305-314: the RANSAC call the reference makes for every KITTI test pair, as register_pairs' keywords."""
+    v = float(voxel_size) * 1.0
+    return dict(max_correspondence_distance=v, ransac_n=4, edge_similarity=0.9, checker_distance=v, max_iteration=50000,
+                max_validation=1000)
+
+
+def frame_pairs(n_pairs, device=None):
+    """(2i, 2i + 1) for i < n_pairs, the block order of FragmentEngine(two_clouds=True, keypoints=K) -> device i32[n_pairs, 2]."""
+    a = np.arange(2 * int(n_pairs), dtype=np.int32).reshape(-1, 2)
+    return torch.from_numpy(a).to(_dev(device))
+
+
+class PairPoseErrors:
+    """Result of pose_errors: DEVICE tensors rte f64[P, n] (metres), rre_deg f64[P, n] (degrees, NaN kept), flags i32[P, n] (bit 0:
+    rte under its threshold, bit 1: rre under its threshold and no NaN, bit 2: both = success) and sums f64[n, 8] (per column the
+    sums of d3f_pose_errors' meters: rte sum / square sum / number, the same of rre_deg, successes, P); n is 1 for a [P, 3, 4] input
+    (the tensors are then [P]).  .meters(c) turns the sums into the reference's AverageMeter figures."""
+
+    def __init__(self, P, per_pair, flat, device):
+        self.P, self.per_pair, self.flat = P, per_pair, flat
+        shape = (P,) if flat else (P, per_pair)
+        self.rte = torch.empty(shape, dtype=torch.float64, device=device)
+        self.rre_deg = torch.empty(shape, dtype=torch.float64, device=device)
+        self.flags = torch.empty(shape, dtype=torch.int32, device=device)
+        self.sums = torch.empty((per_pair, 8), dtype=torch.float64, device=device)
+
+    _cache = None
+
+    def host(self):
+        """One read-back of the whole result, kept until the next pose_errors(out=self): dict of numpy arrays rte, rre_deg, flags
+        ([P, n], a column per count) and sums [n, 8]."""
+        if self._cache is None:
+            two = lambda t: t.cpu().numpy().reshape(self.P, self.per_pair)
+            self._cache = dict(rte=two(self.rte), rre_deg=two(self.rre_deg), flags=two(self.flags), sums=self.sums.cpu().numpy())
+        return self._cache
+
+    def meters(self, c=0):
+        """{"rte" | "rre" | "success": dict(sum, count, avg, var)} of column c: the AverageMeters of tester.py:252 after the last pair
+        (var is NaN for a meter that never updated: the reference has no such attribute then)."""
+        return results.kitti_meters_from_sums(self.host()["sums"][c])
+
+    def failed(self, ids, c=0):
+        """[(id, rte, rre_deg)] of the pairs without success in column c, in pair order: the 'Failed with' lines of tester.py:342."""
+        h = self.host()
+        if len(ids) != self.P:
+            raise ValueError("PairPoseErrors.failed: %d ids for %d pairs" % (len(ids), self.P))
+        return [(ids[p], float(h["rte"][p, c]), float(h["rre_deg"][p, c])) for p in range(self.P) if not h["flags"][p, c] & 4]
+
+    def running(self, every=10, c=0):
+        """[(i, meters after the first i pairs)] for i = every, 2 every, ...: the figures of the periodic line (tester.py:346-352),
+        computed on the host from the per-pair arrays in pair order."""
+        h = self.host()
+        return [(i, results.kitti_meters(h["rte"][:i, c], h["rre_deg"][:i, c], h["flags"][:i, c]))
+                for i in range(int(every), self.P + 1, int(every))]
+
+
+def pose_errors(T, gt, rte_threshold=KITTI_SUCCESS["rte_threshold"], rre_threshold=KITTI_SUCCESS["rre_threshold"], out=None):
+    """The KITTI test metric (tester.py:326-344) of estimated transforms in one call: T f32[P, 3, 4] (PairRegistration.T) or
+    f32[P, n, 3, 4] (PairRegistrationCounts.T), gt f32[P, 3, 4] in the SAME direction as T -- source -> target, KITTI's `trans` and what
+    register_pairs returns for (anchor, positive); NOT the target -> source gt register_pairs itself takes -- both on the device.
+    rte = |t - t_gt|, rre = arccos((trace(R^T R_gt) - 1) / 2) in float64 (NaN kept and counted as a failure), thresholds in metres and
+    radians, strict.  Two launches whatever P is, no read-back (capturable: pass the previous result as `out`).
+    -> PairPoseErrors (device tensors; .host(), .meters(), .failed(ids), .running())."""
+    lib = _lib.load()
+    T = ops._req(T, torch.float32, "T")
+    if T.dim() not in (3, 4) or tuple(T.shape[-2:]) != (3, 4) or not T.is_contiguous():
+        raise ValueError("pose_errors: T of shape %s (contiguous [P, 3, 4] or [P, n, 3, 4])" % (tuple(T.shape),))
+    dev, P, flat = T.device, T.shape[0], T.dim() == 3
+    n = 1 if flat else T.shape[1]
+    gt = ops._req(gt, torch.float32, "gt", 3)
+    if tuple(gt.shape) != (P, 3, 4) or not gt.is_contiguous() or n < 1:
+        raise ValueError("pose_errors: gt of shape %s for T %s" % (tuple(gt.shape), tuple(T.shape)))
+    thr = (float(rte_threshold), float(rre_threshold))
+    if not (thr[0] > 0.0 and thr[1] > 0.0):
+        raise ValueError("pose_errors: thresholds %r, %r" % (rte_threshold, rre_threshold))
+    if out is None:
+        out = PairPoseErrors(P, n, flat, dev)
+    elif not isinstance(out, PairPoseErrors) or (out.P, out.per_pair, out.flat) != (P, n, flat) or out.rte.device != dev:
+        raise ValueError("pose_errors: out= was made for another call")
+    out._cache = None
+    if P == 0:
+        out.sums.zero_()                                         # (plumbing: the meters of no pairs; an empty tensor has no address)
+        return out
+    c_thr = (_lib.C.c_double * 2)(*thr)
+    # one call whatever P is: the summation order of the meters is part of their definition
+    rc = lib.d3f_pose_errors(T.data_ptr(), gt.data_ptr(), P, n, _lib.C.addressof(c_thr), out.rte.data_ptr(), out.rre_deg.data_ptr(),
+                             out.flags.data_ptr(), out.sums.data_ptr(), ops._stream(dev))
+    _lib.check(rc, "pose_errors")
+    return out
+
+
+class KittiRegistration:
+    """Result of register_kitti_pairs: `registration` (PairRegistration of register_pairs(frame_pairs, **EVALUATE_KITTI)) and `errors`
+    (PairPoseErrors of its T against gt), both device tensors."""
+
+    def __init__(self, registration, errors, pairs):
+        self.registration, self.errors, self.pairs = registration, errors, pairs
+        self.T = registration.T
+
+
+def register_kitti_pairs(kp, count, gt, voxel_size, seed=0, out=None):
+    """The registration and the metric of ModelTester.test_kitti (tester.py:292-344) for every pair in one call: kp f32[2 P, K, ld] /
+    count i32[2 P] the keypoint blocks of FragmentEngine(two_clouds=True, keypoints=K) -- blocks 2i and 2i + 1 are anchor and positive
+    of pair i --, gt f32[P, 3, 4] KITTI's `trans` (source -> target).  register_pairs(frame_pairs(P), **EVALUATE_KITTI(voxel_size))
+    and then pose_errors on its T with KITTI_SUCCESS, no read-back in between (capturable: pass the previous result as `out`); T is
+    bit-equal to register_pairs' own.  gt is NOT handed to register_pairs, whose gt runs target -> source.  -> KittiRegistration."""
+    kp = ops._req(kp, torch.float32, "kp", 3)
+    if kp.shape[0] % 2:
+        raise ValueError("register_kitti_pairs: %d keypoint blocks, not two per pair" % kp.shape[0])
+    P = kp.shape[0] // 2
+    if out is not None and not isinstance(out, KittiRegistration):
+        raise ValueError("register_kitti_pairs: out= was made for another call")
+    pairs = out.pairs if out is not None else frame_pairs(P, kp.device)
+    reg = register_pairs(kp, count, pairs, seed=seed, out=out.registration if out is not None else None, **EVALUATE_KITTI(voxel_size))
+    err = pose_errors(reg.T, gt, out=out.errors if out is not None else None, **KITTI_SUCCESS)
+    return out if out is not None else KittiRegistration(reg, err, pairs)

@@ -188,3 +188,85 @@ def save_overlap_tables(savepath, ids, pairs, ratios, matches, split="train", do
             pickle.dump(table, f)
         out.append(path)
     return out
+
+
+# ---- the files and log lines of ModelTester.test_kitti (utils/tester.py:235-360) ----------------------------------------------------
+def kitti_pair_filename(anc_id, pos_id):
+    """tester.py:298: '<drive>@<t0>-<t1>.npz' from the generator's ids '<drive>@<t0>' and '<drive>@<t1>' (str or bytes)."""
+    a, p = (s.decode("utf-8") if isinstance(s, bytes) else str(s) for s in (anc_id, pos_id))
+    return a + "-" + p.split("@")[-1] + ".npz"
+
+
+def save_kitti_pair(directory, anc_id, pos_id, T, anc_pts, pos_pts, anc_scores, pos_scores):
+    """The per-pair file of tester.py:317-323 under `directory`: trans f32[4,4] (T as [3,4] or [4,4], source -> target) and the
+    keypoints and scores of both clouds.  Returns the path."""
+    T = np.asarray(T, dtype=np.float32)
+    if T.shape == (3, 4):
+        T = np.vstack([T, np.array([[0, 0, 0, 1]], np.float32)])
+    if T.shape != (4, 4):
+        raise ValueError("save_kitti_pair: T of shape %s" % (T.shape,))
+    os.makedirs(directory, exist_ok=True)
+    path = os.path.join(directory, kitti_pair_filename(anc_id, pos_id))
+    np.savez(path, trans=T, anc_pts=np.asarray(anc_pts), pos_pts=np.asarray(pos_pts), anc_scores=np.asarray(anc_scores),
+             pos_scores=np.asarray(pos_scores))
+    return path
+
+
+def _meter(s, sq, n):
+    n = int(n)
+    avg = float(s) / n if n else 0                       # AverageMeter.reset: avg = 0 until the first update
+    return dict(sum=float(s), count=n, avg=avg, var=float(sq) / n - avg ** 2 if n else float("nan"))
+
+
+def kitti_meters_from_sums(sums):
+    """The three AverageMeters of tester.py:252 from the eight sums of d3f_pose_errors (rte sum, square sum, number; the same of
+    rre in degrees; successes; pairs) -> {"rte" | "rre" | "success": dict(sum, count, avg, var)}; var is NaN for a meter without an
+    update (the reference has no such attribute then)."""
+    s = [float(v) for v in np.asarray(sums, dtype=np.float64).reshape(8)]
+    return dict(rte=_meter(s[0], s[1], s[2]), rre=_meter(s[3], s[4], s[5]), success=_meter(s[6], s[6], s[7]))
+
+
+def kitti_meters(rte, rre_deg, flags):
+    """kitti_meters_from_sums of per-pair arrays (flags: bit 0 rte under its threshold, bit 1 rre, bit 2 success), summed in pair
+    order in float64 as the reference's loop updates its meters (tester.py:332-341)."""
+    rte, rre_deg, flags = np.asarray(rte, np.float64), np.asarray(rre_deg, np.float64), np.asarray(flags)
+    s = [0.0] * 8
+    for t, r, f in zip(rte, rre_deg, flags):
+        if f & 1:
+            s[0] += t; s[1] += t * t; s[2] += 1
+        if f & 2:
+            s[3] += r; s[4] += r * r; s[5] += 1
+        s[6] += 1 if f & 4 else 0
+        s[7] += 1
+    return kitti_meters_from_sums(s)
+
+
+def kitti_lines(anc_ids, rte, rre_deg, flags, every=10, feat_times=None, reg_times=None, final=None):
+    """The log lines of ModelTester.test_kitti without their time stamps, in its order: per failed pair
+    "b'<id>' Failed with RTE: .., RRE: .." (tester.py:342), after every `every` pairs the running line (:347-352, the two timers averaged
+    since the last such line and then reset), and the closing "Total loss" line (:356-360).  anc_ids: str or bytes per pair; rte /
+    rre_deg / flags: the per-pair arrays of registration.pose_errors(...).host() (one column); feat_times / reg_times: seconds per
+    pair (None: 0.0); final: the meters of the closing line (PairPoseErrors.meters(); None: from the arrays).  The loss is the
+    constant 0 the reference sets (:328), Success is the float sum over the integer count."""
+    rte, rre_deg, flags = (np.asarray(a).reshape(-1) for a in (rte, rre_deg, flags))
+    n = len(anc_ids)
+    if not (rte.shape[0] == rre_deg.shape[0] == flags.shape[0] == n):
+        raise ValueError("kitti_lines: %d ids, %d / %d / %d figures" % (n, rte.shape[0], rre_deg.shape[0], flags.shape[0]))
+    every = int(every)
+    ft = np.zeros(n) if feat_times is None else np.asarray(feat_times, np.float64)
+    rt = np.zeros(n) if reg_times is None else np.asarray(reg_times, np.float64)
+    lines = []
+    for i in range(n):
+        if not flags[i] & 4:
+            a = anc_ids[i] if isinstance(anc_ids[i], bytes) else str(anc_ids[i]).encode("utf-8")
+            lines.append(f"{a} Failed with RTE: {float(rte[i])}, RRE: {float(rre_deg[i])}")
+        if (i + 1) % every == 0:
+            m = kitti_meters(rte[:i + 1], rre_deg[:i + 1], flags[:i + 1])
+            w = slice(i + 1 - every, i + 1)
+            lines.append(f"{i+1} / {n}: Feat time: {float(np.mean(ft[w]))}, Reg time: {float(np.mean(rt[w]))}, Loss: {0.0},"
+                         f" RTE: {m['rte']['avg']}, RRE: {m['rre']['avg']}, Success: {m['success']['sum']} / {m['success']['count']}"
+                         f" ({m['success']['avg'] * 100} %)")
+    m = final if final is not None else kitti_meters(rte, rre_deg, flags)
+    lines.append(f"Total loss: {0.0}, RTE: {m['rte']['avg']}, var: {m['rte']['var']}, RRE: {m['rre']['avg']}, var: {m['rre']['var']},"
+                 f" Success: {m['success']['sum']} / {m['success']['count']} ({m['success']['avg'] * 100} %)")
+    return lines

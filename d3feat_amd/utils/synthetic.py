@@ -105,3 +105,28 @@ def overlap_scene(seed, n_frag=6, n_raw=12000, thr=0.05, edge=3.0, half_width=0.
         sel = inside[rng.random(len(inside)) < keep]
         out.append((world[sel] + rng.normal(scale=0.3 * thr / np.sqrt(3.0), size=(len(sel), 3))).astype(np.float32))
     return out
+
+
+def keypoint_pairs(seed, n_pairs=3, K=64, C=32, extent=20.0, noise=0.03, dnoise=0.1, outliers=0.2):
+    """Keypoint blocks [xyz | C-d unit desc | score] (ascending score) of n_pairs pairs of frames at the scale of a KITTI sweep: block
+    2i + 1 is block 2i moved by a known motion of a few metres and degrees, re-noised, a share `outliers` of its rows replaced, its
+    rows in another order.  -> (kp f32[2 n_pairs, K, C + 4], gt f32[n_pairs, 3, 4] taking block 2i into the frame of block 2i + 1)."""
+    rng = np.random.default_rng(seed)
+    kp, gt = np.zeros((2 * n_pairs, K, C + 4), np.float32), np.zeros((n_pairs, 3, 4), np.float32)
+    for i in range(n_pairs):
+        xyz = rng.uniform(-extent, extent, (K, 3)) * [1, 1, 0.1]
+        desc = rng.standard_normal((K, C))
+        a = rng.normal(size=3) * [0.1, 0.1, 1]
+        a /= np.linalg.norm(a)
+        th = np.deg2rad(rng.uniform(1, 15))
+        Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+        R, t = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx), rng.normal(size=3) * [4, 1, 0.1]
+        xyz1, desc1 = xyz @ R.T + t + rng.normal(scale=noise, size=xyz.shape), desc + dnoise * rng.standard_normal(desc.shape)
+        out = rng.random(K) < outliers
+        xyz1[out], desc1[out] = rng.uniform(-extent, extent, (int(out.sum()), 3)), rng.standard_normal((int(out.sum()), C))
+        perm = rng.permutation(K)
+        for b, (x, d) in enumerate(((xyz, desc), (xyz1[perm], desc1[perm]))):
+            d = d / np.linalg.norm(d, axis=1, keepdims=True)
+            kp[2 * i + b] = np.concatenate([x, d, np.sort(rng.random((K, 1)), 0)], 1)
+        gt[i] = np.hstack([R, t.reshape(3, 1)])
+    return kp, gt

@@ -724,6 +724,38 @@ int d3f_validation_pairs(const float* desc, int ldd, int C, const float* score, 
                          float log_scale, float* values, int* status_dev, double* sums_dev, int64_t* counts_dev, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* The KITTI test metric of P * per_pair estimated transforms in two launches (utils/tester.py:326-344 of the reference: relative
+ * translation error, relative rotation error, success under both thresholds, and the sums of its three AverageMeters).
+ *   T_est f32[P * per_pair, 12], row-major [R | t]; gt f32[P, 12] in the SAME direction as T_est: source -> target, the direction of
+ *     KITTI's `trans` and of what d3f_register_pairs returns for the pair (anchor, positive).  NOT the target -> source convention of
+ *     d3f_register_pairs' own gt argument.  Row i uses gt[i / per_pair]: per_pair is 1 for d3f_register_pairs' T_out and n_counts for
+ *     d3f_register_pairs_counts' T_out.
+ *   thresholds_host: TWO doubles on the host, [rte_max, rre_max in radians] (2 and pi / 180 * 5 in the reference), read before the
+ *     call returns.
+ * Per row, in float64, the inputs widened f32 -> f64 and every operation rounded on its own (never contracted):
+ *     d_r = T[r,3] - G[r,3];  rte = sqrt((d0 d0 + d1 d1) + d2 d2);
+ *     tr  = the nine products T[k,i] G[k,i] of the rotation parts in row-major order (k outer), summed left to right
+ *           (= trace(R_est^T R_gt));  c = (tr - 1) / 2;  rre = acos(c);  rre_deg = (rre * 180) / pi.
+ *   A NaN is kept, never clamped: c > 1 gives rre = NaN, and NaN counts as a failure (tester.py:330,335 do not clamp either).
+ *   rte_dev f64[P * per_pair], rre_deg_dev f64[P * per_pair] (degrees), flags_dev i32[P * per_pair]:
+ *     bit 0: rte < rte_max;  bit 1: rre is no NaN and rre < rre_max (radians);  bit 2: both.  Strict comparisons (tester.py:332-338).
+ *   meters_dev (optional) f64[per_pair, 8], per column c over the rows p * per_pair + c, p = 0 .. P - 1:
+ *     [0] sum of rte, [1] sum of rte * rte, [2] their number -- over the rows with bit 0 (whatever bit 1 is);
+ *     [3] sum of rre_deg, [4] sum of rre_deg * rre_deg, [5] their number -- over the rows with bit 1 (whatever bit 0 is);
+ *     [6] rows with bit 2, [7] P.  avg = sum / n and var = sq_sum / n - avg^2 are the reference's AverageMeter figures.
+ *   THE SUMMATION ORDER IS PART OF THE DEFINITION: 256 partial sums, partial t adding the rows p = t, t + 256, t + 512, ... in ascending
+ *     order from 0.0 (rows without the bit are skipped); then s = 128, 64, ... 1: partial[t] += partial[t + s] for t < s; the result
+ *     is partial[0].  The squares are rounded products.  One workgroup, a second launch.
+ * NEAR THE GROUND TRUTH the decision rests on the float32 rounding of the two matrices: for T_est == gt, c computed in float64
+ * exceeds 1 (rre NaN, a failure) for about half of random float32-rounded rotations, where the reference's own float32 evaluation
+ * exceeds 1 for about 0.25 % of them; within roughly 0.03 degrees of gt the two can differ.  RANSAC on 0.3 m voxels does not get there.
+ * D3F_ERR_ARG before anything touches the device: P < 0, per_pair < 1, P * per_pair >= 2^31, a NULL pointer other than meters_dev, a
+ * NaN or non-positive threshold.  P == 0 is D3F_OK (the meters, when asked for, are written as zeros by one launch).
+ * Asynchronous on `stream`; no float atomics, no ticket counter, no memset, no workspace, no allocation, no synchronisation:
+ * capturable. */
+int d3f_pose_errors(const float* T_est, const float* gt, int P, int per_pair, const double* thresholds_host, double* rte_dev,
+                    double* rre_deg_dev, int* flags_dev, double* meters_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
