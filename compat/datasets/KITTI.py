@@ -1,8 +1,11 @@
 """datasets.KITTI.KITTIDataset for the reference's unchanged test_kitti.py: the TEST split only (datasets/KITTI.py:62-80
 constructor, :82-133 pair list, :135-243 generator, :245-256 mapping, :268-337 one pair).  Sweeps are read from
-data/kitti/sequences/<drive>/velodyne/, poses from data/kitti/poses/, the ground truth of a pair from the reference's cache
-data/kitti/icp/<drive>_<t0>_<t1>.npy.  ICP refinement is not built here: a pair without a cache file is an error unless the
-environment says D3FEAT_KITTI_ODOMETRY_GT=1, which selects the unrefined odometry transform (:288-289) and writes nothing.
+data/kitti/sequences/<drive>/velodyne/, poses from data/kitti/poses/, the ground truth of a pair from the cache
+data/kitti/icp/<drive>_<t0>_<t1>.npy.  A pair without a cache file is an error unless the environment says
+D3FEAT_KITTI_REFINE_GT=1 (refine_gt: the file is computed by the device ICP and written, as the reference does at :293-303 -- one
+pair per device call, as the generator reads them; `python tools/kitti_icp.py --root data/kitti` fills the whole cache 16 pairs per
+call and is the faster way, run it first), or
+D3FEAT_KITTI_ODOMETRY_GT=1, which selects the unrefined odometry transform (:288-289) and writes nothing.
 Training / validation splits and augmentation are out of scope."""
 import os
 
@@ -32,7 +35,7 @@ def make_open3d_feature(data, dim, npts):
 class KITTIDataset(Dataset):
     DATA_FILES = {'test': 'data/kitti/config/test_kitti.txt'}
 
-    def __init__(self, input_threads=8, first_subsampling_dl=0.30, load_test=False):
+    def __init__(self, input_threads=8, first_subsampling_dl=0.30, load_test=False, refine_gt=None):
         Dataset.__init__(self, 'KITTI')
         self.network_model = 'descriptor'
         self.num_threads = input_threads
@@ -41,6 +44,7 @@ class KITTIDataset(Dataset):
         self.icp_path = 'data/kitti/icp'
         self.voxel_size = first_subsampling_dl
         self.odometry_gt = os.environ.get("D3FEAT_KITTI_ODOMETRY_GT", "0") == "1"
+        self.refine_gt = (os.environ.get("D3FEAT_KITTI_REFINE_GT", "0") == "1") if refine_gt is None else bool(refine_gt)
         self.anc_points = {'train': [], 'val': [], 'test': []}
         self.files = {'train': [], 'val': [], 'test': []}
         if not self.load_test:
@@ -62,7 +66,8 @@ class KITTIDataset(Dataset):
     def __getitem__(self, split, idx):
         """:268-337 for a test pair -> (aligned anchor, positive, anchor, positive, matches, trans, True)"""
         drive, t0, t1 = self.files[split][idx]
-        trans = kitti.pair_transform(self.root, drive, t0, t1, icp_dir=self.icp_path, odometry_gt=self.odometry_gt)
+        trans = kitti.pair_transform(self.root, drive, t0, t1, icp_dir=self.icp_path, odometry_gt=self.odometry_gt,
+                                     refine=self.refine_gt)
         xyz0, xyz1 = kitti.read_pair(self.root, drive, t0, t1)
         pcd0 = open3d.voxel_down_sample(make_open3d_point_cloud(xyz0), self.voxel_size)
         pcd1 = open3d.voxel_down_sample(make_open3d_point_cloud(xyz1), self.voxel_size)

@@ -7,7 +7,7 @@ d3feat_amd.  NOT Open3D.
     registration.Feature                       :226,235
     registration_ransac_based_on_feature_matching, TransformationEstimationPointToPoint,
     CorrespondenceCheckerBasedOnEdgeLength / Distance, RANSACConvergenceCriteria      :184-192, evaluate.py:93-99
-    geometry.PointCloud, registration.* of the above, registration.registration_icp (refused) / ICPConvergenceCriteria
+    geometry.PointCloud, registration.* of the above, registration.registration_icp (point to point) / ICPConvergenceCriteria
                                                utils/tester.py:292-314, datasets/KITTI.py:20-32, 293-297 (test_kitti.py)
     estimate_normals, draw_geometries, geometry.create_mesh_sphere, set_verbosity_level, VerbosityLevel   (display: no-ops)
 
@@ -143,9 +143,23 @@ class ICPConvergenceCriteria:
         self.relative_fitness, self.relative_rmse, self.max_iteration = relative_fitness, relative_rmse, int(max_iteration)
 
 
-def registration_icp(*a, **kw):
-    # datasets/KITTI.py:295 refines the KITTI ground truth with it; the refined transforms come from the reference's cache files here
-    raise NotImplementedError("registration_icp is not part of d3feat_amd: use the cached data/kitti/icp/*.npy ground truth")
+def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None):
+    """datasets/KITTI.py:295 refines the KITTI ground truth with it.  Point to point without scaling only: d3feat_amd.icp.icp_pairs on
+    one pair (the definition of include/d3feat_amd.h, not Open3D's bits; the points are rounded to float32 as every cloud here)."""
+    est = estimation_method if estimation_method is not None else TransformationEstimationPointToPoint(False)
+    if not isinstance(est, TransformationEstimationPointToPoint):
+        raise NotImplementedError("registration_icp: only TransformationEstimationPointToPoint is built (got %s)" % type(est).__name__)
+    if est.with_scaling:
+        raise NotImplementedError("TransformationEstimationPointToPoint(with_scaling=True) is not used by the reference")
+    from d3feat_amd import icp as _icp
+    crit = criteria if criteria is not None else ICPConvergenceCriteria()
+    src = np.ascontiguousarray(np.asarray(source.points), dtype=np.float32).reshape(-1, 3)
+    tgt = np.ascontiguousarray(np.asarray(target.points), dtype=np.float32).reshape(-1, 3)
+    T0 = None if init is None else np.asarray(init, np.float64).reshape(1, 4, 4)
+    r = _icp.icp_pairs(src, [len(src)], tgt, [len(tgt)], init=T0, max_correspondence_distance=float(max_correspondence_distance),
+                       max_iteration=crit.max_iteration, relative_fitness=float(crit.relative_fitness),
+                       relative_rmse=float(crit.relative_rmse))
+    return RegistrationResult(r.transformation[0], float(r.fitness[0]), float(r.inlier_rmse[0]), r.correspondences(0))
 
 
 class RegistrationResult:

@@ -97,6 +97,8 @@ SIGNATURES = {
     "d3f_validation_pairs": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _f, _f, _f, _f] + [_vp] * 5
                              + [_sz, _vp]),
     "d3f_pose_errors": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "d3f_icp_pairs_workspace_bytes": (_sz, [_i, _i]),
+    "d3f_icp_pairs": (_i, [_vp, _sz, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i] + [_vp] * 9 + [_sz, _vp]),
     "d3f_gemm_pack_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_pack_f32t": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_f32t": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _sz,

@@ -822,3 +822,6 @@ extern "C" int d3f_batch_radius_neighbors(const float* queries, int Nq, const fl
 
 // ---- RANSAC registration of every pair at every keypoint count: the stack, the grid, scoring and selection (nb_register_counts.h) --
 #include "nb_register_counts.h"
+
+// ---- point-to-point ICP of every pair to convergence (nb_icp.h) -------------------------------------------------------------------
+#include "nb_icp.h"

@@ -16,6 +16,7 @@
 // hypothesis (Horn's closed-form absolute orientation: largest eigenvector of a 4x4 symmetric matrix by cyclic Jacobi, fp64);
 // scoring of the validated hypotheses against the neighbour grid of radius_neighbors.hip (d3f_neighbor_grid_score).
 #include "prims.h"
+#include "rc_shared.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // nearest feature: key[i] = min_j (||A_i - B_j||^2 bits << 32 | j)
@@ -156,50 +157,7 @@ __host__ __device__ __forceinline__ int rg_draw(unsigned long long seed, unsigne
     return (int)((r >> 11) % (unsigned long long)n);
 }
 
-// Horn 1987: rotation maximising sum t_i . R s_i from the cross-covariance S = sum (s_i - ms)(t_i - mt)^T: unit quaternion =
-// eigenvector of the largest eigenvalue of the symmetric 4x4 matrix N(S); cyclic Jacobi in fp64 (a fixed number of sweeps).
-__device__ void rg_horn(const double S[3][3], double R[3][3]) {
-    double N[4][4] = {
-        {S[0][0] + S[1][1] + S[2][2], S[1][2] - S[2][1], S[2][0] - S[0][2], S[0][1] - S[1][0]},
-        {0, S[0][0] - S[1][1] - S[2][2], S[0][1] + S[1][0], S[2][0] + S[0][2]},
-        {0, 0, -S[0][0] + S[1][1] - S[2][2], S[1][2] + S[2][1]},
-        {0, 0, 0, -S[0][0] - S[1][1] + S[2][2]}};
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < i; ++j) N[i][j] = N[j][i];
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        for (int p = 0; p < 3; ++p)
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = N[p][q];
-                if (fabs(apq) < 1e-300) continue;
-                const double theta = (N[q][q] - N[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 4; ++k) {   // columns p, q of N
-                    const double nkp = N[k][p], nkq = N[k][q];
-                    N[k][p] = c * nkp - s * nkq;
-                    N[k][q] = s * nkp + c * nkq;
-                }
-                for (int k = 0; k < 4; ++k) {   // rows p, q of N
-                    const double npk = N[p][k], nqk = N[q][k];
-                    N[p][k] = c * npk - s * nqk;
-                    N[q][k] = s * npk + c * nqk;
-                }
-                for (int k = 0; k < 4; ++k) {
-                    const double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    int m = 0;
-    for (int i = 1; i < 4; ++i) if (N[i][i] > N[m][m]) m = i;
-    double w = V[0][m], x = V[1][m], y = V[2][m], z = V[3][m];
-    const double nrm = sqrt(w * w + x * x + y * y + z * z);
-    w /= nrm; x /= nrm; y /= nrm; z /= nrm;
-    R[0][0] = 1 - 2 * (y * y + z * z); R[0][1] = 2 * (x * y - w * z);     R[0][2] = 2 * (x * z + w * y);
-    R[1][0] = 2 * (x * y + w * z);     R[1][1] = 1 - 2 * (x * x + z * z); R[1][2] = 2 * (y * z - w * x);
-    R[2][0] = 2 * (x * z - w * y);     R[2][1] = 2 * (y * z + w * x);     R[2][2] = 1 - 2 * (x * x + y * y);
-}
+// rg_horn (Horn 1987, fp64 Jacobi): rc_shared.h -- shared with the ICP finish kernel of radius_neighbors.hip (nb_icp.h)
 
 #define RG_MAXN 8
 

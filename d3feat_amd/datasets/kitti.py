@@ -1,10 +1,12 @@
 """The host side of the KITTI odometry TEST split (datasets/KITTI.py of the reference): which frame pairs are tested, the ground-truth
-transform of a pair, and its two sweeps.  Pure numpy; ICP refinement of the ground truth (KITTI.py:295) is not built here -- the
-refined transforms are read from the reference's cache files, or the unrefined odometry is used when the caller says so.
+transform of a pair, and its two sweeps.  Pure numpy, except the ICP refinement of the ground truth (KITTI.py:293-303), which runs on
+the device (d3feat_amd.icp) and only when asked for: refine_pairs / pair_transform(refine=True) write the cache files the reference
+would.  By default the refined transforms are read from the cache, or the unrefined odometry is used when the caller says so.
 
     <root>/sequences/<drive:02d>/velodyne/<frame:06d>.bin      float32 records x, y, z, reflectance
     <root>/poses/<drive:02d>.txt                               one 3x4 camera pose per frame, row-major
     <icp_dir>/<drive>_<t0>_<t1>.npy                            f64[4,4], source (t0) -> target (t1), ICP-refined by the reference
+                                                               (or by refine_pairs: the same file name, the same content rule)
 """
 import glob
 import os
@@ -92,20 +94,58 @@ def odometry_transform(root, drive, t0, t1):
     return (v2c @ pos[t0].T @ np.linalg.inv(pos[t1].T) @ np.linalg.inv(v2c)).T
 
 
-def pair_transform(root, drive, t0, t1, icp_dir=None, odometry_gt=False):
-    """Ground truth of a test pair, source (t0) -> target (t1), f64[4,4] (KITTI.py:283-310): <icp_dir>/<drive>_<t0>_<t1>.npy when it
-    exists -- the reference's ICP-refined cache.  Without it: FileNotFoundError naming the file, unless odometry_gt=True asks for the
-    unrefined odometry transform (:288-289), which is never written to the cache.  A missing cache never silently changes the metric."""
+def cache_file(root, drive, t0, t1, icp_dir=None):
     icp_dir = icp_dir if icp_dir is not None else os.path.join(root, "icp")
-    path = os.path.join(icp_dir, "%d_%d_%d.npy" % (drive, t0, t1))
+    return os.path.join(icp_dir, "%d_%d_%d.npy" % (drive, t0, t1))
+
+
+def refine_pairs(root, pairs, icp_dir=None, batch=16, check_every=8):
+    """For every (drive, t0, t1) of `pairs` without a cache file: the ICP-refined ground truth of KITTI.py:288-303, computed on the
+    device `batch` pairs per call (d3feat_amd.icp.icp_pairs with ICP_KITTI) and np.save'd where the reference would -> the number of
+    files written.  The file holds WHAT THE REFERENCE WRITES: M2 = M @ T_icp (KITTI.py:300, in that order), M the odometry transform and
+    T_icp the ICP from the identity on the sweep pre-moved by M.
+
+    The one deliberate difference: the reference moves the sweep by M once (apply_transform), hands the moved points to Open3D, and
+    Open3D accumulates its updates on those moved points.  Here the device call gets init = M and the RAW float32 rows, and moves them
+    by the accumulated float64 transform T in every round; T_icp = T M^-1 is recovered on the host in float64.  The same algebra, one
+    rounding of the moved points less."""
+    from .. import icp as _icp
+    todo = [(int(d), int(t0), int(t1)) for d, t0, t1 in pairs if not os.path.exists(cache_file(root, int(d), int(t0), int(t1), icp_dir))]
+    todo = list(dict.fromkeys(todo))
+    for a in range(0, len(todo), max(int(batch), 1)):
+        part = todo[a:a + max(int(batch), 1)]
+        sweeps = [read_pair(root, d, t0, t1) for d, t0, t1 in part]
+        M = np.stack([odometry_transform(root, d, t0, t1) for d, t0, t1 in part])
+        src = np.concatenate([np.ascontiguousarray(s[0], np.float32).reshape(-1, 3) for s in sweeps])
+        tgt = np.concatenate([np.ascontiguousarray(s[1], np.float32).reshape(-1, 3) for s in sweeps])
+        res = _icp.icp_pairs(src, [len(s[0]) for s in sweeps], tgt, [len(s[1]) for s in sweeps], init=M, check_every=check_every,
+                             **_icp.ICP_KITTI)
+        T = np.asarray(res.transformation, np.float64)
+        for (d, t0, t1), Mi, Ti in zip(part, M, T):
+            T_icp = Ti @ np.linalg.inv(Mi)
+            path = cache_file(root, d, t0, t1, icp_dir)
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            np.save(path, Mi @ T_icp)
+    return len(todo)
+
+
+def pair_transform(root, drive, t0, t1, icp_dir=None, odometry_gt=False, refine=False):
+    """Ground truth of a test pair, source (t0) -> target (t1), f64[4,4] (KITTI.py:283-310): <icp_dir>/<drive>_<t0>_<t1>.npy when it
+    exists -- the ICP-refined cache, the reference's or refine_pairs'.  Without it: FileNotFoundError naming the file, unless
+    refine=True computes and caches it (refine_pairs; needs the GPU), or odometry_gt=True asks for the unrefined odometry transform
+    (:288-289), which is never written to the cache.  A missing cache never silently changes the metric."""
+    path = cache_file(root, drive, t0, t1, icp_dir)
+    if not os.path.exists(path) and refine:
+        refine_pairs(root, [(drive, t0, t1)], icp_dir=icp_dir)
     if os.path.exists(path):
         M = np.load(path)
         if M.shape != (4, 4):
             raise ValueError("%s: a transform of shape %s" % (path, M.shape))
         return M
     if not odometry_gt:
-        raise FileNotFoundError("%s: no ICP-refined ground truth for pair (%d, %d, %d); ICP refinement is not built here -- copy the "
-                                "reference's cache, or pass odometry_gt=True for the unrefined odometry" % (path, drive, t0, t1))
+        raise FileNotFoundError("%s: no ICP-refined ground truth for pair (%d, %d, %d) -- copy the reference's cache, compute it with "
+                                "refine=True (tools/kitti_icp.py), or pass odometry_gt=True for the unrefined odometry"
+                                % (path, drive, t0, t1))
     return odometry_transform(root, drive, t0, t1)
 
 

@@ -756,6 +756,56 @@ int d3f_validation_pairs(const float* desc, int ldd, int C, const float* score, 
 int d3f_pose_errors(const float* T_est, const float* gt, int P, int per_pair, const double* thresholds_host, double* rte_dev,
                     double* rre_deg_dev, int* flags_dev, double* meters_dev, void* stream);
 
+/* Point-to-point ICP of B (source, target) pairs, run to convergence on the device (datasets/KITTI.py:293-297 of the reference refines
+ * the KITTI ground truth with it).  THE DEFINITION is Open3D's registration_icp with TransformationEstimationPointToPoint(False) and
+ * ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration), restated here; tests/icp_np.py is this text in numpy, and
+ * what the tests pin is this text, not Open3D's bits.
+ *   grid: built by d3f_neighbor_grid_build over the N_tgt stacked rows of the B target clouds (s_lens_dev = their lengths) with a
+ *     radius >= max_correspondence_distance.  (Any built grid gives the same result: the kernel derives the stencil from the grid's
+ *     own cell edge; a radius below the distance only widens the stencil and costs time.)
+ *   src f32[N_src, 3]: the stacked source rows; src_lens_dev i32[B] on the device (a length that runs past N_src is cut there, a
+ *     negative one is 0).  Pair p is source cloud p against target cloud p.  init f64[B, 12] on the device: row-major [R | t] of T_0.
+ *   criteria_host: THREE doubles on the host, [max_correspondence_distance r, relative_fitness, relative_rmse], read before the call returns.
+ * Per pair, with Ns source rows s_i, T_0 = init and k = 0, 1, ..., everything in float64 with every operation rounded on its own:
+ *   move      p_i = ((R[r,0] x + R[r,1] y) + R[r,2] z) + t[r] for r = 0, 1, 2, (x, y, z) = s_i widened f32 -> f64, [R | t] = T_k
+ *             (the convention of d3f_repeatability_pairs' moved keypoints, in float64);
+ *   search    the nearest row of the pair's target cloud by d2 = (dx dx + dy dy) + dz dz, dx = p_i - x widened, among those with
+ *             d2 < r r STRICTLY (r r the rounded float64 product); equal d2: the lowest target index.  n_k = the rows that have one.
+ *   figures   fitness_k = n_k / Ns (0 for Ns = 0), rmse_k = sqrt(sum d2 / n_k) (0 for n_k = 0).
+ *   stop      at k with T_k if k >= 1 and |fitness_k - fitness_{k-1}| < relative_fitness and |rmse_k - rmse_{k-1}| < relative_rmse:
+ *             converged = 1; otherwise if k == max_iteration: converged = 0.  iterations = k, the updates applied (Open3D's loop count).
+ *   update    otherwise T_{k+1} = U_k T_k, each entry ((u0 m0 + u1 m1) + u2 m2), the translation column + t_U last.  U_k = [R_U | t_U]
+ *             is the rigid fit without scaling of the pairs (p_i -> its target row x_i): mp = (sum p) / n_k, mt = (sum x) / n_k,
+ *             S[a][b] = (sum p_a x_b) - (sum p_a) mt[b], R_U = the rotation of Horn's quaternion method on S (the largest eigenvector
+ *             of the 4 x 4 matrix N(S) by 12 cyclic Jacobi sweeps, as the RANSAC fit of d3f_ransac_hypotheses),
+ *             t_U[a] = mt[a] - ((R_U[a,0] mp[0] + R_U[a,1] mp[1]) + R_U[a,2] mp[2]).  n_k = 0: U_k is the identity and T_{k+1} has T_k's bits.
+ *   At most max_iteration + 1 searches run per pair.
+ * THE SUMMATION ORDER IS PART OF THE DEFINITION.  The 16 sums are sum d2 | sum p (3) | sum x (3) | sum p_a x_b (a outer; rounded
+ * products); a row without a correspondence adds +0.0 to each.  Chunk c of a pair = its rows 256 c .. 256 c + 255 in original
+ * numbering (the last one padded with +0.0).  Inside a chunk: each group of 64 consecutive rows by the halving tree s = 32, 16, .. 1
+ * (v[t] += v[t + s] for t < s), then (g0 + g1) + (g2 + g3) over the four groups.  Over the chunks of the pair: 256 partial sums,
+ * partial t adding the chunks c = t, t + 256, ... in ascending order from 0.0, then s = 128, 64, .. 1: partial[t] += partial[t + s]
+ * for t < s.  No floating-point atomics: nothing depends on an order of arrival.
+ * Outputs, all on the device and OVERWRITTEN: T f64[B, 12] = T_k at the stop; count i32[B] = n_k, sumd2 f64[B], fitness f64[B],
+ *   rmse f64[B] -- the figures of the last search, the one under the returned T; iterations i32[B]; converged i32[B]; nearest
+ *   (optional) i32[N_src]: per source row the index INSIDE the pair's target cloud of its correspondence under the returned T, -1:
+ *   none (rows past the sum of the lengths are not written).
+ * Launches: one to initialise, then per round a search over the rows of every unfinished pair and a one-workgroup-per-pair finish
+ *   (sums, stop test, fit, T_{k+1}); both return at once for a finished pair.  No persistent kernel, no grid-wide sync, no workgroup
+ *   waits for another.  check_every = n > 0: after every n rounds the host reads the number of unfinished pairs (one more launch, one
+ *   4-byte copy, one stream synchronisation) and stops enqueueing when it is 0.  check_every = 0: exactly max_iteration + 1 rounds
+ *   are enqueued with no read-back, no allocation and no memset -- capturable in a HIP graph.  Both forms give the same bits.
+ * workspace >= d3f_icp_pairs_workspace_bytes(N_src, B) (132 bytes per 256 source rows, plus the per-pair words), else
+ * D3F_ERR_WORKSPACE; so is a grid_bytes below d3f_neighbor_grid_bytes(N_tgt, B).  The size function returns 0 for sizes the call refuses.
+ * D3F_ERR_ARG before anything touches the device: a negative size, B outside 1 .. D3F_MAX_BATCH, max_iteration < 0, check_every < 0,
+ * r not positive and finite (NaN too), a NaN criterion, a NULL pointer other than nearest (src may be NULL when N_src == 0).
+ * Asynchronous on `stream` apart from the read-backs of check_every > 0; no allocation. */
+size_t d3f_icp_pairs_workspace_bytes(int N_src, int B);
+int d3f_icp_pairs(const void* grid, size_t grid_bytes, int N_tgt, const float* src, int N_src, const int* src_lens_dev, int B,
+                  const double* init, const double* criteria_host, int max_iteration, int check_every, double* T, int* count,
+                  double* sumd2, double* fitness, double* rmse, int* iterations, int* converged, int* nearest, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
