@@ -21,6 +21,7 @@ PAIRS_KMAX = 1024
 REPEAT_COUNTS_MAX = 16
 MATCH_KMAX = 8192
 VALIDATION_NMAX = 1024
+SCENES_MAX = 256
 VP_INDEX_RANGE, VP_COUNT_RANGE = 1, 2           # status of a pair of d3f_validation_pairs
 
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
@@ -97,6 +98,8 @@ SIGNATURES = {
     "d3f_validation_pairs": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _f, _f, _f, _f] + [_vp] * 5
                              + [_sz, _vp]),
     "d3f_pose_errors": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "d3f_sanitize_descriptors": (_i, [_vp, _i, _i, _i, _i, _vp]),
+    "d3f_matching_summary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "d3f_icp_pairs_workspace_bytes": (_sz, [_i, _i]),
     "d3f_icp_pairs": (_i, [_vp, _sz, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i] + [_vp] * 9 + [_sz, _vp]),
     "d3f_gemm_pack_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -767,3 +767,8 @@ extern "C" int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int
 // KITTI test metric (RTE, RRE, success, the running meters) of every estimate in two launches (d3f_pose_errors)
 // ---------------------------------------------------------------------------------------------------------------------
 #include "rp_pose_errors.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// ETH test: np.nan_to_num of the descriptors and the per-scene matching summary (d3f_sanitize_descriptors, d3f_matching_summary)
+// ---------------------------------------------------------------------------------------------------------------------
+#include "rp_scene_summary.h"

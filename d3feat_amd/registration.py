@@ -18,6 +18,10 @@
     pose_errors(T, gt)                      the KITTI test metric (RTE, RRE, success, the running meters) of every estimate in two
                                             launches (utils/tester.py:326-344; float64); register_kitti_pairs(kp, count, gt, voxel)
                                             is register_pairs + pose_errors as ModelTester.test_kitti pairs them (:292-344)
+    sanitize_descriptors(kp)                np.nan_to_num of the descriptor columns, in place (evaluate_eth.py:26-27)
+    matching_summary(matching, gt_flag, scene_start) recall, average inliers and average inlier ratio of every scene at every count
+                                            in two launches (evaluate.py:200-219, evaluate_eth.py:142-177); match_scenes(...) is
+                                            sanitize_descriptors + match_pairs + matching_summary, the ETH test in one call
 
 Every computation is a kernel of libd3feat_amd.so (csrc/registration.hip, csrc/radius_neighbors.hip); numpy / torch only
 move data and run the host loop over batches of hypotheses.  Open3D's own random stream is unspecified, so results are
@@ -731,3 +735,157 @@ def register_kitti_pairs(kp, count, gt, voxel_size, seed=0, out=None):
     reg = register_pairs(kp, count, pairs, seed=seed, out=out.registration if out is not None else None, **EVALUATE_KITTI(voxel_size))
     err = pose_errors(reg.T, gt, out=out.errors if out is not None else None, **KITTI_SUCCESS)
     return out if out is not None else KittiRegistration(reg, err, pairs)
+
+
+# ---- the ETH test: every scene's matching recall in one call (geometric_registration_eth/evaluate_eth.py) -----------------------------
+EVALUATE_ETH = dict(num_keypts=(250,), distance_threshold=0.10, inlier_ratio=0.05)     # evaluate_eth.py:29,123-124
+
+
+def sanitize_descriptors(kp):
+    """np.nan_to_num on the descriptor columns of kp f32[n_blocks, K, 4 + C] (device, contiguous, C in 16 / 32 / 64), IN PLACE
+    (evaluate_eth.py:26-27): NaN -> +0.0, +inf -> FLT_MAX, -inf -> -FLT_MAX, every other bit pattern kept.  The xyz and score columns
+    are not touched.  One launch; a second call changes nothing.  -> kp."""
+    lib = _lib.load()
+    kp = ops._req(kp, torch.float32, "kp", 3)
+    n_blocks, K, ld = kp.shape
+    if not kp.is_contiguous() or ld - 4 not in (16, 32, 64):
+        raise ValueError("sanitize_descriptors: kp %s (contiguous, descriptors of 16, 32 or 64 floats)" % (tuple(kp.shape),))
+    if n_blocks * K:
+        _lib.check(lib.d3f_sanitize_descriptors(kp.data_ptr(), n_blocks, K, ld, ld - 4, ops._stream(kp.device)), "sanitize_descriptors")
+    return kp
+
+
+class SceneMatching:
+    """Result of matching_summary: DEVICE tensors ratio_e8 i32[P, n] (per pair and count the inlier ratio at the 8 decimals of the
+    reference's result file, times 1e8; 0 for a pair gt.log does not list) and figures i64[S, n, 4] (per scene and count: ground-truth
+    pairs, pairs above inlier_ratio, sum of gt_inliers and sum of ratio_e8 over the ground-truth pairs).  .scenes(), .overall() and
+    .rows(c) share one read-back."""
+
+    def __init__(self, P, n, scene_start, inlier_ratio, device):
+        self.P, self.n, self.scene_start, self.inlier_ratio = P, n, tuple(int(v) for v in scene_start), float(inlier_ratio)
+        self.S = len(self.scene_start) - 1
+        self.ratio_e8 = torch.empty((P, n), dtype=torch.int32, device=device)
+        self.figures = torch.empty((self.S, n, 4), dtype=torch.int64, device=device)
+        self.gt_inliers = self.gt_flag = None                   # the inputs of the call, kept for the read-back
+
+    _cache = None
+
+    def host(self):
+        """One read-back of the whole result, kept until the next matching_summary(out=self): dict of numpy arrays ratio_e8 [P, n],
+        figures [S, n, 4], gt_inliers [P, n] and gt_flag [P]."""
+        if self._cache is None:
+            self._cache = dict(ratio_e8=self.ratio_e8.cpu().numpy(), figures=self.figures.cpu().numpy(),
+                               gt_inliers=self.gt_inliers.cpu().numpy().reshape(self.P, self.n), gt_flag=self.gt_flag.cpu().numpy())
+        return self._cache
+
+    def scenes(self):
+        """[scene][count] -> dict(correct, gt, recall, ave_num_inliers, ave_inlier_ratio): the keys and conventions of
+        results.feature_matching_recall (the averages divide the sums over the ground-truth pairs by `correct`; 0.0 where the
+        reference would divide by zero).  correct, gt and the inlier sum are the integers of `figures`.  The reference adds the
+        ratios as float64 in numpy's order, which an integer sum cannot give back bit for bit, so ave_inlier_ratio is np.sum over the
+        read-back ratio_e8 / 1e8 column of the scene -- the reference's own expression on the same numbers; figures[..., 3] / 1e8 is
+        the same sum without a rounding error."""
+        h = self.host()
+        out = []
+        for s in range(self.S):
+            sl, per_count = slice(self.scene_start[s], self.scene_start[s + 1]), []
+            flag = h["gt_flag"][sl] != 0
+            for c in range(self.n):
+                gt, correct, inl = (int(v) for v in h["figures"][s, c, :3])
+                ratio = h["ratio_e8"][sl, c] / 1e8
+                div = lambda a: float(a / correct) if correct else 0.0
+                per_count.append(dict(correct=correct, gt=gt, recall=float(correct / gt) * 100 if gt else 0.0,
+                                      ave_num_inliers=div(np.float64(inl)),
+                                      ave_inlier_ratio=div(np.sum(np.where(flag, ratio, np.zeros(ratio.shape[0]))))))
+            out.append(per_count)
+        return out
+
+    def overall(self, c=0):
+        """The closing figures of evaluate_eth.py:168-177 at count c: dict(recall_list, matching_recall = all correct / all
+        ground-truth pairs in percent, average_recall, average_inliers, average_inliers_ratio = the means over the scenes)."""
+        sc = [per_count[c] for per_count in self.scenes()]
+        pred, gt = sum(r["correct"] for r in sc), sum(r["gt"] for r in sc)
+        mean = lambda key: sum(r[key] for r in sc) / len(sc) if sc else 0.0
+        return dict(recall_list=[r["recall"] for r in sc], matching_recall=pred / gt * 100 if gt else 0.0,
+                    average_recall=mean("recall"), average_inliers=mean("ave_num_inliers"), average_inliers_ratio=mean("ave_inlier_ratio"))
+
+    def rows(self, c=0):
+        """The rows [num_inliers, inlier_ratio, gt_flag] of count c as evaluate_eth.py:150-151 reads them back, one per pair."""
+        h = self.host()
+        return [[int(i) if g else 0, float(m / 1e8), int(g != 0)] for i, m, g in zip(h["gt_inliers"][:, c], h["ratio_e8"][:, c], h["gt_flag"])]
+
+
+def matching_summary(mutual_count, gt_inliers=None, gt_flag=None, scene_start=None, inlier_ratio=0.05, out=None):
+    """The per-scene summary of evaluate.py:200-219 / evaluate_eth.py:142-177 on the device: mutual_count / gt_inliers i32[P, n]
+    (match_pairs' tensors; or a PairMatching in place of the two: matching_summary(matching, gt_flag, scene_start)), gt_flag i32[P]
+    device (1 where gt.log lists the pair), scene_start: S + 1 ascending host ints from 0 to P, scene s owning the pairs
+    scene_start[s] .. scene_start[s + 1] - 1 (S <= 256).  Per pair and count the ratio gt_inliers / mutual_count rounded to the 8
+    decimals of the reference's result file, as an integer (0 without a mutual match: PairMatching.ratios' convention; the reference
+    would divide by zero); per scene and count four integer sums.  Two launches, no read-back (capturable: pass the previous result
+    as `out`).  -> SceneMatching (device tensors; .scenes(), .overall(), .rows(c))."""
+    lib = _lib.load()
+    if isinstance(mutual_count, PairMatching):
+        if scene_start is None:
+            gt_inliers, gt_flag, scene_start = None, gt_inliers, gt_flag
+        elif gt_inliers is not None:
+            raise ValueError("matching_summary: a PairMatching brings its own gt_inliers")
+        matching = mutual_count
+        if matching.gt_inliers is None:
+            raise ValueError("matching_summary: match_pairs was called without gt")
+        mutual_count, gt_inliers = matching.mutual_count, matching.gt_inliers
+    mutual_count = ops._req(mutual_count, torch.int32, "mutual_count")
+    gt_inliers = ops._req(gt_inliers, torch.int32, "gt_inliers")
+    gt_flag = ops._req(gt_flag, torch.int32, "gt_flag", 1)
+    if mutual_count.dim() == 1:
+        mutual_count, gt_inliers = mutual_count.reshape(-1, 1), gt_inliers.reshape(-1, 1)
+    P, n = mutual_count.shape[0], mutual_count.shape[1] if mutual_count.dim() == 2 else 0
+    if (mutual_count.dim() != 2 or mutual_count.shape != gt_inliers.shape or gt_flag.shape[0] != P or not 1 <= n <= _lib.REPEAT_COUNTS_MAX
+            or not (mutual_count.is_contiguous() and gt_inliers.is_contiguous() and gt_flag.is_contiguous())):
+        raise ValueError("matching_summary: mutual_count %s, gt_inliers %s, gt_flag %s (contiguous [P, n], [P, n], [P])"
+                         % (tuple(mutual_count.shape), tuple(gt_inliers.shape), tuple(gt_flag.shape)))
+    starts = [int(v) for v in np.asarray(scene_start).reshape(-1)]
+    S = len(starts) - 1
+    if (not 0 <= S <= _lib.SCENES_MAX or starts[0] != 0 or starts[-1] != P or any(b < a for a, b in zip(starts, starts[1:]))):
+        raise ValueError("matching_summary: scene_start %s must hold 1 to %d ascending ints from 0 to P = %d" % (starts, _lib.SCENES_MAX + 1, P))
+    ratio = float(inlier_ratio)
+    if ratio != ratio:
+        raise ValueError("matching_summary: inlier_ratio %r" % (inlier_ratio,))
+    dev = mutual_count.device
+    if out is None:
+        out = SceneMatching(P, n, starts, ratio, dev)
+    elif (not isinstance(out, SceneMatching) or (out.P, out.n, out.scene_start, out.inlier_ratio) != (P, n, tuple(starts), ratio)
+          or out.ratio_e8.device != dev):
+        raise ValueError("matching_summary: out= was made for another call")
+    out._cache = None
+    out.gt_inliers, out.gt_flag = gt_inliers, gt_flag
+    c_starts, c_ratio = (_lib.C.c_int * (S + 1))(*starts), _lib.C.c_double(ratio)
+    ptr = lambda t: t.data_ptr() if t.numel() else None          # (an empty tensor has no address)
+    rc = lib.d3f_matching_summary(ptr(mutual_count), ptr(gt_inliers), ptr(gt_flag), P, n, _lib.C.addressof(c_starts), S,
+                                  _lib.C.addressof(c_ratio), ptr(out.ratio_e8), ptr(out.figures), ops._stream(dev))
+    _lib.check(rc, "matching_summary")
+    return out
+
+
+class SceneMatches:
+    """Result of match_scenes: `matching` (PairMatching of match_pairs) and `summary` (SceneMatching of matching_summary), both device
+    tensors."""
+
+    def __init__(self, matching, summary):
+        self.matching, self.summary = matching, summary
+
+
+def match_scenes(kp, count, pairs, gt, gt_flag, scene_start, num_keypts=EVALUATE_ETH["num_keypts"],
+                 distance_threshold=EVALUATE_ETH["distance_threshold"], inlier_ratio=EVALUATE_ETH["inlier_ratio"], nan_to_num=True, out=None):
+    """geometric_registration_eth/evaluate_eth.py for every pair of every scene in one call: kp f32[n_blocks, K, 4 + C] / count the
+    keypoint blocks of ALL scenes (stack_keypoints), pairs i32[P, 2] global block indices with the scenes contiguous, gt f32[P, 3, 4]
+    target -> source, gt_flag i32[P], scene_start as matching_summary takes it (datasets.eth.benchmark makes the four).
+    sanitize_descriptors(kp) -- IN PLACE, skipped with nan_to_num=False --, match_pairs and matching_summary, no read-back in between
+    (capturable: pass the previous result as `out`).  -> SceneMatches (.matching, .summary)."""
+    if out is not None and not isinstance(out, SceneMatches):
+        raise ValueError("match_scenes: out= was made for another call")
+    if nan_to_num:
+        sanitize_descriptors(kp)
+    m = match_pairs(kp, count, pairs, gt, num_keypts=num_keypts, distance_threshold=distance_threshold,
+                    out=out.matching if out is not None else None)
+    s = matching_summary(m, gt_flag, scene_start, inlier_ratio=inlier_ratio, out=out.summary if out is not None else None)
+    return out if out is not None else SceneMatches(m, s)

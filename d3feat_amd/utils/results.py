@@ -150,6 +150,25 @@ def matching_table(num_keypts, rows_per_count, inlier_ratio=0.05):
     return lines, table
 
 
+def eth_lines(scene_names, summary, c=0):
+    """The lines geometric_registration_eth/evaluate_eth.py:158-177 prints, in its order and with its wording (its typos too): four per
+    scene, the row of stars, the list of recalls and the four closing figures.  summary: registration.SceneMatching (or anything with
+    its .scenes() / .overall()), one scene per name; c: the column of the keypoint count (the script has one, 250)."""
+    scenes = summary.scenes()
+    if len(scene_names) != len(scenes):
+        raise ValueError("eth_lines: %d names, %d scenes" % (len(scene_names), len(scenes)))
+    lines = []
+    for per_count in scenes:
+        r = per_count[c]
+        lines += [f"Correct Match {r['correct']}, ground truth Match {r['gt']}", f"Recall {r['recall']}%",
+                  f"Average Num Inliners: {r['ave_num_inliers']}", f"Average Num Inliner Ratio: {r['ave_inlier_ratio']}"]
+    o = summary.overall(c)
+    lines += ["*" * 40, str(o["recall_list"]), f"Avergae Matching Recall: {o['matching_recall']}%",
+              f"All 8 scene, average recall: {o['average_recall']}%", f"All 8 scene, average num inliers: {o['average_inliers']}",
+              f"All 8 scene, average num inliers ratio: {o['average_inliers_ratio']}"]
+    return lines
+
+
 # ---- the lines of repeatability/evaluate_3dmatch_our.py / evaluate_kitti_our.py -------------------------------------------------
 def repeatability_table(num_keypts, scene_values):
     """The lines both scripts print, one per keypoint count (evaluate_3dmatch_our.py:66, evaluate_kitti_our.py:44), from values

@@ -45,6 +45,7 @@ extern "C" {
 #define D3F_TOPK_MAX 8192        /* most keypoints per cloud d3f_topk_records selects */
 #define D3F_PAIRS_KMAX 1024      /* most rows of one keypoint block d3f_register_pairs uses */
 #define D3F_REPEAT_COUNTS_MAX 16 /* most keypoint counts one d3f_repeatability_pairs / d3f_match_pairs call evaluates */
+#define D3F_SCENES_MAX 256       /* most scenes one d3f_matching_summary call summarises */
 #define D3F_MATCH_KMAX 8192      /* largest keypoint count of d3f_match_pairs (= D3F_TOPK_MAX, the largest block the selection makes) */
 #define D3F_VALIDATION_NMAX 1024 /* most index pairs (keypoint correspondences) of one pair d3f_validation_pairs takes */
 #define D3F_NUM_KP_MAX 16        /* kernel points per KPConv (reference uses 15) */
@@ -755,6 +756,38 @@ int d3f_validation_pairs(const float* desc, int ldd, int C, const float* score, 
  * capturable. */
 int d3f_pose_errors(const float* T_est, const float* gt, int P, int per_pair, const double* thresholds_host, double* rte_dev,
                     double* rre_deg_dev, int* flags_dev, double* meters_dev, void* stream);
+
+/* np.nan_to_num of the descriptors of keypoint blocks, in place (geometric_registration_eth/evaluate_eth.py:26-27 of the reference pass
+ * the descriptors through it before matching; d3f_match_pairs alone never matches a row that holds a NaN, which is not the same for a
+ * row with one bad component).  kp f32[n_blocks, K, ld] on the device, rows [xyz | C descriptor floats | ...]; on the columns
+ * 3 .. 3 + C - 1 of every row of every block:
+ *     NaN (either sign, any payload) -> +0.0;  +inf -> FLT_MAX;  -inf -> -FLT_MAX;  every other bit pattern, -0.0 and denormals
+ *     included, is left as it is (only an element that changes is written).
+ * The xyz columns, the score and any further column are never read or written, whatever they hold.  One launch, one thread per
+ * element, every element has one writer; a second call changes nothing.  C in {16, 32, 64}, ld >= C + 3, else D3F_ERR_ARG; so are
+ * negative sizes and a NULL kp with n_blocks * K > 0.  n_blocks * K == 0 is D3F_OK.  Asynchronous on `stream`, capturable. */
+int d3f_sanitize_descriptors(float* kp, int n_blocks, int K, int ld, int C, void* stream);
+
+/* Per-scene summary of the feature-matching figures of d3f_match_pairs: what geometric_registration/evaluate.py:200-219 and
+ * geometric_registration_eth/evaluate_eth.py:142-177 of the reference compute from the .rt.txt rows of a scene, for S scenes and n
+ * keypoint counts at once.  mutual_count i32[P, n], gt_inliers i32[P, n] (d3f_match_pairs' outputs), gt_flag i32[P] (1 where gt.log
+ * lists the pair), all on the device; scene s owns the pairs scene_start_host[s] .. scene_start_host[s + 1] - 1 (S + 1 ints on the
+ * HOST, read before the call returns); inlier_ratio_host: one double on the host (0.05 in both scripts).
+ * ratio_e8 i32[P, n]: per pair and count the integer m with m / 1e8 == float("%.8f" % (a / b)), a = gt_inliers, b = mutual_count --
+ *   the inlier ratio as the reference reads it back from the 8 decimals of its result file -- computed in integers:
+ *   m = floor((2 a 10^8 + b) / (2 b)); where a 10^8 / b is exactly a half-integer (only possible when 512 divides b) the decimal
+ *   conversion rounds the double fl(a / b), not the rational: with e = fma(fl(a / b), b, -a), which is exact, e > 0 rounds up, e < 0
+ *   down, e == 0 to the even integer.  a is clamped to 0 .. b.  b == 0 gives m = 0: the convention of this library's Python layer
+ *   (PairMatching.ratios); the reference would divide by zero there.  A pair with gt_flag == 0 gets m = 0 (evaluate_eth.py:43-47).
+ * figures i64[S, n, 4], per scene and count: [0] the pairs with gt_flag != 0; [1] the pairs, flagged or not, with
+ *   fl(m / 1e8) > inlier_ratio (division and comparison in float64, evaluate_eth.py:154); [2] the sum of gt_inliers and [3] the sum
+ *   of m over the pairs with gt_flag != 0.  All integers: no summation order enters.  An empty scene gives four zeros.
+ * Two launches (one thread per (pair, count); one workgroup per (scene, count)), no atomics, no memset, no workspace, no allocation,
+ * no synchronisation: capturable.  D3F_ERR_ARG before anything touches the device: P < 0, n outside 1 .. D3F_REPEAT_COUNTS_MAX,
+ * P * n >= 2^31, S outside 0 .. D3F_SCENES_MAX, scene_start_host not ascending from 0 or scene_start_host[S] != P, a NaN
+ * inlier_ratio, a NULL pointer that is needed (the device inputs and ratio_e8 when P > 0, figures when S > 0).  P == 0 is legal. */
+int d3f_matching_summary(const int* mutual_count, const int* gt_inliers, const int* gt_flag, int P, int n, const int* scene_start_host,
+                         int S, const double* inlier_ratio_host, int* ratio_e8, long long* figures, void* stream);
 
 /* Point-to-point ICP of B (source, target) pairs, run to convergence on the device (datasets/KITTI.py:293-297 of the reference refines
  * the KITTI ground truth with it).  THE DEFINITION is Open3D's registration_icp with TransformationEstimationPointToPoint(False) and
