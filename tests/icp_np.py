@@ -4,7 +4,8 @@ device's bits), and the rigid fit by rg_horn's formulation through numpy.linalg.
 the one step whose bits differ from the device's (LAPACK against 12 Jacobi sweeps): the transform is compared within a tolerance, and
 the margins recorded here say that such a last-bit difference cannot flip a correspondence or the stop test.
 
-Not a test module (no test_ prefix); imported by tests/test_icp_host.py, tests/test_gpu_icp.py and tools/make_golden_icp.py.
+Not a test module (no test_ prefix); imported by tests/test_icp_host.py, tests/test_gpu_icp.py, tests/test_gpu_icp_branches.py,
+tools/make_golden_icp.py and tools/icp_bench.py.
 """
 import contextlib
 import os
@@ -51,17 +52,31 @@ def nearest_brute(p, tgt, r):
 
 
 def nearest_ckdtree(p, tgt, r):
-    """The same correspondences through scipy's k-d tree (the bench's host comparison): the tree proposes, the header's d2 decides."""
+    """The same correspondences through scipy's k-d tree (the bench's host comparison, and the only search that is affordable at sweep
+    size): the tree proposes its two nearest targets, the header's d2 decides between them -- among equal d2 the lower index, as
+    nearest_brute.  The margins: margin_nn = the smallest (second d2 - first d2) over matched rows, the same number nearest_brute
+    gives as long as the tree's two proposals are the two nearest by the header's d2 (they can only fail to be where the margin is
+    within rounding of 0 anyway); margin_r = the smallest |d2 of the nearest - r r| over ALL rows: only the nearest target of a row can
+    change whether the row counts, so this is never below nearest_brute's minimum over every couple."""
     from scipy.spatial import cKDTree
     t = np.asarray(tgt, np.float32).reshape(-1, 3).astype(np.float64)
     n = p.shape[0]
     if n == 0 or t.shape[0] == 0:
         return np.full(n, -1, np.int64), np.zeros(n), np.inf, np.inf
-    _, j = cKDTree(t).query(p, k=1)
-    d = p - t[j]
-    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-    ok = d2 < np.float64(r) * np.float64(r)
-    return np.where(ok, j, -1), np.where(ok, d2, 0.0), np.inf, np.inf
+    k = min(2, t.shape[0])
+    _, j = cKDTree(t).query(p, k=k)
+    j = np.asarray(j).reshape(n, k)
+    d = p[:, None, :] - t[j]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    if k == 2:
+        swap = (d2[:, 1] < d2[:, 0]) | ((d2[:, 1] == d2[:, 0]) & (j[:, 1] < j[:, 0]))
+        j = np.where(swap[:, None], j[:, ::-1], j)
+        d2 = np.where(swap[:, None], d2[:, ::-1], d2)
+    r2 = np.float64(r) * np.float64(r)
+    ok = d2[:, 0] < r2
+    gap_nn = float(np.min((d2[:, 1] - d2[:, 0])[ok])) if k == 2 and ok.any() else np.inf
+    gap_r = float(np.min(np.abs(d2[:, 0] - r2)))
+    return np.where(ok, j[:, 0], -1), np.where(ok, d2[:, 0], 0.0), gap_nn, gap_r
 
 
 def _halve(x, s0):

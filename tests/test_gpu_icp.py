@@ -20,11 +20,10 @@ import torch
 
 import icp_np
 from conftest import GOLDEN, ROOT
+from icp_cases import H, R, branch_pairs as _branch_pairs, single_pass_pairs as _single_pass_pairs      # the input builders
 
 pytestmark = pytest.mark.gpu
 
-R = 0.125                                   # r and r r are exact in binary: d2 == r r can be hit on purpose
-H = R * (1.0 + 2.0 ** -20)                  # the grid's cell edge for that radius (nb_prep)
 KITTI = dict(max_correspondence_distance=0.2, max_iteration=200, relative_fitness=1e-6, relative_rmse=1e-6)
 OUT = ("T", "count", "sumd2", "fitness", "rmse", "iterations", "converged", "nearest")
 
@@ -32,16 +31,6 @@ OUT = ("T", "count", "sumd2", "fitness", "rmse", "iterations", "converged", "nea
 @pytest.fixture(scope="module")
 def gold():
     return np.load(os.path.join(GOLDEN, "icp.npz"))
-
-
-def _rigid(deg, axis, shift):
-    axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    a = np.deg2rad(deg)
-    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-    T = np.eye(4)
-    T[:3, :3] = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K
-    T[:3, 3] = shift
-    return T
 
 
 def _run(device, pairs, **kw):
@@ -70,35 +59,6 @@ def _check_exact_part(h, p, off, want):
 
 
 # ---- 1. a single search --------------------------------------------------------------------------------------------------------------------
-def _single_pass_pairs():
-    rng = np.random.default_rng(17)
-    f32 = np.float32
-    pairs = []
-    pairs.append((np.zeros((0, 3), f32), np.array([[1.0, 2.0, 3.0]], f32), None))                          # 0 rows against 1
-    pairs.append((np.zeros((1, 3), f32), np.array([[R, 0.0, 0.0]], f32), None))                            # 1 row, d2 == r r: excluded
-    # 257 rows: 250 random ones, then  [250] three targets at equal d2 (the lowest index wins, and it is not the first in the stack),
-    # [251] a target at exactly the radius (excluded, the next one is farther), [252..256] queries far outside the box of the targets
-    src = np.concatenate([rng.uniform(0, 1, (250, 3)), [[3.0, 0.5, 0.5], [3.0, 2.0, 0.5]],
-                          [[50, 50, 50], [-40, 0.5, 0.5], [0.5, -3.0, 0.5], [0.5, 0.5, 9.0], [1e6, -1e6, 1e6]]]).astype(f32)
-    tgt = np.concatenate([[[0.0, 0.0, 0.0]], rng.uniform(0, 1, (292, 3)),
-                          [[3.0, 0.5625, 0.5], [3.0625, 0.5, 0.5], [2.9375, 0.5, 0.5], [3.0, 0.5, 0.4375]],
-                          [[3.0 + R, 2.0, 0.5], [3.0, 2.1875, 0.5]], [[0.5, 0.5, 0.5]]]).astype(f32)
-    pairs.append((src, tgt, None))
-    # 700 rows moved by a pure shift so that row 699 lands EXACTLY on the cell boundary x = 3 h (0.25 + t_x in float64, the box of the
-    # targets starts at 0); its only correspondence is a radius (less a hair) below, just above the low edge of the neighbouring cell 2.
-    # Row 698 the same one cell up, its correspondence a radius (less a hair) above.
-    shift = np.eye(4)
-    shift[0, 3] = R + 3 * R * 2.0 ** -20
-    lo = np.nextafter(np.nextafter(f32(3 * H - R), f32(9)), f32(9))                        # two float32 steps inside the radius
-    hi = np.nextafter(np.nextafter(f32((0.25 + R) + shift[0, 3] + R), f32(-9)), f32(-9))
-    src = np.concatenate([rng.uniform(0, 1, (698, 3)), [[0.25 + R, 0.5, 2.5], [0.25, 0.5, 2.5]]]).astype(f32)
-    tgt = np.concatenate([[[0.0, 0.0, 0.0]], rng.uniform(0, 1, (600, 3)), [[lo, 0.5, 2.5]], [[hi, 0.5, 3.5]]]).astype(f32)
-    src[698] = [0.25 + R, 0.5, 3.5]
-    pairs.append((src, tgt, shift))
-    pairs.append((rng.uniform(0, 1, (300, 3)).astype(f32), rng.uniform(0, 1, (900, 3)).astype(f32), _rigid(5.0, (1, 2, 3), (0.02, -0.01, 0.03))))
-    return pairs
-
-
 def test_single_search(device):
     pairs = _single_pass_pairs()
     assert [len(p[0]) for p in pairs] == [0, 1, 257, 700, 300] and [len(p[1]) for p in pairs] == [1, 1, 300, 603, 900]
@@ -147,18 +107,6 @@ def test_whole_loop_on_the_golden_pair(device, gold):
 
 
 # ---- 3. the branches -----------------------------------------------------------------------------------------------------------------------
-def _branch_pairs(gold):
-    rng = np.random.default_rng(23)
-    cloud = rng.uniform(0, 2, (500, 3)).astype(np.float32)
-    single_src = np.array([[0, 0, 0], [5, 0, 0], [0, 5, 0]], np.float32)
-    single_tgt = np.array([[9, 9, 9], [5.05, 0.02, -0.03], [-7, 0, 0]], np.float32)
-    return [(gold["src"], gold["tgt"], None),                                          # the golden pair
-            (cloud, cloud.copy(), None),                                               # identical clouds: converged at k = 1
-            (np.zeros((0, 3), np.float32), cloud[:50], None),                          # an empty source
-            (cloud[:300], cloud[:300] + np.float32(10.0), None),                       # 10 m apart: no correspondence at all
-            (single_src, single_tgt, None)]                                            # one correspondence: a pure shift
-
-
 def _check_branch(h, p, off, pair, **kw):
     w = icp_np.icp(pair[0], pair[1], pair[2], **kw)
     _check_exact_part(h, p, off, w)

@@ -1,5 +1,6 @@
-"""ICP refinement without a GPU: the float64 restatement (tests/icp_np.py) on its own, the margins of tests/golden/icp.npz
-(tools/make_golden_icp.py), d3f_icp_pairs' argument checks, the cache files of d3feat_amd/datasets/kitti.py with the device call
+"""ICP refinement without a GPU: the float64 restatement (tests/icp_np.py) on its own (the summation order spelled out at 3 and at 258
+chunks, the k-d tree search and its margins against the brute-force one), the margins of tests/golden/icp.npz and of
+tests/golden/icp_sweep.npz (tools/make_golden_icp.py) and the inputs the latter is regenerated from, d3f_icp_pairs' argument checks, the cache files of d3feat_amd/datasets/kitti.py with the device call
 replaced by the restatement, and the compat entry point's refusals."""
 import ctypes
 import os
@@ -7,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import icp_cases
 import icp_np
 from conftest import GOLDEN, ROOT
 from d3feat_amd.datasets import kitti
@@ -103,7 +105,136 @@ def test_summation_order_is_the_headers():
     assert sm[0] == ((0.0 + chunks[0]) + (0.0 + chunks[2])) + (0.0 + chunks[1])     # partials 0, 1, 2; tree: s = 2 adds [0] += [2], s = 1 [0] += [1]
 
 
-# ---- the fixture -------------------------------------------------------------------------------------------------------------------------
+def test_summation_order_at_258_chunks_restated_literally():
+    """66 000 rows are 258 chunks: partial 0 adds chunks 0 and 256, partial 1 adds 1 and 257, every other partial one chunk.  The
+    header's order in plain loops -- over the chunks, their four groups of 64 rows and the steps of the two trees -- against
+    icp_np.sums, all 16 sums bit for bit (the restatement's own acc[c % 256] is otherwise only checked at 3 chunks)."""
+    rng = np.random.default_rng(258)
+    n = 66000
+    p, tgt = rng.normal(size=(n, 3)) * [40.0, 40.0, 3.0], (rng.normal(size=(500, 3)) * [40.0, 40.0, 3.0]).astype(np.float32)
+    idx = rng.integers(0, 500, n)
+    idx[rng.random(n) < 0.1] = -1                                          # about 10 % of the rows have no correspondence
+    d2 = np.where(idx >= 0, rng.random(n) * 0.04, 0.0)
+    sm, cnt = icp_np.sums(p, tgt, idx, d2)
+    assert cnt == int((idx >= 0).sum()) and 0.88 * n < cnt < 0.92 * n
+    nc = (n + 255) // 256
+    assert nc == 258
+    x = tgt.astype(np.float64)
+    v = np.zeros((nc * 256, 16))                                           # the last chunk padded with +0.0
+    for i in range(n):
+        if idx[i] >= 0:
+            t = x[idx[i]]
+            v[i] = [d2[i], p[i, 0], p[i, 1], p[i, 2], t[0], t[1], t[2], p[i, 0] * t[0], p[i, 0] * t[1], p[i, 0] * t[2],
+                    p[i, 1] * t[0], p[i, 1] * t[1], p[i, 1] * t[2], p[i, 2] * t[0], p[i, 2] * t[1], p[i, 2] * t[2]]
+    part = []
+    for c in range(nc):
+        g = []
+        for w in range(4):
+            lanes = v[256 * c + 64 * w: 256 * c + 64 * w + 64].copy()      # [64 rows, 16 sums]
+            s_ = 32
+            while s_ > 0:
+                for t in range(s_):
+                    lanes[t] = lanes[t] + lanes[t + s_]
+                s_ //= 2
+            g.append(lanes[0])
+        part.append((g[0] + g[1]) + (g[2] + g[3]))
+    red = []
+    for t in range(256):                                                   # thread t: chunks t, t + 256, ... ascending, from 0.0
+        acc = np.zeros(16)
+        for c in range(t, nc, 256):
+            acc = acc + part[c]
+        red.append(acc)
+    assert sum(1 for t in range(256) if len(range(t, nc, 256)) == 2) == 2
+    s_ = 128
+    while s_ > 0:
+        for t in range(s_):
+            red[t] = red[t] + red[t + s_]
+        s_ //= 2
+    assert np.array_equal(red[0], sm)
+    assert np.all(sm[[0, 7, 11, 15]] != 0.0) and abs(sm[0] - d2.sum()) <= 1e-12 * d2.sum()
+
+
+def test_ckdtree_margins_are_the_brute_force_ones():
+    """600 rows against 300 targets: the same indices and d2, the same margin_nn, and a margin_r that is no smaller than the brute
+    one (the nearest target's |d2 - r r| against every couple's)."""
+    pytest.importorskip("scipy.spatial")
+    rng = np.random.default_rng(600)
+    src, tgt = rng.uniform(0, 1, (600, 3)).astype(np.float32), rng.uniform(0, 1, (300, 3)).astype(np.float32)
+    p = icp_np.move(_rigid(2.0, (1, 2, 3), (0.01, -0.02, 0.01))[:3], src)
+    a, b = icp_np.nearest_brute(p, tgt, 0.1), icp_np.nearest_ckdtree(p, tgt, 0.1)
+    assert 0 < (a[0] >= 0).sum() < 600
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    assert np.isfinite(a[2]) and a[2] > 0.0 and b[2] == a[2]
+    assert np.isfinite(b[3]) and b[3] >= a[3] > 0.0
+    # the nearest target's margin itself, from the brute-force matrix of every couple
+    D = icp_np._d2(p, tgt.astype(np.float64))
+    assert b[3] == np.min(np.abs(D.min(axis=1) - 0.1 * 0.1))
+    # equal d2: the lower index, whichever the tree proposes first; a single target: no second one, margin_nn stays inf
+    two = np.array([[0.0, 0.125, 0.0], [0.0, -0.125, 0.0]], np.float32)
+    for t in (two, two[::-1].copy()):
+        idx, d2, gap, _ = icp_np.nearest_ckdtree(np.zeros((1, 3)), t, 0.2)
+        assert idx[0] == 0 and d2[0] == 0.015625 and gap == 0.0
+    idx, d2, gap, gap_r = icp_np.nearest_ckdtree(np.zeros((1, 3)), two[:1], 0.2)
+    assert idx[0] == 0 and gap == np.inf and gap_r == abs(0.015625 - 0.2 * 0.2)
+
+
+# ---- the fixtures ------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def sweep():
+    return np.load(os.path.join(GOLDEN, "icp_sweep.npz"))
+
+
+@pytest.fixture(scope="module")
+def sweep_pairs():
+    return icp_cases.sweep_pairs()
+
+
+def test_sweep_fixture_margins_meet_the_cap(sweep):
+    assert sweep["margins"].shape == (2, 3) and np.all(sweep["margins"] >= MARGIN)
+    assert np.all(sweep["fit_difference"] >= 0.0) and np.all(sweep["fit_difference"] < 1e-12)
+    assert sweep["nearest"].shape == (2, 65984) and sweep["nearest"].dtype == np.int32 and sweep["T"].shape == (2, 4, 4)
+    assert np.all(sweep["converged"] == 1) and np.all(sweep["iterations"] >= 2) and np.all(sweep["iterations"] <= 200)
+    assert np.array_equal(sweep["count"], (sweep["nearest"] >= 0).sum(axis=1)) and np.all(sweep["count"] > 50000)
+    assert os.path.getsize(os.path.join(GOLDEN, "icp_sweep.npz")) < 1000000
+    for k, v in icp_cases.SWEEP.items():
+        assert float(sweep["recipe_" + k]) == float(v), k
+
+
+def test_sweep_fixture_inputs_are_the_regenerated_ones(sweep, sweep_pairs):
+    assert [len(p[0]) for p in sweep_pairs] == list(sweep["src_rows"]) == [65984, 65984]                # 258 chunks each
+    assert [len(p[1]) for p in sweep_pairs] == list(sweep["tgt_rows"]) == [20000, 20000]
+    assert [icp_cases.pair_sha256(p) for p in sweep_pairs] == [str(x) for x in sweep["sha256"]]
+    # the regime the fixture is there for: cells of eight radii, in the batch of two and for a pair alone
+    from d3feat_amd import icp
+    gr = icp.grid_radius(0.2)
+    assert np.array_equal(icp_cases.cell_edge([p[1] for p in sweep_pairs], gr), [8 * gr * (1 + 2.0 ** -20)] * 2)
+    assert np.array_equal(icp_cases.cell_edge([sweep_pairs[1][1]], gr), [8 * gr * (1 + 2.0 ** -20)])
+
+
+def test_sweep_fixture_is_the_restatement(sweep, sweep_pairs):
+    """Pair 0 recomputed (eight rounds of 66 k rows through the k-d tree: about a second)."""
+    pytest.importorskip("scipy.spatial")
+    src, tgt, init = sweep_pairs[0]
+    r = icp_np.icp(src, tgt, init, nearest=icp_np.nearest_ckdtree, **{k[3:]: float(sweep[k]) for k in sweep.files if k.startswith("kw_")})
+    assert np.array_equal(r.T, sweep["T"][0]) and np.array_equal(r.nearest, sweep["nearest"][0])
+    assert (r.count, r.iterations, r.converged) == (int(sweep["count"][0]), int(sweep["iterations"][0]), int(sweep["converged"][0]))
+    assert (r.sumd2, r.fitness, r.rmse) == (float(sweep["sumd2"][0]), float(sweep["fitness"][0]), float(sweep["rmse"][0]))
+    assert np.array_equal([r.margin_nn, r.margin_r, r.margin_stop], sweep["margins"][0])
+
+
+def test_cell_edge_is_the_budget_arithmetic():
+    """icp_cases.cell_edge on cases worked out by hand: 65 536 cells at least, an equal share per element, the edge doubled until the
+    cloud fits."""
+    cube = np.array([[0, 0, 0], [1, 1, 1]], np.float32)
+    h = 0.125 * (1 + 2.0 ** -20)
+    assert np.array_equal(icp_cases.cell_edge([cube], 0.125), [h])                                      # 8^3 cells
+    assert np.array_equal(icp_cases.cell_edge([cube], 0.125 / 4), [h / 4])                              # 32^3 <= 65 536
+    assert np.array_equal(icp_cases.cell_edge([cube], 0.125 / 8), [h / 4])                              # 64^3 does not fit: doubled once
+    assert np.array_equal(icp_cases.cell_edge([cube, cube[:1], cube[:0]], 0.125 / 4), [h / 2, h / 4, 1.0])   # a third of the budget each
+    bad = np.array([[0, 0, 0], [np.inf, 0, 0]], np.float32)
+    assert np.array_equal(icp_cases.cell_edge([cube, bad], 0.125), [h, np.inf])                         # never fits: the one-cell grid
+
+
 def test_fixture_margins_meet_the_cap(gold):
     for tag in ("", "it3_"):
         assert gold[tag + "margins"].shape == (3,) and np.all(gold[tag + "margins"] >= MARGIN), tag

@@ -4,21 +4,34 @@ the margins of that run, and the largest difference of the transform between the
 rg_horn states it, against SVD-Kabsch).
 
     python tools/make_golden_icp.py [--seed 7]
+    python tools/make_golden_icp.py --sweep          (needs scipy)
 
 The golden pair: 2000 source rows on three noisy planes; the target is a permuted copy thinned by 30 %, rotated by about one degree
 and shifted by 0.08 m.  A case whose margin (nearest against second-nearest d2, any d2 against r r, the stop test against its
 thresholds) is below 1e-9 is REFUSED: above it a last-bit difference in T -- Jacobi on the device, LAPACK here -- cannot flip a
 correspondence or the stop test, so both walk the same sequence of rounds.  Open3D is not involved: what the fixture pins is the
 definition of include/d3feat_amd.h.
+
+--sweep writes tests/golden/icp_sweep.npz instead: two pairs at sweep size (tests/icp_cases.py sweep_pairs: tools/icp_bench.py's
+recipe at 66 000 points, 258 chunks of source rows, the target thinned to 20 000 rows over 160 x 160 x 9.6 m, so that the grid's cells
+come out at eight radii) run to convergence by the restatement with scipy's k-d tree as the nearest search.  The clouds are NOT stored:
+the fixture holds the recipe's parameters and a SHA-256 per pair of the bytes of src, tgt and init, which the tests check against the
+inputs they regenerate; then per pair T, count, sumd2, fitness, rmse, iterations, converged, nearest, the three margins and the
+difference between the two fit formulations.  The same refusals apply.  The archive is written with fixed member dates, so that the
+same inputs give the same file byte for byte.
 """
 import argparse
+import io
 import os
 import sys
+import zipfile
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import icp_cases  # noqa: E402
 import icp_np  # noqa: E402
 
 MARGIN = 1e-9
@@ -48,11 +61,56 @@ def golden_pair(seed):
     return src, tgt
 
 
+def save_npz_reproducibly(path, arrays):
+    """numpy.savez_compressed with every member dated 1980-01-01: the bytes depend on the arrays alone."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arrays[name]), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def sweep(out_path):
+    pairs = icp_cases.sweep_pairs()
+    kw = dict(KW, nearest=icp_np.nearest_ckdtree)
+    runs = []
+    for p, (src, tgt, init) in enumerate(pairs):
+        a = icp_np.icp(src, tgt, init, fit="eigh", **kw)
+        b = icp_np.icp(src, tgt, init, fit="svd", **kw)              # a prerequisite: the fit difference, and the same sequence of rounds
+        margins = np.array([a.margin_nn, a.margin_r, a.margin_stop])
+        if not np.all(margins >= MARGIN) or a.iterations != b.iterations or not np.array_equal(a.nearest, b.nearest):
+            raise SystemExit("refused: pair %d, margins %s below %g, or the two fits walk different sequences" % (p, margins, MARGIN))
+        a.margins, a.fit_difference = margins, float(np.max(np.abs(a.T - b.T)))
+        print("pair %d: rows %d / %d iterations %d converged %d count %d fitness %.6f rmse %.3e margins %s fit difference %.3e"
+              % (p, len(src), len(tgt), a.iterations, a.converged, a.count, a.fitness, a.rmse, margins, a.fit_difference))
+        runs.append(a)
+    out = {"recipe_" + k: np.float64(v) if isinstance(v, float) else np.int64(v) for k, v in icp_cases.SWEEP.items()}
+    out.update({"kw_" + k: np.float64(v) for k, v in KW.items()})
+    out["sha256"] = np.array([icp_cases.pair_sha256(p) for p in pairs])
+    out["src_rows"] = np.array([len(p[0]) for p in pairs], np.int64)
+    out["tgt_rows"] = np.array([len(p[1]) for p in pairs], np.int64)
+    out["T"] = np.stack([r.T for r in runs])
+    for k, dt in (("count", np.int64), ("sumd2", np.float64), ("fitness", np.float64), ("rmse", np.float64), ("iterations", np.int64),
+                  ("converged", np.int64), ("fit_difference", np.float64)):
+        out[k] = np.array([getattr(r, k) for r in runs], dt)
+    out["margins"] = np.stack([r.margins for r in runs])
+    out["nearest"] = np.stack([r.nearest.astype(np.int32) for r in runs])
+    save_npz_reproducibly(out_path, out)
+    print("wrote %s (%d bytes)" % (out_path, os.path.getsize(out_path)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "icp.npz"))
+    ap.add_argument("--sweep", action="store_true", help="write tests/golden/icp_sweep.npz, the two pairs at sweep size")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.sweep:
+        return sweep(args.out or os.path.join(ROOT, "tests", "golden", "icp_sweep.npz"))
+    args.out = args.out or os.path.join(ROOT, "tests", "golden", "icp.npz")
     src, tgt = golden_pair(args.seed)
     out = dict(src=src, tgt=tgt, seed=np.int64(args.seed), **{"kw_" + k: np.float64(v) for k, v in KW.items()})
     for tag, kw in (("", KW), ("it3_", dict(KW, max_iteration=3))):
