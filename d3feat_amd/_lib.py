@@ -100,6 +100,7 @@ SIGNATURES = {
     "d3f_pose_errors": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_sanitize_descriptors": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "d3f_matching_summary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "d3f_registration_recall": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "d3f_icp_pairs_workspace_bytes": (_sz, [_i, _i]),
     "d3f_icp_pairs": (_i, [_vp, _sz, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i] + [_vp] * 9 + [_sz, _vp]),
     "d3f_gemm_pack_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -772,3 +772,8 @@ extern "C" int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int
 // ETH test: np.nan_to_num of the descriptors and the per-scene matching summary (d3f_sanitize_descriptors, d3f_matching_summary)
 // ---------------------------------------------------------------------------------------------------------------------
 #include "rp_scene_summary.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// 3DMatch registration recall of every scene at every keypoint count in two launches (d3f_registration_recall)
+// ---------------------------------------------------------------------------------------------------------------------
+#include "rp_registration_recall.h"

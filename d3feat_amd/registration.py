@@ -22,6 +22,10 @@
     matching_summary(matching, gt_flag, scene_start) recall, average inliers and average inlier ratio of every scene at every count
                                             in two launches (evaluate.py:200-219, evaluate_eth.py:142-177); match_scenes(...) is
                                             sanitize_descriptors + match_pairs + matching_summary, the ETH test in one call
+    registration_recall(T, gt, info, gt_flag, ids, scene_start) the registration recall of the 3DMatch benchmark (3dmatch/evaluate.m,
+                                            mrEvaluateRegistration.m; float64) of every scene at every count in two launches;
+                                            register_scenes(...) is sanitize_descriptors + register_pairs(_counts) + matching_summary
+                                            + registration_recall: both recalls of all eight scenes in one call
 
 Every computation is a kernel of libd3feat_amd.so (csrc/registration.hip, csrc/radius_neighbors.hip); numpy / torch only
 move data and run the host loop over batches of hypotheses.  Open3D's own random stream is unspecified, so results are
@@ -889,3 +893,178 @@ def match_scenes(kp, count, pairs, gt, gt_flag, scene_start, num_keypts=EVALUATE
                     out=out.matching if out is not None else None)
     s = matching_summary(m, gt_flag, scene_start, inlier_ratio=inlier_ratio, out=out.summary if out is not None else None)
     return out if out is not None else SceneMatches(m, s)
+
+
+# ---- the 3DMatch registration benchmark: registration recall of every scene in one call (geometric_registration/3dmatch/evaluate.m) ---
+RECALL_3DMATCH = dict(err2=0.04)                                               # mrEvaluateRegistration.m:2-4 (0.2 ^ 2)
+RECALL_GOOD, RECALL_RESULT, RECALL_FALSE_POS, RECALL_GT = 1, 2, 4, 8           # the bits of SceneRecall.flags
+RECALL_FIGURES = ("good", "bad", "false_pos", "gt_num", "rs_num")
+
+
+def _round_half_away(x):
+    """MATLAB's round for x >= 0 (evaluate.m:45)."""
+    f = int(np.floor(x))
+    return f + (1 if x - f >= 0.5 else 0)
+
+
+class SceneRecall:
+    """Result of registration_recall: DEVICE tensors error f64[P, n] (the transformation error p of mrComputeTransformationError where
+    the pair has a result and a ground truth and is not consecutive, 0 elsewhere; NaN kept), flags i32[P, n] (bit 0: good, bit 1:
+    counted in rs_num, bit 2: false positive, bit 3: counted in gt_num) and figures i64[S, n, 5] (per scene and count: good, bad,
+    false_pos, gt_num, rs_num); n is 1 for a [P, 3, 4] / [P, 4, 4] input (error and flags are then [P]).  .host(), .scenes(),
+    .overall(c) and .failed(c) share one read-back."""
+
+    def __init__(self, P, n, flat, scene_start, err2, logged, device):
+        self.P, self.n, self.flat, self.scene_start = P, n, flat, tuple(int(v) for v in scene_start)
+        self.err2, self.logged, self.S = float(err2), bool(logged), len(self.scene_start) - 1
+        shape = (P,) if flat else (P, n)
+        self.error = torch.empty(shape, dtype=torch.float64, device=device)
+        self.flags = torch.empty(shape, dtype=torch.int32, device=device)
+        self.figures = torch.empty((self.S, n, 5), dtype=torch.int64, device=device)
+        self.ids = None                                         # an input of the call, kept for the read-back
+
+    _cache = None
+
+    def host(self):
+        """One read-back of the whole result, kept until the next registration_recall(out=self): dict of numpy arrays error [P, n],
+        flags [P, n], figures [S, n, 5] and ids [P, 2]."""
+        if self._cache is None:
+            two = lambda t: t.cpu().numpy().reshape(self.P, self.n)
+            self._cache = dict(error=two(self.error), flags=two(self.flags), figures=self.figures.cpu().numpy(),
+                               ids=self.ids.cpu().numpy().reshape(self.P, 2))
+        return self._cache
+
+    def scenes(self):
+        """[scene][count] -> dict(good, bad, false_pos, gt_num, rs_num, recall, precision): the integers of `figures`, recall = good /
+        gt_num and precision = good / rs_num as FRACTIONS (mrEvaluateRegistration.m:38-39), 0.0 where MATLAB would divide by zero."""
+        fig = self.host()["figures"]
+        out = []
+        for s in range(self.S):
+            per_count = []
+            for c in range(self.n):
+                r = {k: int(v) for k, v in zip(RECALL_FIGURES, fig[s, c])}
+                r["recall"] = r["good"] / r["gt_num"] if r["gt_num"] else 0.0
+                r["precision"] = r["good"] / r["rs_num"] if r["rs_num"] else 0.0
+                per_count.append(r)
+            out.append(per_count)
+        return out
+
+    def overall(self, c=0):
+        """The closing figures of evaluate.m:41-48 at count c: dict(recall_list, mean_recall, mean_precision = the means over the scenes,
+        total_tp = the sum of round(gt_num * recall), total_gt, true_recall = total_tp / total_gt)."""
+        sc = [per_count[c] for per_count in self.scenes()]
+        mean = lambda key: sum(r[key] for r in sc) / len(sc) if sc else 0.0
+        tp, gt = sum(_round_half_away(r["gt_num"] * r["recall"]) for r in sc), sum(r["gt_num"] for r in sc)
+        return dict(recall_list=[r["recall"] for r in sc], mean_recall=mean("recall"), mean_precision=mean("precision"), total_tp=tp,
+                    total_gt=gt, true_recall=tp / gt if gt else 0.0)
+
+    def failed(self, c=0):
+        """[(scene, id1, id2, p)] of the bad rows of count c, in pair order: a result for a listed, non-consecutive pair whose error is
+        above err2 (or NaN)."""
+        h = self.host()
+        out = []
+        for s in range(self.S):
+            for p in range(self.scene_start[s], self.scene_start[s + 1]):
+                if h["flags"][p, c] & (RECALL_GOOD | RECALL_RESULT | RECALL_FALSE_POS) == RECALL_RESULT:
+                    out.append((s, int(h["ids"][p, 0]), int(h["ids"][p, 1]), float(h["error"][p, c])))
+        return out
+
+
+def registration_recall(T, gt, info, gt_flag, ids, scene_start, err2=RECALL_3DMATCH["err2"], result_flag=None, logged=False, out=None):
+    """The registration recall of the 3DMatch benchmark (geometric_registration/3dmatch/evaluate.m with mrEvaluateRegistration.m) for
+    every scene in one call.  T: f32[P, 3, 4] / f32[P, n, 3, 4] estimates source -> target, or the PairRegistration /
+    PairRegistrationCounts that holds them -- widened to float64 and inverted on the device, as evaluate.py:104 logs the inverse --, or
+    with logged=True f64[P, 4, 4] / f64[P, n, 4, 4] matrices as a .log file holds them (results.read_result_log), not inverted.
+    gt f64[P, 4, 4] the gt.log matrix (target -> source, register_pairs' direction), info f64[P, 6, 6] the gt.info matrix, gt_flag
+    i32[P] (1 where gt.log lists the pair), result_flag i32[P] (1 where the pair has a result; None: gt_flag, what evaluate.py logs),
+    ids i32[P, 2] the fragment numbers of the pair inside its scene -- all on the device (datasets.threedmatch.benchmark makes them);
+    scene_start as matching_summary takes it.  Per row the error p = er' info er / info[0][0] of gt^-1 * result in float64 (NaN kept, a
+    bad row) and four flags, per scene and count five integer sums.  Two launches whatever P is, no read-back (capturable: pass the
+    previous result as `out`).  -> SceneRecall (device tensors; .host(), .scenes(), .overall(c), .failed(c))."""
+    lib = _lib.load()
+    if isinstance(T, (PairRegistration, PairRegistrationCounts)):
+        T = T.T
+    T = ops._req(T, torch.float64 if logged else torch.float32, "T")
+    tail = (4, 4) if logged else (3, 4)
+    if T.dim() not in (3, 4) or tuple(T.shape[-2:]) != tail or not T.is_contiguous():
+        raise ValueError("registration_recall: T of shape %s (contiguous [P, %d, 4] or [P, n, %d, 4])" % (tuple(T.shape), tail[0], tail[0]))
+    dev, P, flat = T.device, T.shape[0], T.dim() == 3
+    n = 1 if flat else T.shape[1]
+    gt = ops._req(gt, torch.float64, "gt", 3)
+    info = ops._req(info, torch.float64, "info", 3)
+    gt_flag = ops._req(gt_flag, torch.int32, "gt_flag", 1)
+    ids = ops._req(ids, torch.int32, "ids", 2)
+    if result_flag is not None:
+        result_flag = ops._req(result_flag, torch.int32, "result_flag", 1)
+    if (tuple(gt.shape) != (P, 4, 4) or tuple(info.shape) != (P, 6, 6) or gt_flag.shape[0] != P or tuple(ids.shape) != (P, 2)
+            or (result_flag is not None and result_flag.shape[0] != P) or not 1 <= n <= _lib.REPEAT_COUNTS_MAX
+            or not all(t.is_contiguous() for t in (gt, info, gt_flag, ids) + ((result_flag,) if result_flag is not None else ()))):
+        raise ValueError("registration_recall: gt %s, info %s, gt_flag %s, ids %s for T %s (contiguous [P, 4, 4], [P, 6, 6], [P], [P, 2])"
+                         % (tuple(gt.shape), tuple(info.shape), tuple(gt_flag.shape), tuple(ids.shape), tuple(T.shape)))
+    starts = [int(v) for v in np.asarray(scene_start).reshape(-1)]
+    S = len(starts) - 1
+    if not 0 <= S <= _lib.SCENES_MAX or starts[0] != 0 or starts[-1] != P or any(b < a for a, b in zip(starts, starts[1:])):
+        raise ValueError("registration_recall: scene_start %s must hold 1 to %d ascending ints from 0 to P = %d" % (starts, _lib.SCENES_MAX + 1, P))
+    e2 = float(err2)
+    if not e2 > 0.0:
+        raise ValueError("registration_recall: err2 %r" % (err2,))
+    if out is None:
+        out = SceneRecall(P, n, flat, starts, e2, logged, dev)
+    elif (not isinstance(out, SceneRecall) or out.error.device != dev
+          or (out.P, out.n, out.flat, out.scene_start, out.err2, out.logged) != (P, n, flat, tuple(starts), e2, bool(logged))):
+        raise ValueError("registration_recall: out= was made for another call")
+    out._cache = None
+    out.ids = ids
+    c_starts, c_err2 = (_lib.C.c_int * (S + 1))(*starts), _lib.C.c_double(e2)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None      # (an empty tensor has no address)
+    rc = lib.d3f_registration_recall(ptr(T), 1 if logged else 0, ptr(gt), ptr(info), ptr(gt_flag), ptr(result_flag), ptr(ids), P, n,
+                                     _lib.C.addressof(c_starts), S, _lib.C.addressof(c_err2), ptr(out.error), ptr(out.flags),
+                                     ptr(out.figures), ops._stream(dev))
+    _lib.check(rc, "registration_recall")
+    return out
+
+
+class SceneRegistration:
+    """Result of register_scenes: `registration` (PairRegistration of register_pairs, or PairRegistrationCounts of
+    register_pairs_counts for a tuple of counts), `matching` (SceneMatching of matching_summary on its mutual_count / gt_inliers) and
+    `recall` (SceneRecall of registration_recall on its T), all device tensors; gt32 is the float32 ground truth RANSAC was given."""
+
+    def __init__(self, registration, matching, recall, gt32):
+        self.registration, self.matching, self.recall, self.gt32 = registration, matching, recall, gt32
+        self.T = registration.T
+
+
+def register_scenes(kp, count, pairs, gt, info, gt_flag, ids, scene_start, num_keypts=250, seed=0,
+                    distance_threshold=0.10, inlier_ratio=0.05, err2=RECALL_3DMATCH["err2"], nan_to_num=True, out=None):
+    """The 3DMatch benchmark for every pair of every scene in one call: geometric_registration/evaluate.py (np.nan_to_num of the
+    descriptors, :43-44; the mutual matches and their inliers under gt, :67-82; RANSAC, :93-99) and 3dmatch/evaluate.m (registration
+    recall).  kp f32[n_blocks, K, 4 + C] / count the keypoint blocks of ALL scenes (stack_keypoints), pairs i32[P, 2] global block
+    indices with the scenes contiguous, gt f64[P, 4, 4] (target -> source), info f64[P, 6, 6], gt_flag i32[P], ids i32[P, 2] and
+    scene_start as registration_recall takes them (datasets.threedmatch.benchmark makes the six).  sanitize_descriptors(kp) -- IN
+    PLACE, skipped with nan_to_num=False --, then register_pairs(num_keypts, gt rounded to float32, **EVALUATE_3DMATCH) for one count or
+    register_pairs_counts for a tuple of counts, matching_summary on its mutual_count / gt_inliers and registration_recall on its T; no
+    read-back in between (capturable: pass the previous result as `out`).  T and the matching figures are bit-equal to the
+    stand-alone calls.  -> SceneRegistration (.registration, .matching, .recall): both recalls of every scene at every count."""
+    if out is not None and not isinstance(out, SceneRegistration):
+        raise ValueError("register_scenes: out= was made for another call")
+    gt = ops._req(gt, torch.float64, "gt", 3)
+    if tuple(gt.shape[1:]) != (4, 4):
+        raise ValueError("register_scenes: gt of shape %s ([P, 4, 4])" % (tuple(gt.shape),))
+    many = isinstance(num_keypts, (tuple, list))
+    if out is not None and isinstance(out.registration, PairRegistrationCounts) != many:
+        raise ValueError("register_scenes: out= was made for another call")
+    if nan_to_num:
+        sanitize_descriptors(kp)
+    if out is not None:
+        gt32 = out.gt32.copy_(gt[:, :3])                         # (plumbing: the rounding of the ground truth, in place under capture)
+    else:
+        gt32 = gt[:, :3].to(torch.float32).contiguous()
+    kw = dict(seed=seed, gt=gt32, distance_threshold=distance_threshold, out=out.registration if out is not None else None, **EVALUATE_3DMATCH)
+    if many:
+        reg = register_pairs_counts(kp, count, pairs, num_keypts=tuple(num_keypts), **kw)
+    else:
+        reg = register_pairs(kp, count, pairs, num_keypts=int(num_keypts), **kw)
+    m = matching_summary(reg.mutual_count, reg.gt_inliers, gt_flag, scene_start, inlier_ratio=inlier_ratio,
+                         out=out.matching if out is not None else None)
+    r = registration_recall(reg.T, gt, info, gt_flag, ids, scene_start, err2=err2, out=out.recall if out is not None else None)
+    return out if out is not None else SceneRegistration(reg, m, r, gt32)

@@ -169,6 +169,63 @@ def eth_lines(scene_names, summary, c=0):
     return lines
 
 
+# ---- the files and lines of geometric_registration/3dmatch/evaluate.m --------------------------------------------------------------
+def _blocks(path, width):
+    """The whitespace-separated numbers of a .log / .info file as fscanf reads them (mrLoadLog.m, mrLoadInfo.m): blocks of three
+    integers and width * width floats -> [((id1, id2, n), f64[width, width])]; a trailing partial block is an error."""
+    with open(path) as f:
+        tok = f.read().split()
+    per = 3 + width * width
+    if len(tok) % per:
+        raise ValueError("%s: %d numbers, not a multiple of %d" % (path, len(tok), per))
+    out = []
+    for i in range(0, len(tok), per):
+        head = tuple(int(t) for t in tok[i:i + 3])
+        out.append((head, np.array([float(t) for t in tok[i + 3:i + per]], np.float64).reshape(width, width)))
+    return out
+
+
+def read_gt_info(path):
+    """A gt.info (blocks of `id1 \\t id2 \\t n` + six rows of a 6x6 information matrix, mrLoadInfo.m) -> {"id1_id2": f64[6,6]}, the
+    keys of read_gt_log.  Two entries for one pair are an error: mrEvaluateRegistration.m:9-14 would keep the last and count both, the
+    benchmark's files hold none."""
+    result = {}
+    for (id1, id2, _), mat in _blocks(path, 6):
+        key = "%d_%d" % (id1, id2)
+        if key in result:
+            raise ValueError("%s: two entries for the pair %s" % (path, key))
+        result[key] = mat
+    return result
+
+
+def read_result_log(path):
+    """A .log of results as write_registration_log / evaluate.py:101-110 write it (mrLoadLog.m) -> the ordered list
+    [(id1, id2, f64[4,4])]; a pair that appears twice appears twice here, and counts twice, as in mrEvaluateRegistration.m:21-37."""
+    return [(id1, id2, mat) for (id1, id2, _), mat in _blocks(path, 4)]
+
+
+def _num2str(x):
+    """MATLAB's num2str of a scalar in [0, 1]: '%d' for an integer, otherwise sprintf('%.5g') (max(floor(log10(x)) + 5, 5) significant
+    digits), which drops trailing zeros."""
+    return "%d" % x if float(x) == int(x) else "%.5g" % x
+
+
+def registration_recall_lines(scene_names, summary, c=0):
+    """The lines geometric_registration/3dmatch/evaluate.m prints for count c, with the .m files' own wording: per scene
+    `recall : R ( good / gt_num )` (mrEvaluateRegistration.m:40, MATLAB's disp of num2str = %.5g with trailing zeros dropped), then
+    evaluate.m:47-48 (`%f`, `%d`).  The `totalRecall` column MATLAB echoes in between is its console format, not reproduced.  summary:
+    registration.SceneRecall (or anything with its .scenes() / .overall()), one scene per name.  Where MATLAB would print NaN (a scene
+    without a non-consecutive ground-truth pair) the ratio is 0."""
+    scenes = summary.scenes()
+    if len(scene_names) != len(scenes):
+        raise ValueError("registration_recall_lines: %d names, %d scenes" % (len(scene_names), len(scenes)))
+    lines = ["recall : %s ( %s / %s )" % (_num2str(per[c]["recall"]), _num2str(per[c]["good"]), _num2str(per[c]["gt_num"])) for per in scenes]
+    o = summary.overall(c)
+    lines += ["Mean registration recall: %f precision: %f" % (o["mean_recall"], o["mean_precision"]),
+              "True average recall: %f (%d/%d)" % (o["true_recall"], o["total_tp"], o["total_gt"])]
+    return lines
+
+
 # ---- the lines of repeatability/evaluate_3dmatch_our.py / evaluate_kitti_our.py -------------------------------------------------
 def repeatability_table(num_keypts, scene_values):
     """The lines both scripts print, one per keypoint count (evaluate_3dmatch_our.py:66, evaluate_kitti_our.py:44), from values

@@ -789,6 +789,49 @@ int d3f_sanitize_descriptors(float* kp, int n_blocks, int K, int ld, int C, void
 int d3f_matching_summary(const int* mutual_count, const int* gt_inliers, const int* gt_flag, int P, int n, const int* scene_start_host,
                          int S, const double* inlier_ratio_host, int* ratio_e8, long long* figures, void* stream);
 
+/* Registration recall of the 3DMatch benchmark (Choi et al.) for S scenes and n estimates per pair at once: what
+ * geometric_registration/3dmatch/evaluate.m of the reference computes, through external/ElasticReconstruction/mrEvaluateRegistration.m,
+ * from the .log file geometric_registration/evaluate.py:101-110 writes and the scene's gt.log / gt.info.  THE DEFINITION is the text
+ * below (tests/recall_np.py is this text in numpy); MATLAB's own bits and the summation order of its BLAS are not reproduced.
+ *   T_est, logged: logged == 0: f32[P, n, 3, 4] estimates source -> target (d3f_register_pairs' / d3f_register_pairs_counts' T), widened
+ *     to float64 and INVERTED on the device, because evaluate.py:104 logs inv(transformation); logged != 0: f64[P, n, 4, 4] as the
+ *     .log holds them, not inverted, the fourth row not read.
+ *   gt f64[P, 4, 4]: the gt.log matrix of the pair, target -> source (the direction of d3f_register_pairs' gt; fourth row not read);
+ *   info f64[P, 6, 6]: its gt.info matrix;  gt_flag i32[P]: 1 where gt.log lists the pair;  result_flag i32[P]: 1 where the pair has a
+ *   result, NULL: result_flag == gt_flag (evaluate.py:60-65 logs exactly the listed pairs);  ids i32[P, 2]: the fragment numbers of the
+ *   pair INSIDE ITS SCENE;  all on the device.  Scene s owns the pairs scene_start_host[s] .. scene_start_host[s + 1] - 1 (S + 1 ints
+ *   on the HOST, read before the call returns); err2_host: one double on the host (0.04 = 0.2^2 in the .m file).
+ * Per row (pair p, column c), with apart = ids[p][1] - ids[p][0] > 1, g = gt_flag[p] != 0, r = result_flag[p] != 0:
+ *   flags i32[P, n]: bit 1 (rs_num): r and apart;  bit 3 (gt_num): g and apart, with or without a result;  bit 2 (false positive): r
+ *     and apart and not g;  bit 0 (good): r and g and apart and p <= err2 -- NOT strict, and false for a NaN.
+ *   error f64[P, n]: the transformation error p where r and g and apart, 0 elsewhere.  In float64, every operation rounded on its own
+ *   and every sum taken left to right as written:
+ *     inverse of an affine [A | t] by cofactors over the determinant (a general inverse, not A^T: a float32 rotation is orthonormal
+ *     to 1e-7 only, and the log holds its true inverse):
+ *       n00 = a11 a22 - a12 a21   n01 = a02 a21 - a01 a22   n02 = a01 a12 - a02 a11
+ *       n10 = a12 a20 - a10 a22   n11 = a00 a22 - a02 a20   n12 = a02 a10 - a00 a12
+ *       n20 = a10 a21 - a11 a20   n21 = a01 a20 - a00 a21   n22 = a00 a11 - a01 a10
+ *       det = (a00 n00 + a01 n10) + a02 n20;  B[r][c] = n_rc / det;  u[r] = -((B[r][0] t0 + B[r][1] t1) + B[r][2] t2)
+ *     result [R | w] = the inverse of T_est (logged == 0) or the first three rows of T_est (logged != 0);  [B | u] = the inverse of gt;
+ *     E[r][c] = (B[r][0] R[0][c] + B[r][1] R[1][c]) + B[r][2] R[2][c];  E[r][3] = ((B[r][0] w0 + B[r][1] w1) + B[r][2] w2) + u[r]
+ *     s = ((1 + E00) + E11) + E22;  q0 = 0.5 sqrt(s);  d = 4 q0;
+ *     er = [E03, E13, E23, (E21 - E12) / d, (E02 - E20) / d, (E10 - E01) / d]
+ *     v[r] = the six products info[r][c] er[c], c ascending;  p = (the six products er[r] v[r], r ascending) / info[0][0].
+ *   Where s > 0 is false, p is NaN (MATLAB would go complex for s < 0: only within rounding of a 180 degree error).  A NaN anywhere
+ *   gives a NaN p and a row that is not good.
+ * figures i64[S, n, 5], per scene and column the rows with: [0] bit 0 (good); [1] bit 1 without bits 0 and 2 (bad); [2] bit 2
+ *   (false_pos); [3] bit 3 (gt_num); [4] bit 1 (rs_num).  recall = good / gt_num, precision = good / rs_num.  All integers: no
+ *   summation order enters.  An empty scene gives five zeros.  Duplicate ground-truth entries, which the .m file's mask resolves to
+ *   the last one, cannot be expressed: one row per pair and estimate.  Duplicate result rows are rows.
+ * Two launches whatever P is (one thread per row; one workgroup per scene), no atomics, no memset, no workspace, no allocation, no
+ * synchronisation: capturable.  D3F_ERR_ARG before anything touches the device: P < 0, n outside 1 .. D3F_REPEAT_COUNTS_MAX,
+ * P * n >= 2^31, S outside 0 .. D3F_SCENES_MAX, scene_start_host not ascending from 0 or scene_start_host[S] != P, err2 not positive
+ * (NaN too), a NULL pointer that is needed (the host pointers; the device inputs other than result_flag, error and flags when P > 0;
+ * figures when S > 0).  P == 0 is legal. */
+int d3f_registration_recall(const void* T_est, int logged, const double* gt, const double* info, const int* gt_flag,
+                            const int* result_flag, const int* ids, int P, int n, const int* scene_start_host, int S,
+                            const double* err2_host, double* error, int* flags, long long* figures, void* stream);
+
 /* Point-to-point ICP of B (source, target) pairs, run to convergence on the device (datasets/KITTI.py:293-297 of the reference refines
  * the KITTI ground truth with it).  THE DEFINITION is Open3D's registration_icp with TransformationEstimationPointToPoint(False) and
  * ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration), restated here; tests/icp_np.py is this text in numpy, and

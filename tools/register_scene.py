@@ -16,6 +16,10 @@ and prints the recall line of evaluate.py:200-219.  Without --gt no pair has a g
 registration.register_pairs_counts call for all pairs at all counts, the same files per count under --out/num_keypts_<k>/ and one
 recall line per count (with its num_keypts).
 
+--info gt.info (with --gt) adds, before each of those lines, the line of external/ElasticReconstruction/mrEvaluateRegistration.m:40 for
+the scene: the registration recall of geometric_registration/3dmatch/evaluate.m, from registration.registration_recall on the
+transforms while they are still on the device.  Without the flag the output is unchanged.
+
     python tools/register_scene.py --root RESULTS --scene sun3d-hotel_umd-maryland_hotel3 --gt gt.log --out OUT
     python tools/register_scene.py --root RESULTS --scene sun3d-hotel_umd-maryland_hotel3 --gt gt.log --out OUT --counts 250,500,1000,2500,5000
 """
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--root", required=True)
     ap.add_argument("--scene", required=True)
     ap.add_argument("--gt", default=None, help="the scene's gt.log (geometric_registration/gt_result/<scene>-evaluation/gt.log)")
+    ap.add_argument("--info", default=None, help="the scene's gt.info: adds the registration recall line of mrEvaluateRegistration.m")
     ap.add_argument("--num-keypts", type=int, default=250)
     ap.add_argument("--counts", default=None, help="comma-separated ascending keypoint counts: all of them in one call, files per count")
     ap.add_argument("--desc-name", default="D3Feat")
@@ -74,9 +79,23 @@ def main():
     for i, p in enumerate(host_pairs):
         if flag[i]:
             gt[i] = gt_log["%d_%d" % p][:3]
+    recall = None
+    if a.info:
+        if not a.gt:
+            raise SystemExit("--info needs --gt")
+        info_log = results.read_gt_info(a.info)
+        if set(info_log) != set(gt_log):
+            raise SystemExit("%s and %s list different pairs" % (a.gt, a.info))
+        gt64, info = np.tile(np.eye(4), (len(host_pairs), 1, 1)), np.tile(np.eye(6), (len(host_pairs), 1, 1))
+        for i, p in enumerate(host_pairs):
+            if flag[i]:
+                gt64[i], info[i] = gt_log["%d_%d" % p], info_log["%d_%d" % p]
+        gt64, info, dflag = torch.from_numpy(gt64).to(dev), torch.from_numpy(info).to(dev), torch.from_numpy(flag.astype(np.int32)).to(dev)
+        # one scene: the block indices of `pairs` are the fragment numbers
+        recall = lambda res: reg.registration_recall(res, gt64, info, dflag, pairs, [0, len(host_pairs)], **reg.RECALL_3DMATCH)
     gt = torch.from_numpy(gt.astype(np.float32)).to(dev)
 
-    def write(out_dir, mutual, inl, T34, extra):
+    def write(out_dir, mutual, inl, T34, extra, recall_line=None):
         T = np.tile(np.eye(4), (len(host_pairs), 1, 1))
         T[:, :3] = T34.astype(np.float64)
         # pairs that gt.log does not list: num_inliers = inlier_ratio = gt_flag = 0 and no .log block (evaluate.py:60-65)
@@ -87,18 +106,23 @@ def main():
         results.write_registration_log(os.path.join(out_dir, "%s.log" % a.desc_name), [host_pairs[i] for i in logged], [T[i] for i in logged])
         rows = results.write_pair_results(out_dir, host_pairs, num_inliers, ratio, flag)
         rec = results.feature_matching_recall(rows, a.inlier_ratio)
+        if recall_line is not None:
+            print(recall_line)
         print(json.dumps(dict(scene=a.scene, fragments=len(blocks), pairs=len(host_pairs), **extra, **rec)))
 
     if counts is None:
         res = reg.register_pairs(kp, count, pairs, num_keypts=a.num_keypts, seed=a.seed, gt=gt, distance_threshold=a.distance_threshold,
                                  **reg.EVALUATE_3DMATCH)
-        write(a.out, res.mutual_count.cpu().numpy(), res.gt_inliers.cpu().numpy(), res.T.cpu().numpy(), {})
+        write(a.out, res.mutual_count.cpu().numpy(), res.gt_inliers.cpu().numpy(), res.T.cpu().numpy(), {},
+              results.registration_recall_lines([a.scene], recall(res))[0] if recall else None)
         return
     res = reg.register_pairs_counts(kp, count, pairs, num_keypts=counts, seed=a.seed, gt=gt, distance_threshold=a.distance_threshold,
                                     **reg.EVALUATE_3DMATCH)
     mutual, inl, T = res.mutual_count.cpu().numpy(), res.gt_inliers.cpu().numpy(), res.T.cpu().numpy()
+    rec = recall(res) if recall else None
     for c, k in enumerate(counts):
-        write(os.path.join(a.out, "num_keypts_%d" % k), mutual[:, c], inl[:, c], T[:, c], {"num_keypts": k})
+        write(os.path.join(a.out, "num_keypts_%d" % k), mutual[:, c], inl[:, c], T[:, c], {"num_keypts": k},
+              results.registration_recall_lines([a.scene], rec, c)[0] if rec else None)
 
 
 if __name__ == "__main__":
