@@ -22,6 +22,7 @@ REPEAT_COUNTS_MAX = 16
 MATCH_KMAX = 8192
 VALIDATION_NMAX = 1024
 SCENES_MAX = 256
+GRID_RESET_MAX = 8
 VP_INDEX_RANGE, VP_COUNT_RANGE = 1, 2           # status of a pair of d3f_validation_pairs
 
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
@@ -41,6 +42,11 @@ SIGNATURES = {
     "d3f_neighbor_grid_bytes": (_sz, [_i, _i]),
     "d3f_neighbor_grid_order_offset": (_sz, [_i, _i]),
     "d3f_neighbor_grid_build": (_i, [_vp, _i, _vp, _i, _f, _vp, _sz, _vp]),
+    "d3f_neighbor_grid_boxed_form": (_i, [_i, _i]),
+    "d3f_geometry_reset": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "d3f_neighbor_grid_build_boxed": (_i, [_vp, _i, _vp, _i, _f, _vp, _vp, _sz, _vp]),
+    "d3f_stack_self_pair_boxed": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "d3f_batch_grid_subsample_async_boxed": (_i, [_vp, _vp, _i, _vp, _i, _f, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_neighbor_grid_search": (_i, [_vp, _sz, _i, _vp, _i, _vp, _i, _f, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]),
     "d3f_neighbor_grid_search_ordered": (_i, [_vp, _sz, _i, _vp, _i, _vp, _i, _f, _vp, _sz, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]),
     "d3f_neighbor_grid_inv_offset": (_sz, [_i, _i]),

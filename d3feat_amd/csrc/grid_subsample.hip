@@ -135,6 +135,28 @@ struct GsPrepEpi {
     __device__ __forceinline__ void operator()() const { gs_prep(bbox, offs, B, dl, el, status, smeta, n_cap); }
 };
 
+// The first launch of the sort form when the caller brings finished boxes (the kernel that wrote the points gathered them):
+// begin_kernel's resets, and gs_prep in workgroup 0 instead of in the epilogue of a pass over the points.  The status words that
+// gs_prep raises flags in are the second fill, which is small enough (<= 256 words) to be done by workgroup 0 itself.
+__global__ void __launch_bounds__(256) gs_begin_boxed_kernel(const int* __restrict__ lens, int B, int* __restrict__ offs,
+                                                             const unsigned* __restrict__ bbox, unsigned* __restrict__ counters,
+                                                             int ncounters, D3fFill f0, D3fFill fmeta, float dl, GsElem* __restrict__ el,
+                                                             int* __restrict__ status, RsMeta* __restrict__ smeta, int n_cap) {
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    d3f_fill_words(f0, tid, stride);
+    if (blockIdx.x != 0) return;
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int b = 0; b < B; ++b) { offs[b] = s; s += lens[b]; }
+        offs[B] = s;
+    }
+    for (int i = threadIdx.x; i < ncounters; i += blockDim.x) counters[i] = 0u;
+    for (int i = threadIdx.x; i < (int)fmeta.n; i += blockDim.x) fmeta.p[i] = fmeta.v;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (every wave's own stores acknowledged before the barrier, as d3f_last_block)
+    __syncthreads();        // offs and the cleared status words, written by this workgroup, are read by gs_prep below
+    gs_prep(bbox, offs, B, dl, el, status, smeta, n_cap);
+}
+
 // ---- voxel key per point + hash insert (grid_subsampling.cpp:49-59) ----------------------------------
 __global__ void __launch_bounds__(256) gs_insert_kernel(const float* __restrict__ pts, int N, const int* __restrict__ offs,
                                                         int B, float dl, const GsElem* __restrict__ el,
@@ -706,21 +728,32 @@ __global__ void __launch_bounds__(256) gs_runs_kernel(int N, const RsMeta* __res
     bary[3 * (size_t)v + 2] = __fmul_rn(az, sc);
 }
 // barycentre of voxel v -> output row (element offset + iteration-order position)
-__global__ void __launch_bounds__(256) gs_emit_kernel(int* __restrict__ status, const int* __restrict__ moffs, int B,
+// BOX: the kernel also gathers the boxes of the clouds it writes (d3f_box_accum_block; launched with 1024 threads, so that a
+// cloud's box takes few atomics)
+template <bool BOX>
+__global__ void __launch_bounds__(BOX ? 1024 : 256) gs_emit_kernel(int* __restrict__ status, const int* __restrict__ moffs, int B,
                                                       const int* __restrict__ vpos, const float* __restrict__ bary,
-                                                      float* __restrict__ out_p, int out_cap) {
+                                                      float* __restrict__ out_p, int out_cap, unsigned* __restrict__ bbox_out) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= status[0]) return;
-    if (status[1] & (D3F_ST_OUT_OVERFLOW | D3F_ST_KEY_WIDTH)) return;   // reported empty: no row is written (as the one-workgroup form)
-    const int b = d3f_find_elem(moffs, B, v);
-    const size_t dest = (size_t)moffs[b] + (size_t)vpos[v];
-    if (dest >= (size_t)out_cap) {   // (cannot happen once the epilogue has checked M: kept as the last line of defence)
-        atomicOr(&status[1], D3F_ST_OUT_OVERFLOW);
-        return;
+    // reported empty (overflow / key width): no row is written (as the one-workgroup form)
+    bool ok = v < status[0] && !(status[1] & (D3F_ST_OUT_OVERFLOW | D3F_ST_KEY_WIDTH));
+    int b = -1;
+    float x = 0.f, y = 0.f, z = 0.f;
+    if (ok) {
+        b = d3f_find_elem(moffs, B, v);
+        const size_t dest = (size_t)moffs[b] + (size_t)vpos[v];
+        if (dest >= (size_t)out_cap) {   // (cannot happen once the epilogue has checked M: kept as the last line of defence)
+            atomicOr(&status[1], D3F_ST_OUT_OVERFLOW);
+            ok = false;
+        } else {
+            x = bary[3 * (size_t)v + 0]; y = bary[3 * (size_t)v + 1]; z = bary[3 * (size_t)v + 2];
+            out_p[3 * dest + 0] = x;
+            out_p[3 * dest + 1] = y;
+            out_p[3 * dest + 2] = z;
+        }
     }
-    out_p[3 * dest + 0] = bary[3 * (size_t)v + 0];
-    out_p[3 * dest + 1] = bary[3 * (size_t)v + 1];
-    out_p[3 * dest + 2] = bary[3 * (size_t)v + 2];
+    // the boxes of the clouds this kernel writes, for the grid build and the subsampling that read them next (all threads take part)
+    if constexpr (BOX) d3f_box_accum_block(bbox_out, ok ? b : -1, x, y, z);
 }
 
 
@@ -835,7 +868,8 @@ static int gs_small_launch(const GsSmallArgs& A, float* sub_points, int* sub_len
     return D3F_OK;
 }
 static int gs_run_small(const float* points, int N, const int* lens_dev, int B, float dl, float* sub_points, int M_cap, int elem_cap,
-                        int pc, int* sub_lens_dev, int* status_dev, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+                        int pc, int* sub_lens_dev, int* status_dev, void* workspace, size_t workspace_bytes, hipStream_t stream,
+                        unsigned* bbox_out = nullptr) {
     if (elem_cap <= 0 || elem_cap > M_cap) elem_cap = M_cap;
     if (elem_cap > pc) elem_cap = pc;                   // voxels <= points
     D3fArena ar(workspace, workspace_bytes);
@@ -845,6 +879,7 @@ static int gs_run_small(const float* points, int N, const int* lens_dev, int B, 
     A.mcount = ar.take<int>(B);
     A.cflags = ar.take<int>(B);
     if (!ar.ok) return D3F_ERR_WORKSPACE;
+    A.bbox_out = bbox_out;
     A.pts = points; A.lens = lens_dev; A.B = B; A.dl = dl; A.elem_cap = elem_cap; A.pc = pc; A.out_cap = M_cap;
     // the largest iteration-order round that has to fit the workgroup's LDS: the first chain value >= the voxel capacity
     A.nbmax = GSS_NB_MAX;
@@ -866,7 +901,8 @@ static int gs_run_small(const float* points, int N, const int* lens_dev, int B, 
 static int gs_run(const float* points, int N, const int* lens_dev, int B, float dl, const float* features, int fdim,
                   const int* classes, int ldim, float* sub_points, int M_cap, int elem_cap, int elem_points, float* sub_features,
                   int* sub_classes, int* sub_lens_dev, int* status_host, int* status_dev, void* workspace,
-                  size_t workspace_bytes, hipStream_t stream, const float* const* ptrs = nullptr) {
+                  size_t workspace_bytes, hipStream_t stream, const float* const* ptrs = nullptr, const unsigned* bbox_in = nullptr,
+                  unsigned* bbox_out = nullptr) {
     const bool async = status_dev != nullptr;
     if (async && !features && ldim == 0 && !ptrs) {
         // one workgroup per cloud when the caller's capacities fit it: every cloud <= 16384 points and <= 5087 voxels (a cloud
@@ -875,7 +911,7 @@ static int gs_run(const float* points, int N, const int* lens_dev, int B, float 
         int ec = (elem_cap > 0 && elem_cap < M_cap) ? elem_cap : M_cap;
         if (ec > pc) ec = pc;
         if (pc <= 16384 && ec <= GSS_NB_MAX) return gs_run_small(points, N, lens_dev, B, dl, sub_points, M_cap, elem_cap, pc, sub_lens_dev, status_dev,
-                                             workspace, workspace_bytes, stream);
+                                             workspace, workspace_bytes, stream, bbox_out);
     }
     GsLayout L = gs_layout(N, B, async ? M_cap : -1);
     D3fArena ar(workspace, workspace_bytes);
@@ -938,12 +974,23 @@ static int gs_run(const float* points, int N, const int* lens_dev, int B, float 
     const unsigned long long ones_words = (unsigned long long)((char*)(vhead + n) - (char*)tkey) / 4ull;
     const unsigned long long zero_words = (unsigned long long)((char*)(vcnt + n) - (char*)meta) / 4ull;
     // (sort form: only the first-occurrence bits and the status words need clearing)
+    if (bbox_in && use_sort) {
+        // finished boxes: no pass over the points, the grid geometry is derived by the reset launch itself
+        const unsigned long long words = (unsigned long long)(n / 32 + 2);
+        long long blocks = (long long)(words / 4 / 256) + 1;
+        if (blocks > 1024) blocks = 1024;
+        gs_begin_boxed_kernel<<<(int)blocks, 256, 0, stream>>>(lens_dev, B, offs, bbox_in, counters, ncounters, D3fFill{fbits, words, 0u},
+                                                               D3fFill{(unsigned*)meta, (unsigned long long)(B + 2), 0u}, dl, el, meta,
+                                                               smeta, N);
+        D3F_LAUNCH_CHECK();
+    } else {
     if ((rc = use_sort ? d3f_begin_launch(lens_dev, B, offs, bbox, counters, ncounters, D3fFill{fbits, (unsigned long long)(n / 32 + 2), 0u},
                                           D3fFill{(unsigned*)meta, (unsigned long long)(B + 2), 0u}, none, none, stream)
                        : d3f_begin_launch(lens_dev, B, offs, bbox, counters, ncounters, D3fFill{(unsigned*)tkey, ones_words, 0xFFFFFFFFu},
                                           D3fFill{(unsigned*)meta, zero_words, 0u}, none, none, stream)) != D3F_OK) return rc;
     GsPrepEpi prep{bbox, offs, B, dl, el, meta, use_sort ? smeta : nullptr, N};
     if ((rc = d3f_bbox_launch_t(points, offs, B, N, bbox, counters, prep, stream, ptrs)) != D3F_OK) return rc;
+    }
     const int nblk = d3f_cdiv(N, 256);
     const int elem_lim = async ? elem_cap : 0x7fffffff;
     int M, maxM;       // sizes of the voxel-indexed launches
@@ -1010,7 +1057,8 @@ static int gs_run(const float* points, int N, const int* lens_dev, int B, float 
         gs_order_place_kernel<<<gp, 256, 0, stream>>>(A, j);
     }
     if (use_sort)
-        gs_emit_kernel<<<d3f_cdiv(M, 256), 256, 0, stream>>>(meta, moffs, B, A.vpos, bary, sub_points, M_cap);
+        if (bbox_out) gs_emit_kernel<true><<<d3f_cdiv(M, 1024), 1024, 0, stream>>>(meta, moffs, B, A.vpos, bary, sub_points, M_cap, bbox_out);
+        else gs_emit_kernel<false><<<d3f_cdiv(M, 256), 256, 0, stream>>>(meta, moffs, B, A.vpos, bary, sub_points, M_cap, nullptr);
     else
         gs_accum_kernel<<<d3f_cdiv(async ? N : M, 256), 256, 0, stream>>>(points, features, fdim, meta, moffs, B, vstart, sbase,
                                                                          vcnt, sorted, A.vpos, sub_points, sub_features, M_cap);
@@ -1061,14 +1109,34 @@ extern "C" int d3f_batch_grid_subsample_async_inplace(const float* const* clouds
                   nullptr, status_dev, workspace, workspace_bytes, stream, clouds_dev);
 }
 
+// d3f_batch_grid_subsample_async / _inplace (clouds_dev != NULL: in place, `points` unused) with bounding boxes handed along the
+// pyramid: bbox_in_dev (optional) = the finished boxes of the input clouds, gathered by the kernel that wrote them -- the sort form
+// then makes no pass over the points to box them (the one-workgroup form boxes its cloud out of the loads it needs anyway);
+// bbox_out_dev (optional) = the boxes of the clouds this call writes, accumulated into pre-initialised words (d3f_geometry_reset).
+extern "C" int d3f_batch_grid_subsample_async_boxed(const float* points, const float* const* clouds_dev, int N_cap, const int* lens_dev,
+                                                    int B, float dl, float* sub_points, int M_cap, int elem_cap, int elem_points_cap,
+                                                    int* sub_lens_dev, int* status_dev, const unsigned* bbox_in_dev,
+                                                    unsigned* bbox_out_dev, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (N_cap < 1 || N_cap > (1 << 30) || M_cap < 1 || elem_cap < 0 || elem_points_cap < 0 || B < 1 || B > D3F_MAX_BATCH || !(dl > 0.f))
+        return D3F_ERR_ARG;
+    if ((!points && !clouds_dev) || (points && clouds_dev) || !lens_dev || !sub_points || !sub_lens_dev || !status_dev) return D3F_ERR_ARG;
+    return gs_run(points, N_cap, lens_dev, B, dl, nullptr, 0, nullptr, 0, sub_points, M_cap, elem_cap, clouds_dev ? 0 : elem_points_cap,
+                  nullptr, nullptr, sub_lens_dev, nullptr, status_dev, workspace, workspace_bytes, stream, clouds_dev, bbox_in_dev,
+                  bbox_out_dev);
+}
+
 // np.concatenate([pts, pts]) of the reference's test generators (datasets/ThreeDMatch.py:190-192, demo_registration.py:
 // 72-79: every fragment is fed stacked with itself), for B clouds at once and with the row counts read from HBM:
 // cloud b (rows [o_b, o_b + m_b) of pts) becomes rows [2 o_b, 2 o_b + m_b) and [2 o_b + m_b, 2 o_b + 2 m_b) of out,
 // lens_out = [m_0, m_0, m_1, m_1, ...], total = 2 sum m_b.  B = 1 is the single self-pair.
 __global__ void __launch_bounds__(256) gs_stack_pair_kernel(const float* __restrict__ pts, int M_cap, const int* __restrict__ lens_in,
                                                             int B, float* __restrict__ out, int* __restrict__ lens_out,
-                                                            int* __restrict__ total) {
+                                                            int* __restrict__ total, const unsigned* __restrict__ bbox_in,
+                                                            unsigned* __restrict__ bbox_out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    // both copies of a cloud have the cloud's box: the finished boxes of the input, gathered by the kernel that wrote it
+    if (bbox_out && i < 12 * B) bbox_out[i] = bbox_in[(i / 12) * 6 + i % 6];
     int tot = 0;
     for (int b = 0; b < B; ++b) tot += lens_in[b];
     tot = min(tot, M_cap);
@@ -1097,12 +1165,18 @@ __global__ void __launch_bounds__(256) gs_stack_pair_kernel(const float* __restr
     out[3 * (row + m) + c] = v;
 }
 
-extern "C" int d3f_stack_self_pair(const float* pts, int M_cap, const int* lens_in_dev, int B, float* out, int* lens_out_dev,
-                                   int* total_dev, void* stream_) {
+extern "C" int d3f_stack_self_pair_boxed(const float* pts, int M_cap, const int* lens_in_dev, int B, float* out, int* lens_out_dev,
+                                         int* total_dev, const unsigned* bbox_in_dev, unsigned* bbox_out_dev, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (M_cap < 1 || B < 1 || 2 * B > D3F_MAX_BATCH || !pts || !lens_in_dev || !out || !lens_out_dev || !total_dev)
+    if (M_cap < 1 || B < 1 || 2 * B > D3F_MAX_BATCH || !pts || !lens_in_dev || !out || !lens_out_dev || !total_dev ||
+        (bbox_out_dev && !bbox_in_dev))
         return D3F_ERR_ARG;
-    gs_stack_pair_kernel<<<d3f_cdiv(3ll * M_cap, 256), 256, 0, stream>>>(pts, M_cap, lens_in_dev, B, out, lens_out_dev, total_dev);
+    gs_stack_pair_kernel<<<d3f_cdiv(3ll * M_cap, 256), 256, 0, stream>>>(pts, M_cap, lens_in_dev, B, out, lens_out_dev, total_dev,
+                                                                         bbox_in_dev, bbox_out_dev);
     D3F_LAUNCH_CHECK();
     return D3F_OK;
+}
+extern "C" int d3f_stack_self_pair(const float* pts, int M_cap, const int* lens_in_dev, int B, float* out, int* lens_out_dev,
+                                   int* total_dev, void* stream_) {
+    return d3f_stack_self_pair_boxed(pts, M_cap, lens_in_dev, B, out, lens_out_dev, total_dev, nullptr, nullptr, stream_);
 }

@@ -31,6 +31,7 @@ struct GsSmallArgs {
     int nbmax;             // largest bucket count whose round fits the LDS of this launch (a chain value)
     int* mcount;           // [B] voxels per cloud (0 when the cloud could not be processed)
     int* cflags;           // [B] D3F_ST_* bits of each cloud (written, not accumulated: nothing to reset between calls)
+    unsigned* bbox_out;    // optional [B][6]: the box of every cloud's barycentres (ordered-uint min xyz, max xyz; pre-initialised)
 };
 
 template <int T>
@@ -343,14 +344,41 @@ __global__ void __launch_bounds__(T) gs_small_kernel(GsSmallArgs A) {
     }
     // La[v] = iteration-order position of voxel v
     float* __restrict__ out = A.stage + 3 * (size_t)b * (size_t)A.elem_cap;
+    unsigned bmn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, bmx[3] = {0u, 0u, 0u};
     for (int v = tid; v < M; v += T) {
         const float4 q = rec[v];
         const size_t d = (size_t)La[v];
         out[3 * d + 0] = q.x;
         out[3 * d + 1] = q.y;
         out[3 * d + 2] = q.z;
+        const unsigned ux = d3f_f2ord(q.x), uy = d3f_f2ord(q.y), uz = d3f_f2ord(q.z);
+        bmn[0] = min(bmn[0], ux); bmn[1] = min(bmn[1], uy); bmn[2] = min(bmn[2], uz);
+        bmx[0] = max(bmx[0], ux); bmx[1] = max(bmx[1], uy); bmx[2] = max(bmx[2], uz);
     }
     if (tid == 0) { A.mcount[b] = M; A.cflags[b] = *sFlag; }
+    if (A.bbox_out) {
+        // the box of the barycentres, for the grid build that reads this cloud next: the workgroup owns the cloud, so plain stores
+        // (a cloud that returned above keeps the initial values; its length is reported as 0)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                bmn[d] = min(bmn[d], (unsigned)__shfl_xor((int)bmn[d], o, 64));
+                bmx[d] = max(bmx[d], (unsigned)__shfl_xor((int)bmx[d], o, 64));
+            }
+        }
+        __syncthreads();                 // (the scratch words held the last scan's wave sums)
+        if (lane == 0) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) { sScr[w * 6 + d] = (int)bmn[d]; sScr[w * 6 + 3 + d] = (int)bmx[d]; }
+        }
+        __syncthreads();
+        if (tid < 6) {
+            unsigned r = (unsigned)sScr[tid];
+            for (int k = 1; k < W; ++k) r = tid < 3 ? min(r, (unsigned)sScr[k * 6 + tid]) : max(r, (unsigned)sScr[k * 6 + tid]);
+            A.bbox_out[b * 6 + tid] = r;
+        }
+    }
 }
 
 // staging blocks -> contiguous rows; lengths and status (one workgroup per 256 rows; every thread recomputes the offsets)

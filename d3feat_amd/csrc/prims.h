@@ -40,6 +40,17 @@ __device__ __forceinline__ bool d3f_last_block(unsigned* counter, unsigned nbloc
     return last_flag != 0;
 }
 
+// one fill, spread over the whole launch (tid / stride: the thread's index in the launch and the launch's thread count)
+__device__ __forceinline__ void d3f_fill_words(const D3fFill& f, size_t tid, size_t stride) {
+    unsigned* p = f.p;
+    const size_t n = (size_t)f.n;
+    if (n == 0) return;
+    const size_t n4 = (((uintptr_t)p & 15) == 0) ? n / 4 : 0;
+    const uint4 v4 = make_uint4(f.v, f.v, f.v, f.v);
+    for (size_t j = tid; j < n4; j += stride) ((uint4*)p)[j] = v4;
+    for (size_t j = n4 * 4 + tid; j < n; j += stride) p[j] = f.v;
+}
+
 // offs[0..B] = prefix sums of lens; bbox[b*6 + {0,1,2}] = 0xFFFFFFFF (min slots), {3,4,5} = 0 (max slots); counters = 0;
 // fills f0..f3 (n = 0: unused).  Any grid size; 256 threads.
 static __global__ void __launch_bounds__(256) begin_kernel(const int* __restrict__ lens, int B, int* __restrict__ offs,
@@ -56,17 +67,10 @@ static __global__ void __launch_bounds__(256) begin_kernel(const int* __restrict
             for (int i = threadIdx.x; i < B * 6; i += blockDim.x) bbox[i] = ((i % 6) < 3) ? 0xFFFFFFFFu : 0u;
         for (int i = threadIdx.x; i < ncounters; i += blockDim.x) counters[i] = 0u;
     }
-    const D3fFill f[4] = {f0, f1, f2, f3};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        unsigned* p = f[k].p;
-        const size_t n = (size_t)f[k].n;
-        if (n == 0) continue;
-        const size_t n4 = (((uintptr_t)p & 15) == 0) ? n / 4 : 0;
-        const uint4 v4 = make_uint4(f[k].v, f[k].v, f[k].v, f[k].v);
-        for (size_t j = tid; j < n4; j += stride) ((uint4*)p)[j] = v4;
-        for (size_t j = n4 * 4 + tid; j < n; j += stride) p[j] = f[k].v;
-    }
+    d3f_fill_words(f0, tid, stride);
+    d3f_fill_words(f1, tid, stride);
+    d3f_fill_words(f2, tid, stride);
+    d3f_fill_words(f3, tid, stride);
 }
 
 static inline int d3f_begin_launch(const int* lens, int B, int* offs, unsigned* bbox, unsigned* counters, int ncounters,
@@ -149,6 +153,94 @@ static inline int d3f_bbox_launch_t(const float* pts, const int* offs, int B, in
     bbox_kernel<Epi><<<dim3(chunks, B), 256, 0, stream>>>(pts, ptrs, offs, B, bbox, counter, epi);
     D3F_LAUNCH_CHECK();
     return D3F_OK;
+}
+
+// ---- bounding boxes accumulated by the kernel that WRITES the points --------------------------------------------------
+// Min and max do not depend on the order of their operands, so a box gathered by the producer of a cloud equals the one
+// bbox_kernel finds by reading the cloud again, bit for bit.  bbox[b * 6 ..] must hold the initial values (min slots
+// 0xFFFFFFFF, max slots 0) before the producer runs.
+// Atomics on one cache line serialise in L2 at ~12 ns each, and all boxes of a cloud share a line: what counts is the number of
+// atomics per cloud, so the reduction goes wavefront -> workgroup (runs of wavefronts that belong to one element are merged) and
+// a slot whose value would not change is skipped after a plain read (the stored bound only tightens: a stale read can cost an
+// atomic, never lose one).
+// EVERY thread of the workgroup calls this (blockDim.x a multiple of 64, <= 1024; no early return before it).  b < 0: the thread
+// contributes nothing.  Elements must not decrease with the thread index.  A wavefront that straddles two elements falls back to
+// one atomic per lane and slot.
+__device__ __forceinline__ void d3f_box_flush(unsigned* __restrict__ bbox, int b, int slot, unsigned v) {
+    unsigned* p = &bbox[b * 6 + slot];
+    const unsigned old = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (slot < 3) { if (v < old) atomicMin(p, v); }
+    else if (v > old) atomicMax(p, v);
+}
+__device__ __forceinline__ void d3f_box_accum_block(unsigned* __restrict__ bbox, int b, float x, float y, float z) {
+    __shared__ unsigned sBox[16][6];
+    __shared__ int sElem[16];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    unsigned v[6] = {d3f_f2ord(x), d3f_f2ord(y), d3f_f2ord(z), 0u, 0u, 0u};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        v[3 + d] = b < 0 ? 0u : v[d];
+        v[d] = b < 0 ? 0xFFFFFFFFu : v[d];
+    }
+    const unsigned long long live = __ballot(b >= 0);
+    int bw = -1;                                           // the wavefront's element; -1: nothing left for the workgroup step
+    if (live) {
+        bw = __shfl(b, __ffsll((long long)live) - 1, 64);
+        if (__ballot(b >= 0 && b != bw)) {
+            // one element after the other: its lanes reduced, six lanes flush the six slots side by side (a chain of six
+            // read-then-atomic pairs per lane held the whole launch up)
+            unsigned long long rem = live;
+            while (rem) {
+                const int bs = __shfl(b, __ffsll((long long)rem) - 1, 64);
+                const bool mine = b == bs;
+                unsigned r[6], sel = 0u;
+#pragma unroll
+                for (int t = 0; t < 6; ++t) {
+                    r[t] = mine ? v[t] : (t < 3 ? 0xFFFFFFFFu : 0u);
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) {
+                        const unsigned q = (unsigned)__shfl_xor((int)r[t], o, 64);
+                        r[t] = t < 3 ? min(r[t], q) : max(r[t], q);
+                    }
+                    sel = lane == t ? r[t] : sel;
+                }
+                if (lane < 6) d3f_box_flush(bbox, bs, lane, sel);
+                rem &= ~__ballot(mine);
+            }
+            bw = -1;
+        } else {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    v[d] = min(v[d], (unsigned)__shfl_xor((int)v[d], o, 64));
+                    v[3 + d] = max(v[3 + d], (unsigned)__shfl_xor((int)v[3 + d], o, 64));
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        sElem[w] = bw;
+#pragma unroll
+        for (int t = 0; t < 6; ++t) sBox[w][t] = v[t];
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int t = threadIdx.x;
+        int cur = -1;
+        unsigned acc = 0u;
+        for (int k = 0; k <= nw; ++k) {
+            const int bk = k < nw ? sElem[k] : -2;         // (-2: the end, flushes the last run)
+            if (bk == -1) continue;
+            if (bk != cur) {
+                if (cur >= 0) d3f_box_flush(bbox, cur, t, acc);
+                cur = bk;
+                acc = k < nw ? sBox[k][t] : 0u;
+            } else {
+                acc = t < 3 ? min(acc, sBox[k][t]) : max(acc, sBox[k][t]);
+            }
+        }
+    }
 }
 
 // ---- one-launch exclusive scan --------------------------------------------------------------------------------------

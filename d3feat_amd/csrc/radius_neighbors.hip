@@ -35,8 +35,46 @@ struct NbElem {
 #define NB_WAVES_PER_BLOCK 4
 #define NB_EL_LDS 40      // batch elements whose grid geometry the search kernel copies to LDS (56 bytes each; 16 fragments = 32 clouds)
 
-// one thread per element: choose the cell edge (>= radius*(1+2^-20); doubled until the element's grid fits
-// its share of the cell budget), grid dims and cell base.
+// geometry of one element: the cell edge (>= radius*(1+2^-20); doubled until the element's grid fits `per` cells) and the grid
+// dims; cbase is left to the caller
+__device__ __forceinline__ void nb_elem_geometry(const unsigned* __restrict__ bbox, int b, int len, float radius, long long per,
+                                                 NbElem& e) {
+    if (len <= 0) {
+        e.mn[0] = e.mn[1] = e.mn[2] = 0.0;
+        e.inv_h = 1.0;
+        e.dims[0] = e.dims[1] = e.dims[2] = 1;
+    } else {
+        double mx[3];
+        for (int d = 0; d < 3; ++d) {
+            e.mn[d] = (double)d3f_ord2f(__hip_atomic_load(&bbox[b * 6 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            mx[d] = (double)d3f_ord2f(__hip_atomic_load(&bbox[b * 6 + 3 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        }
+        double h = (double)radius * (1.0 + 1.0 / 1048576.0);
+        if (!(h > 0.0)) h = 1.0;
+        bool fits = false;
+        for (int it = 0; it < 64; ++it) {
+            // dims use the same expression as nb_cell_of, so every support's cell is in range by monotonicity
+            e.inv_h = 1.0 / h;
+            double tot = 1.0;
+            for (int d = 0; d < 3; ++d) {
+                double n = floor((mx[d] - e.mn[d]) * e.inv_h) + 1.0;
+                e.dims[d] = (n < 1073741824.0) ? (int)n : 1073741824;
+                tot *= n;
+            }
+            if (tot <= (double)per) { fits = true; break; }
+            h *= 2.0;
+        }
+        if (!fits) {
+            // non-finite coordinates (never produced by the pipeline; possible when a flagged, overflowing capacity-mode
+            // call left garbage rows upstream): one cell, every support a candidate -- slow but memory-safe
+            e.mn[0] = e.mn[1] = e.mn[2] = 0.0;
+            e.inv_h = 0.0;
+            e.dims[0] = e.dims[1] = e.dims[2] = 1;
+        }
+    }
+}
+
+// one thread for all elements: geometry of every element and its cell base.
 __device__ __forceinline__ void nb_prep(const unsigned* __restrict__ bbox, const int* __restrict__ soffs, int B, float radius,
                                         long long cell_budget, NbElem* __restrict__ el, int* __restrict__ ncells_total) {
     if (threadIdx.x != 0) return;
@@ -44,40 +82,7 @@ __device__ __forceinline__ void nb_prep(const unsigned* __restrict__ bbox, const
     const long long per = cell_budget / B;
     for (int b = 0; b < B; ++b) {
         NbElem e;
-        const int len = soffs[b + 1] - soffs[b];
-        if (len <= 0) {
-            e.mn[0] = e.mn[1] = e.mn[2] = 0.0;
-            e.inv_h = 1.0;
-            e.dims[0] = e.dims[1] = e.dims[2] = 1;
-        } else {
-            double mx[3];
-            for (int d = 0; d < 3; ++d) {
-                e.mn[d] = (double)d3f_ord2f(__hip_atomic_load(&bbox[b * 6 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                mx[d] = (double)d3f_ord2f(__hip_atomic_load(&bbox[b * 6 + 3 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            }
-            double h = (double)radius * (1.0 + 1.0 / 1048576.0);
-            if (!(h > 0.0)) h = 1.0;
-            bool fits = false;
-            for (int it = 0; it < 64; ++it) {
-                // dims use the same expression as nb_cell_of, so every support's cell is in range by monotonicity
-                e.inv_h = 1.0 / h;
-                double tot = 1.0;
-                for (int d = 0; d < 3; ++d) {
-                    double n = floor((mx[d] - e.mn[d]) * e.inv_h) + 1.0;
-                    e.dims[d] = (n < 1073741824.0) ? (int)n : 1073741824;
-                    tot *= n;
-                }
-                if (tot <= (double)per) { fits = true; break; }
-                h *= 2.0;
-            }
-            if (!fits) {
-                // non-finite coordinates (never produced by the pipeline; possible when a flagged, overflowing capacity-mode
-                // call left garbage rows upstream): one cell, every support a candidate -- slow but memory-safe
-                e.mn[0] = e.mn[1] = e.mn[2] = 0.0;
-                e.inv_h = 0.0;
-                e.dims[0] = e.dims[1] = e.dims[2] = 1;
-            }
-        }
+        nb_elem_geometry(bbox, b, soffs[b + 1] - soffs[b], radius, per, e);
         e.cbase = (int)base;
         base += (long long)e.dims[0] * e.dims[1] * e.dims[2];
         el[b] = e;
@@ -131,6 +136,159 @@ __global__ void __launch_bounds__(256) nb_scatter_kernel(const float* __restrict
     order[pos] = i;
     inv[i] = pos;
     xyz[3 * (size_t)pos] = x; xyz[3 * (size_t)pos + 1] = y; xyz[3 * (size_t)pos + 2] = z;
+}
+
+// ---- builds from FINISHED boxes (d3f_neighbor_grid_build_boxed) -------------------------------------------------------------
+// The kernel that wrote the supports also gathered their boxes (d3f_box_accum), so nothing reads the cloud to box it and nothing
+// waits for a last workgroup: every workgroup of the first launch derives the geometry of all B elements itself (one thread per
+// element, then a serial prefix over B cell counts), which gives it the offsets and cell bases it needs; workgroup 0 stores them
+// for the searches.  A support's rank inside its cell is what the counting atomic returns -- kept in `inv` until the scatter
+// overwrites it with the final position -- so there are no cursors to clear and no second atomic per support.
+//   large form  count -> scan_fold -> scatter (3 launches), cell counters in memory, cleared by the replay's one reset launch
+//   small form  one launch, one workgroup per element: counters, scan and cell starts in LDS
+#define NBX_SMALL_T 512          // threads of a small-form workgroup
+#define NBX_LDS_CELLS 8192       // cells a small-form workgroup counts in LDS (the element's cell budget is capped by it)
+#define NBX_COUNT_PTS 1024       // supports per workgroup of the large form's count kernel
+
+struct NbxGeom {
+    int offs[D3F_MAX_BATCH + 1];
+    NbElem el[D3F_MAX_BATCH];
+    int ncells;
+};
+// all threads of the workgroup; G in LDS
+__device__ __forceinline__ void nbx_geometry(NbxGeom& G, const int* __restrict__ lens, const unsigned* __restrict__ bbox, int B, float radius,
+                                             long long per) {
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int b = 0; b < B; ++b) { G.offs[b] = s; s += lens[b]; }
+        G.offs[B] = s;
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        NbElem e;
+        nb_elem_geometry(bbox, b, G.offs[b + 1] - G.offs[b], radius, per, e);
+        e.cbase = 0;
+        G.el[b] = e;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long base = 0;
+        for (int b = 0; b < B; ++b) {
+            G.el[b].cbase = (int)base;
+            base += (long long)G.el[b].dims[0] * G.el[b].dims[1] * G.el[b].dims[2];
+        }
+        G.ncells = (int)base;
+    }
+    __syncthreads();
+}
+// what nb_prep and begin_kernel leave in the grid object for the searches (one workgroup stores it)
+__device__ __forceinline__ void nbx_publish(const NbxGeom& G, int B, int* __restrict__ soffs, NbElem* __restrict__ el, int* __restrict__ ncells) {
+    for (int b = threadIdx.x; b <= B; b += blockDim.x) soffs[b] = G.offs[b];
+    for (int b = threadIdx.x; b < B; b += blockDim.x) el[b] = G.el[b];
+    if (threadIdx.x == 0) { ncells[0] = G.ncells; ncells[1] = G.ncells + 1; }
+}
+__device__ __forceinline__ int nbx_local_cell(const NbElem& e, float x, float y, float z) {
+    int cx, cy, cz;
+    nb_cell_of(e, x, y, z, cx, cy, cz);
+    cx = min(max(cx, 0), e.dims[0] - 1);
+    cy = min(max(cy, 0), e.dims[1] - 1);
+    cz = min(max(cz, 0), e.dims[2] - 1);
+    return cx + e.dims[0] * (cy + e.dims[1] * cz);
+}
+
+__global__ void __launch_bounds__(256) nbx_count_kernel(const float* __restrict__ s, int Ns, const int* __restrict__ lens, int B,
+                                                        const unsigned* __restrict__ bbox, float radius, long long per,
+                                                        int* __restrict__ soffs, NbElem* __restrict__ el, int* __restrict__ ncells,
+                                                        int* __restrict__ cell_of, int* __restrict__ cell_cnt, int* __restrict__ rank) {
+    __shared__ NbxGeom G;
+    nbx_geometry(G, lens, bbox, B, radius, per);
+    if (blockIdx.x == 0) nbx_publish(G, B, soffs, el, ncells);
+    const int n = min(Ns, G.offs[B]);   // Ns is the capacity, offs[B] the real number of supports
+#pragma unroll
+    for (int u = 0; u < NBX_COUNT_PTS / 256; ++u) {
+        const int i = blockIdx.x * NBX_COUNT_PTS + u * 256 + threadIdx.x;
+        if (i >= n) continue;
+        const int b = d3f_find_elem(G.offs, B, i);
+        const int c = G.el[b].cbase + nbx_local_cell(G.el[b], s[3 * (size_t)i], s[3 * (size_t)i + 1], s[3 * (size_t)i + 2]);
+        cell_of[i] = c;
+        rank[i] = atomicAdd(&cell_cnt[c], 1);
+    }
+}
+
+__global__ void __launch_bounds__(256) nbx_scatter_kernel(const float* __restrict__ s, int Ns, const int* __restrict__ ns_dev,
+                                                          const int* __restrict__ cell_of, const int* __restrict__ cell_start,
+                                                          const int* __restrict__ cell_base, float4* __restrict__ sorted,
+                                                          int* __restrict__ order, int* __restrict__ inv, float* __restrict__ xyz) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= min(Ns, *ns_dev)) return;
+    const int pos = d3f_scan_at(cell_start, cell_base, cell_of[i]) + inv[i];   // inv[i]: the rank nbx_count_kernel left
+    const float x = s[3 * (size_t)i], y = s[3 * (size_t)i + 1], z = s[3 * (size_t)i + 2];
+    sorted[pos] = make_float4(x, y, z, __int_as_float(i));
+    order[pos] = i;
+    inv[i] = pos;
+    xyz[3 * (size_t)pos] = x; xyz[3 * (size_t)pos + 1] = y; xyz[3 * (size_t)pos + 2] = z;
+}
+
+// small form: workgroup b builds element b.  cell_start holds the complete prefix (supports before the cell), so the tile bases
+// of the cells it owns are zero (d3f_scan_at adds them).
+__global__ void __launch_bounds__(NBX_SMALL_T) nbx_small_kernel(const float* __restrict__ s, int Ns, const int* __restrict__ lens, int B,
+                                                                const unsigned* __restrict__ bbox, float radius, long long per,
+                                                                int* __restrict__ soffs, NbElem* __restrict__ el, int* __restrict__ ncells,
+                                                                int* __restrict__ cell_of, int* __restrict__ cell_start,
+                                                                int* __restrict__ cell_base, float4* __restrict__ sorted,
+                                                                int* __restrict__ order, int* __restrict__ inv, float* __restrict__ xyz) {
+    __shared__ NbxGeom G;
+    __shared__ int sCnt[NBX_LDS_CELLS];
+    __shared__ int sW[NBX_SMALL_T / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    nbx_geometry(G, lens, bbox, B, radius, per);
+    if (b == 0) nbx_publish(G, B, soffs, el, ncells);
+    const NbElem e = G.el[b];
+    const int nc = e.dims[0] * e.dims[1] * e.dims[2];          // <= per <= NBX_LDS_CELLS (one cell when nothing fits)
+    const int n = min(Ns, G.offs[B]);
+    const int lo = min(G.offs[b], n), hi = min(G.offs[b + 1], n);
+    for (int j = tid; j < nc; j += NBX_SMALL_T) sCnt[j] = 0;
+    __syncthreads();
+    for (int i = lo + tid; i < hi; i += NBX_SMALL_T) {
+        const int c = nbx_local_cell(e, s[3 * (size_t)i], s[3 * (size_t)i + 1], s[3 * (size_t)i + 2]);
+        cell_of[i] = e.cbase + c;
+        inv[i] = atomicAdd(&sCnt[c], 1);
+    }
+    __syncthreads();
+    // exclusive scan of the counts in place: a run of consecutive cells per thread, the run sums across the workgroup
+    const int per_t = (nc + NBX_SMALL_T - 1) / NBX_SMALL_T;
+    const int j0 = min(tid * per_t, nc), j1 = min(j0 + per_t, nc);
+    int sum = 0;
+    for (int j = j0; j < j1; ++j) sum += sCnt[j];
+    int x = sum;
+    const int lane = tid & 63, w = tid >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) sW[w] = x;
+    __syncthreads();
+    int run = lo + x - sum;
+    for (int k = 0; k < w; ++k) run += sW[k];
+    for (int j = j0; j < j1; ++j) {
+        const int c = sCnt[j];
+        sCnt[j] = run;
+        run += c;
+    }
+    __syncthreads();
+    for (int j = tid; j < nc; j += NBX_SMALL_T) cell_start[e.cbase + j] = sCnt[j];
+    const int t0 = e.cbase / D3F_SCAN_TILE, t1 = (e.cbase + nc - (b == B - 1 ? 0 : 1)) / D3F_SCAN_TILE;
+    for (int t = t0 + tid; t <= t1; t += NBX_SMALL_T) cell_base[t] = 0;
+    if (b == B - 1 && tid == 0) cell_start[e.cbase + nc] = n;   // the prefix one past the last cell
+    for (int i = lo + tid; i < hi; i += NBX_SMALL_T) {
+        const int pos = sCnt[cell_of[i] - e.cbase] + inv[i];
+        const float px = s[3 * (size_t)i], py = s[3 * (size_t)i + 1], pz = s[3 * (size_t)i + 2];
+        sorted[pos] = make_float4(px, py, pz, __int_as_float(i));
+        order[pos] = i;
+        inv[i] = pos;
+        xyz[3 * (size_t)pos] = px; xyz[3 * (size_t)pos + 1] = py; xyz[3 * (size_t)pos + 2] = pz;
+    }
 }
 
 // ---- search: one wavefront per query -----------------------------------------------------------------
@@ -458,6 +616,10 @@ nb_search_kernel(const float* __restrict__ q, int Nq, const int* __restrict__ ql
 // cells the grid may use: 4 per support (surface clouds occupy ~0.3 cells per point at cell edge = radius; a sparser cloud gets
 // larger cells).  The budget is what every build has to clear -- in capacity mode whatever the real cloud size -- so it is
 // kept tight: 16 per support meant 40 MB of fills per level-0 build.
+static int nb_env(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 static long long nb_cell_budget(int Ns) {
     long long b = 4ll * (long long)(Ns > 0 ? Ns : 1);
     if (b < (1ll << 16)) b = 1ll << 16;
@@ -561,6 +723,87 @@ extern "C" int d3f_neighbor_grid_build(const float* supports, int Ns, const int*
     return D3F_OK;
 }
 
+// ---- d3f_neighbor_grid_build from finished boxes ------------------------------------------------------------------------------
+// The form is chosen on the host from the capacities (the sizes live on the device): the small form when an element's share of
+// the rows, ceil(Ns / B), is at most T (D3F_NB_SMALL_T, default 4096: measured).  T only decides speed: either
+// form builds any cloud (a small-form element of any size counts through LDS, its cell budget capped by NBX_LDS_CELLS).
+static int nbx_small_t() { return nb_env("D3F_NB_SMALL_T", 4096); }
+static bool nbx_is_small(int Ns, int B) { return d3f_cdiv(Ns > 0 ? Ns : 0, B) <= nbx_small_t(); }
+static long long nbx_per(int Ns, int B, bool small) {
+    const long long per = nb_cell_budget(Ns) / B;
+    return (small && per > NBX_LDS_CELLS) ? NBX_LDS_CELLS : per;
+}
+
+extern "C" int d3f_neighbor_grid_boxed_form(int Ns, int B) {
+    if (Ns < 0 || B < 1 || B > D3F_MAX_BATCH) return 0;
+    return nbx_is_small(Ns, B) ? 1 : 2;
+}
+
+// One launch for every reset a replay's boxed builds need: the boxes (n_boxes rows of 6 words: min slots 0xFFFFFFFF, max slots 0)
+// and, for every large-form grid, its cell counters and the ticket of its scan.
+struct NbxReset {
+    unsigned* boxes; int n_box_words; int n;
+    D3fFill f[2 * D3F_GRID_RESET_MAX];
+};
+__global__ void __launch_bounds__(256) nbx_reset_kernel(NbxReset R) {
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = tid; i < (size_t)R.n_box_words; i += stride) R.boxes[i] = ((i % 6) < 3) ? 0xFFFFFFFFu : 0u;
+    for (int k = 0; k < R.n; ++k) d3f_fill_words(R.f[k], tid, stride);
+}
+extern "C" int d3f_geometry_reset(unsigned* boxes_dev, int n_boxes, const void* const* grids, const size_t* grid_bytes, const int* Ns,
+                                  const int* B, int n_grids, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_boxes < 0 || (n_boxes > 0 && !boxes_dev) || n_grids < 0 || n_grids > D3F_GRID_RESET_MAX ||
+        (n_grids > 0 && (!grids || !grid_bytes || !Ns || !B)))
+        return D3F_ERR_ARG;
+    NbxReset R;
+    R.boxes = boxes_dev; R.n_box_words = 6 * n_boxes; R.n = 0;
+    unsigned long long words = (unsigned long long)R.n_box_words;
+    for (int k = 0; k < n_grids; ++k) {
+        if (Ns[k] < 0 || B[k] < 1 || B[k] > D3F_MAX_BATCH || !grids[k]) return D3F_ERR_ARG;
+        if (nbx_is_small(Ns[k], B[k])) continue;           // counts in LDS, no ticket
+        NbGrid g = nb_carve((void*)grids[k], grid_bytes[k], Ns[k], B[k]);
+        if (!g.ok) return D3F_ERR_WORKSPACE;
+        R.f[R.n++] = D3fFill{(unsigned*)g.cell_cnt, (unsigned long long)g.cells, 0u};
+        R.f[R.n++] = D3fFill{g.counters, 2ull, 0u};
+        words += (unsigned long long)g.cells + 2ull;
+    }
+    if (words == 0) return D3F_OK;
+    long long blocks = (long long)(words / 4 / 256) + 1;
+    if (blocks > 1024) blocks = 1024;
+    nbx_reset_kernel<<<(int)blocks, 256, 0, stream>>>(R);
+    D3F_LAUNCH_CHECK();
+    return D3F_OK;
+}
+
+extern "C" int d3f_neighbor_grid_build_boxed(const float* supports, int Ns, const int* s_lens_dev, int B, float radius,
+                                             const unsigned* bbox_dev, void* grid, size_t grid_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (Ns < 0 || B < 1 || B > D3F_MAX_BATCH || !(radius >= 0.f) || !s_lens_dev || (Ns > 0 && !supports) || !grid || !bbox_dev)
+        return D3F_ERR_ARG;
+    NbGrid g = nb_carve(grid, grid_bytes, Ns, B);
+    if (!g.ok) return D3F_ERR_WORKSPACE;
+    const bool small = nbx_is_small(Ns, B);
+    const long long per = nbx_per(Ns, B, small);
+    if (small) {
+        nbx_small_kernel<<<B, NBX_SMALL_T, 0, stream>>>(supports, Ns, s_lens_dev, B, bbox_dev, radius, per, g.soffs, g.el, g.ncells,
+                                                        g.cell_of, g.cell_start, g.stmp, g.sorted, g.order, g.inv, g.xyz);
+        D3F_LAUNCH_CHECK();
+        return D3F_OK;
+    }
+    // (Ns > 0 here: an empty capacity is small)
+    int rc;
+    nbx_count_kernel<<<d3f_cdiv(Ns, NBX_COUNT_PTS), 256, 0, stream>>>(supports, Ns, s_lens_dev, B, bbox_dev, radius, per, g.soffs, g.el,
+                                                                      g.ncells, g.cell_of, g.cell_cnt, g.inv);
+    D3F_LAUNCH_CHECK();
+    if ((rc = d3f_scan_fold_launch(D3fScanIn{g.cell_cnt}, (int)g.cells, g.ncells + 1, g.cell_start, g.stmp, g.counters + 1, D3fNoEpi{},
+                                   stream)) != D3F_OK) return rc;
+    nbx_scatter_kernel<<<d3f_cdiv(Ns, 256), 256, 0, stream>>>(supports, Ns, g.soffs + B, g.cell_of, g.cell_start, g.stmp, g.sorted,
+                                                              g.order, g.inv, g.xyz);
+    D3F_LAUNCH_CHECK();
+    return D3F_OK;
+}
+
 // ---- the searches of a built grid: one dispatcher ---------------------------------------------------------------------------------
 // qsorted: cell-sorted records {x, y, z, index} of a grid built over the QUERIES -- the visiting order (neighbouring wavefronts /
 // lane groups then read the same support runs); the grid's own records when the queries ARE its supports; NULL: plain order.
@@ -576,10 +819,6 @@ extern "C" int d3f_neighbor_grid_build(const float* supports, int Ns, const int*
 //   nearest only, no Kmax           nb_nearest_kernel (four lanes per query, a stencil row per lane) from 40 k queries on
 //                                   (235 k: 59 -> 48 with the queries' own cell order, 58 k: 25 -> 20); nb_search_kernel below
 // D3F_NB_CELL / D3F_NB_NEAREST = 0: never, = 2: always (A/B measurements; read per call so that one process can switch).
-static int nb_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 static int nb_search_dispatch(const NbGrid& g, const float* queries, int Nq, const int* q_lens_dev, int B, float radius,
                               const float4* qsorted, bool queries_are_supports, int* out, int ld, int width, int pad_value, int cap,
                               int first_only, float nn_hint, int want_kmax, int* status_dev, hipStream_t stream, bool internal = false) {

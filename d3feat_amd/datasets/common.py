@@ -306,7 +306,11 @@ class Dataset:
         layer_blocks = []
         hints = getattr(self, 'hints', None)
         units = max(int(getattr(self, 'cap_units', 1)), 1)
-        grids.append(ops.NeighborGrid(stacked_points, lens_dev, r_normal))
+        # boxed grid builds (ops.GridChain, set by the engine): the boxes travel from the kernel that writes a level to its grid build
+        # and to the subsampling that reads it
+        chain = getattr(self, 'grid_chain', None)
+        box = (lambda l: chain.box(l) if chain.boxed[l] else None) if chain is not None else (lambda l: None)
+        grids.append(ops.NeighborGrid(stacked_points, lens_dev, r_normal, chain=chain, level=0))
         for block_i, block in enumerate(arch):
             if 'global' in block or 'upsample' in block:
                 break
@@ -324,8 +328,9 @@ class Dataset:
                 pool_p, pool_b, _ = ops.batch_grid_subsample_async(P, L, dl, caps[layer + 1], status=status(),
                                                                    m_hint=hints[layer + 1] if hints else 0,
                                                                    elem_cap=-(-caps[layer + 1] // units),
-                                                                   elem_points=-(-caps[layer] // units))
-                Gn = ops.NeighborGrid(pool_p, pool_b, 2 * r_normal)
+                                                                   elem_points=-(-caps[layer] // units),
+                                                                   bbox_in=box(layer), bbox_out=box(layer + 1))
+                Gn = ops.NeighborGrid(pool_p, pool_b, 2 * r_normal, chain=chain, level=layer + 1)
             neighbors.append(search(G, P, L, G, layer) if layer_blocks else empty_i)
             if pooled:
                 pools.append(search(G, pool_p, pool_b, Gn, layer))

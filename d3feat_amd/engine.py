@@ -167,13 +167,22 @@ class FragmentEngine:
     # ---- the fixed launch sequence -------------------------------------------------------------------------------
     def _sequence(self, sl):
         cfg = self.cfg
+        # boxed grid builds (ops.GRID_BOXED): one reset launch for the replay's whole geometry chain, then every kernel that writes
+        # a level's cloud also gathers its boxes -- box0: where the writer of the level-0 stack leaves them
+        chain = sl.chain
+        box0 = chain.box(0) if chain is not None and chain.boxed[0] else None
+        stacked_here = not (self.mirror or self.two)      # the self-pair is stacked from the stage-0 clouds: their boxes, copied
+        pre = chain.pre[: self.nin] if box0 is not None and stacked_here else None
+        if chain is not None:
+            chain.reset()
         if self.stage0:
             # the raw clouds are read IN PLACE through a table of addresses (sl.raw_ptrs): a cloud that already lives in HBM is
             # never copied into the slot; one that arrives from the host (or as file records) is written to the slot's staging
             # buffer sl.raw and its address there goes into the table
             sub, sub_l, st0 = ops.batch_grid_subsample_async(None, sl.raw_len, cfg.first_subsampling_dl, self.F * self.n0_cap,
                                                              status=sl.status0, m_hint=self.F * self.n0_hint,
-                                                             elem_cap=self.n0_cap, clouds=sl.raw_ptrs, n_cap=self.F * self.raw_cap)
+                                                             elem_cap=self.n0_cap, clouds=sl.raw_ptrs, n_cap=self.F * self.raw_cap,
+                                                             bbox_out=pre if stacked_here else box0)
         else:
             sub, sub_l = sl.raw, sl.raw_len            # already at first_subsampling_dl: the stack is made of the clouds as fed
             sub.n_hint = self.F * self.n0_hint
@@ -185,7 +194,7 @@ class FragmentEngine:
         if self.mirror or self.two:
             pts, lens = sub, sub_l     # the stack as subsampled: lens = [m_1 .. m_F] (mirror) or [m_a1, m_b1, ...] (two clouds)
         else:
-            pts, lens = ops.stack_self_pair(sub, sub_l)        # [c_1; c_1; c_2; c_2; ...]
+            pts, lens = ops.stack_self_pair(sub, sub_l, bbox_in=pre, bbox_out=box0 if pre is not None else None)   # [c_1; c_1; c_2; c_2; ...]
         flat = sl.map(pts, None, None, None, lens, ("a", "a"), pts)
         with ops.bf16_contraction(self.bf16, features=self.bf16_features):
             desc, score = self.model.run(flat)
@@ -245,6 +254,12 @@ class FragmentEngine:
         # must not see the stack mates (models/D3Feat.py:84-85, datasets/common.py:453-496)
         sl.ds.stack_group = 1 if self.mirror else 2
         sl.ds.internal_order = self.internal
+        sl.chain = None
+        if ops.GRID_BOXED and self.internal and len(self.caps) <= _lib.GRID_RESET_MAX:
+            # the level-0 clouds of a stage0=False engine are the fed rows: no kernel of the sequence writes them
+            fed = not self.stage0
+            sl.chain = ops.GridChain(self.caps, self.F * (1 if self.mirror else 2), dev, boxed=[not fed] + [True] * (len(self.caps) - 1))
+        sl.ds.grid_chain = sl.chain
         sl.ds._neighbor_cap = self.neighbor_cap
         sl.cap = self.neighbor_cap
         sl.map = sl.ds.get_tf_mapping(self.cfg)

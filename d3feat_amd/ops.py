@@ -207,14 +207,17 @@ def batch_grid_subsample(points, lens, dl, features=None, classes=None):
     return sub_p[:M], sub_l, (sub_f[:M] if fdim else None), (sub_c[:M] if ldim else None)
 
 
-def batch_grid_subsample_async(points, lens, dl, m_cap, status=None, m_hint=0, elem_cap=0, elem_points=0, clouds=None, n_cap=0):
+def batch_grid_subsample_async(points, lens, dl, m_cap, status=None, m_hint=0, elem_cap=0, elem_points=0, clouds=None, n_cap=0,
+                               bbox_in=None, bbox_out=None):
     """Capacity mode of batch_grid_subsample (points only): no host synchronisation.
     clouds (device int64[B]: the ADDRESS of every cloud's own f32[len, 3] array) with points=None and n_cap = bound of sum(lens):
     the clouds are read in place, nothing is stacked (d3f_batch_grid_subsample_async_inplace).
     points f32[N_cap,3] (sum(lens) rows valid) -> (sub_points f32[m_cap,3] tagged with n_dev, sub_lens i32[B] device,
     status i32[2] device = [M, flags]).  elem_cap: capacity of ONE cloud of the stack (0: m_cap); a cloud above it raises
     the overflow flag like a stack above m_cap does.  elem_points: capacity of one cloud in POINTS (0: all rows of `points`);
-    at most 16384 selects the one-workgroup-per-cloud form (the coarse pyramid levels: 2 launches instead of ~25)."""
+    at most 16384 selects the one-workgroup-per-cloud form (the coarse pyramid levels: 2 launches instead of ~25).
+    bbox_in / bbox_out (device i32[B, 6], GridChain.box): finished boxes of the input clouds (the sort form then skips its boxing
+    pass) / where the boxes of the written clouds are accumulated (d3f_batch_grid_subsample_async_boxed)."""
     lib = _lib.load()
     if clouds is not None:
         assert points is None and clouds.dtype == torch.int64 and clouds.is_contiguous() and int(n_cap) > 0
@@ -232,7 +235,14 @@ def batch_grid_subsample_async(points, lens, dl, m_cap, status=None, m_hint=0, e
     nbytes = lib.d3f_grid_subsample_workspace_bytes(N, B, 0, 0)
     ws = workspace(nbytes, dev)
     with _timed("grid_subsample", dict(N=N, M=int(m_cap)), dev):
-        if clouds is not None:
+        if bbox_in is not None or bbox_out is not None:
+            assert all(b is None or (b.dtype == torch.int32 and b.is_contiguous() and b.numel() == 6 * B) for b in (bbox_in, bbox_out))
+            assert clouds is None or clouds.numel() == B
+            rc = lib.d3f_batch_grid_subsample_async_boxed(_ptr(points), _ptr(clouds), N, lens_t.data_ptr(), B, float(dl),
+                                                          sub_p.data_ptr(), int(m_cap), int(elem_cap), int(elem_points),
+                                                          sub_l.data_ptr(), status.data_ptr(), _ptr(bbox_in), _ptr(bbox_out),
+                                                          ws.data_ptr(), ws.numel(), _stream(dev))
+        elif clouds is not None:
             assert clouds.numel() == B
             rc = lib.d3f_batch_grid_subsample_async_inplace(clouds.data_ptr(), N, lens_t.data_ptr(), B, float(dl), sub_p.data_ptr(),
                                                             int(m_cap), int(elem_cap), sub_l.data_ptr(), status.data_ptr(),
@@ -268,10 +278,11 @@ def pack_status(dst, blocks, clear=None):
     return dst
 
 
-def stack_self_pair(pts, lens=None):
+def stack_self_pair(pts, lens=None, bbox_in=None, bbox_out=None):
     """np.concatenate([c, c]) for every cloud c of a stack whose row counts live on the device:
     pts f32[cap,3] holding B clouds (lens i32[B] on the device; default: one cloud of pts.n_dev rows)
-    -> (out f32[2*cap,3] = [c_0; c_0; c_1; c_1; ...] tagged with n_dev, lens_out i32[2B])."""
+    -> (out f32[2*cap,3] = [c_0; c_0; c_1; c_1; ...] tagged with n_dev, lens_out i32[2B]).
+    bbox_in (device i32[B, 6]: the finished boxes of the input clouds) -> bbox_out (device i32[2B, 6]): a box per written cloud."""
     lib = _lib.load()
     pts = _req(pts, torch.float32, "pts", 2).contiguous()
     dev = pts.device
@@ -284,19 +295,70 @@ def stack_self_pair(pts, lens=None):
     out = torch.empty((2 * cap, 3), dtype=torch.float32, device=dev)
     lens_out = torch.empty((2 * B,), dtype=torch.int32, device=dev)
     total = torch.empty((1,), dtype=torch.int32, device=dev)
-    rc = lib.d3f_stack_self_pair(pts.data_ptr(), cap, lens.data_ptr(), B, out.data_ptr(), lens_out.data_ptr(),
-                                 total.data_ptr(), _stream(dev))
+    if bbox_out is not None:
+        assert bbox_out.dtype == torch.int32 and bbox_out.is_contiguous() and bbox_out.numel() == 12 * B
+        assert bbox_in is not None and bbox_in.dtype == torch.int32 and bbox_in.is_contiguous() and bbox_in.numel() == 6 * B
+        rc = lib.d3f_stack_self_pair_boxed(pts.data_ptr(), cap, lens.data_ptr(), B, out.data_ptr(), lens_out.data_ptr(),
+                                           total.data_ptr(), bbox_in.data_ptr(), bbox_out.data_ptr(), _stream(dev))
+    else:
+        rc = lib.d3f_stack_self_pair(pts.data_ptr(), cap, lens.data_ptr(), B, out.data_ptr(), lens_out.data_ptr(),
+                                     total.data_ptr(), _stream(dev))
     _lib.check(rc, "stack_self_pair")
     out.n_dev = total
     out.n_hint = 2 * int(getattr(pts, "n_hint", 0) or 0)
     return out, lens_out
 
 
-class NeighborGrid:
-    """Cell grid over a stacked support cloud (see d3f_neighbor_grid_build); owns its device memory."""
+# Neighbour grids built from boxes that the kernels writing the clouds gathered (D3F_GRID_BOXED=0: every grid boxes its cloud
+# itself, d3f_neighbor_grid_build -- the five-launch build throughout).
+GRID_BOXED = os.environ.get("D3F_GRID_BOXED", "1") != "0"
 
-    def __init__(self, supports, s_lens, radius):
+
+class GridChain:
+    """The static memory of one replay's boxed grid builds: a box block i32[B, 6] and a grid object per pyramid level (rows[l]
+    support rows, B clouds), one more box block for the clouds a self-pair is stacked from (`pre`), and the ONE reset launch that precedes the geometry chain (d3f_geometry_reset): initial values of
+    every box, cleared counters of every large-form grid.  boxed[l] False: level l's cloud has no producer in the sequence, its
+    grid is built by d3f_neighbor_grid_build."""
+
+    def __init__(self, rows, B, device, boxed=None):
         lib = _lib.load()
+        self.rows, self.B = [int(r) for r in rows], int(B)
+        self.boxed = list(boxed) if boxed is not None else [True] * len(self.rows)
+        assert len(self.rows) <= _lib.GRID_RESET_MAX and len(self.boxed) == len(self.rows)
+        self.boxes = torch.zeros((len(self.rows) + 1, self.B, 6), dtype=torch.int32, device=device)
+        self.pre = self.boxes[len(self.rows)]
+        self.nbytes = [lib.d3f_neighbor_grid_bytes(r, self.B) for r in self.rows]
+        self.mems = [torch.empty((n,), dtype=torch.uint8, device=device) for n in self.nbytes]
+        self.forms = [lib.d3f_neighbor_grid_boxed_form(r, self.B) if on else 0 for r, on in zip(self.rows, self.boxed)]
+
+    def box(self, level):
+        return self.boxes[level]
+
+    def reset(self):
+        import ctypes
+        lib = _lib.load()
+        ks = [k for k, on in enumerate(self.boxed) if on]
+        n = len(ks)
+        grids = (ctypes.c_void_p * max(n, 1))(*[self.mems[k].data_ptr() for k in ks])
+        nbytes = (ctypes.c_size_t * max(n, 1))(*[self.nbytes[k] for k in ks])
+        rows = (ctypes.c_int * max(n, 1))(*[self.rows[k] for k in ks])
+        Bs = (ctypes.c_int * max(n, 1))(*([self.B] * n))
+        rc = lib.d3f_geometry_reset(self.boxes.data_ptr(), self.boxes.numel() // 6, ctypes.addressof(grids), ctypes.addressof(nbytes),
+                                    ctypes.addressof(rows), ctypes.addressof(Bs), n, _stream(self.boxes.device))
+        _lib.check(rc, "geometry_reset")
+
+
+class NeighborGrid:
+    """Cell grid over a stacked support cloud (see d3f_neighbor_grid_build); owns its device memory.
+    chain / level: build from the finished boxes of GridChain level `level`, inside the chain's memory
+    (d3f_neighbor_grid_build_boxed; the chain's reset launch and the producer of `supports` have run on this stream)."""
+
+    def __init__(self, supports, s_lens, radius, chain=None, level=0):
+        lib = _lib.load()
+        if chain is not None and chain.boxed[level]:
+            self._init_boxed(lib, supports, s_lens, radius, chain, level)
+            self._views(lib)
+            return
         self.supports = _tag(_req(supports, torch.float32, "supports", 2).contiguous(), supports)
         dev = self.supports.device
         self.Ns = self.supports.shape[0]
@@ -309,6 +371,27 @@ class NeighborGrid:
             rc = lib.d3f_neighbor_grid_build(self.supports.data_ptr(), self.Ns, self.s_lens.data_ptr(), self.B, self.radius,
                                              self.mem.data_ptr(), self.nbytes, _stream(dev))
         _lib.check(rc, "neighbor_grid_build")
+        self._views(lib)
+
+    def _init_boxed(self, lib, supports, s_lens, radius, chain, level):
+        self.supports = _tag(_req(supports, torch.float32, "supports", 2).contiguous(), supports)
+        dev = self.supports.device
+        self.Ns = self.supports.shape[0]
+        self.s_lens = as_lens(s_lens, dev)
+        self.B = self.s_lens.numel()
+        self.radius = float(radius)
+        if self.Ns != chain.rows[level] or self.B != chain.B:
+            raise ValueError("grid chain level %d was laid out for %d rows / %d clouds, not %d / %d"
+                             % (level, chain.rows[level], chain.B, self.Ns, self.B))
+        self.nbytes, self.mem = chain.nbytes[level], chain.mems[level]
+        self.form = chain.forms[level]
+        with _timed("nb_grid_build", dict(Ns=self.Ns), dev):
+            rc = lib.d3f_neighbor_grid_build_boxed(self.supports.data_ptr(), self.Ns, self.s_lens.data_ptr(), self.B, self.radius,
+                                                   chain.box(level).data_ptr(), self.mem.data_ptr(), self.nbytes, _stream(dev))
+        _lib.check(rc, "neighbor_grid_build_boxed")
+
+    def _views(self, lib):
+        dev = self.supports.device
         # support indices sorted by cell (a view into the grid object): a spatially coherent visiting order
         off = lib.d3f_neighbor_grid_order_offset(self.Ns, self.B)
         self.order = self.mem[off: off + 4 * max(self.Ns, 1)].view(torch.int32)

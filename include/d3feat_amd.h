@@ -115,6 +115,20 @@ int d3f_batch_grid_subsample_async_inplace(const float* const* clouds_dev, int N
  * total_dev i32[1] = 2 * sum m_b.  B = 1: the single self-pair; B > 1: several fragments in one stack. */
 int d3f_stack_self_pair(const float* pts, int M_cap, const int* lens_in_dev, int B, float* out, int* lens_out_dev,
                         int* total_dev, void* stream);
+/* The same two producers with bounding boxes handed along (see d3f_neighbor_grid_build_boxed).
+ * d3f_batch_grid_subsample_async_boxed is the capacity-mode subsampling of `points` or, when clouds_dev is given (points NULL), of
+ * the clouds in place.  bbox_out_dev (optional) u32[B][6] receives the boxes of the clouds it writes: the sort form accumulates
+ * them with atomic min / max into words pre-initialised by d3f_geometry_reset, the one-workgroup form stores them.  bbox_in_dev
+ * (optional) = finished boxes of its INPUT clouds: the sort form then skips its boxing pass.
+ * d3f_stack_self_pair_boxed: bbox_in_dev u32[B][6] = finished boxes of the B input clouds; bbox_out_dev u32[2B][6] receives them,
+ * one per copy (when M_cap cuts a cloud short its box is that of the whole cloud: a superset, which every consumer accepts).
+ * NULL box pointers give the plain calls. */
+int d3f_stack_self_pair_boxed(const float* pts, int M_cap, const int* lens_in_dev, int B, float* out, int* lens_out_dev,
+                              int* total_dev, const unsigned* bbox_in_dev, unsigned* bbox_out_dev, void* stream);
+int d3f_batch_grid_subsample_async_boxed(const float* points, const float* const* clouds_dev, int N_cap, const int* lens_dev,
+                                         int B, float dl, float* sub_points, int M_cap, int elem_cap, int elem_points_cap,
+                                         int* sub_lens_dev, int* status_dev, const unsigned* bbox_in_dev,
+                                         unsigned* bbox_out_dev, void* workspace, size_t workspace_bytes, void* stream);
 int d3f_batch_grid_subsample(const float* points, int N, const int* lens_dev, int B, float dl,
                              const float* features, int fdim, const int* classes, int ldim,
                              float* sub_points, float* sub_features, int* sub_classes, int* sub_lens_dev,
@@ -174,6 +188,24 @@ size_t d3f_neighbor_grid_bytes(int Ns, int B);
 size_t d3f_neighbor_grid_order_offset(int Ns, int B);
 int d3f_neighbor_grid_build(const float* supports, int Ns, const int* s_lens_dev, int B, float radius,
                             void* grid, size_t grid_bytes, void* stream);
+/* d3f_neighbor_grid_build from FINISHED bounding boxes: bbox_dev u32[B][6] (ordered-uint min xyz, max xyz) of the B clouds, gathered
+ * by the kernel that wrote `supports` (the *_boxed producers below and above).  Nothing reads the cloud to box it and no workgroup
+ * waits for another: the geometry is derived per workgroup.  Two forms, chosen on the host from the capacities only
+ * (d3f_neighbor_grid_boxed_form: 1 = small, 2 = large):
+ *   small  ceil(Ns / B) <= T (4096; environment D3F_NB_SMALL_T): ONE launch, one workgroup per cloud, cell counters / scan in LDS; the
+ *          cell budget of a cloud is min(d3f_neighbor_grid_build's, 8192) -- a cloud over it gets a coarser cell edge, as there
+ *   large  three launches (count, scan, scatter); its cell counters and scan ticket must have been cleared by d3f_geometry_reset
+ * The grid object serves every search exactly as one built by d3f_neighbor_grid_build; the order of the supports INSIDE a cell
+ * (atomics) is the only freedom, and no search result depends on it.
+ *   d3f_geometry_reset: ONE launch that prepares a whole chain of boxed calls -- n_boxes box rows get their initial values (the
+ *   producers accumulate into them with atomic min / max), and every large-form grid of the list (HOST arrays of n_grids <=
+ *   D3F_GRID_RESET_MAX grid objects with their byte sizes, Ns and B) has its counters cleared.  It must precede the producers. */
+#define D3F_GRID_RESET_MAX 8
+int d3f_neighbor_grid_boxed_form(int Ns, int B);
+int d3f_geometry_reset(unsigned* boxes_dev, int n_boxes, const void* const* grids, const size_t* grid_bytes, const int* Ns,
+                       const int* B, int n_grids, void* stream);
+int d3f_neighbor_grid_build_boxed(const float* supports, int Ns, const int* s_lens_dev, int B, float radius,
+                                  const unsigned* bbox_dev, void* grid, size_t grid_bytes, void* stream);
 int d3f_neighbor_grid_search(const void* grid, size_t grid_bytes, int Ns, const float* queries, int Nq,
                              const int* q_lens_dev, int B, float radius, int queries_are_supports,
                              int* out, int ld, int width, int pad_value, int cap, int first_only, float nn_hint,
