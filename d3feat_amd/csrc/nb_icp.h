@@ -232,6 +232,7 @@ __global__ void __launch_bounds__(256) icp_finish_kernel(const int* __restrict__
     for (int j = 0; j < ICP_NSUM; ++j) red[j][t] = acc[j];
     redn[t] = n;
     __syncthreads();
+    // (not d3f_block_sum: one tree for all ICP_NSUM + 1 sums shares its eight barriers among them)
     for (int s = 128; s > 0; s >>= 1) {
         if (t < s) {
 #pragma unroll
@@ -284,13 +285,8 @@ __global__ void __launch_bounds__(256) icp_count_kernel(const int* __restrict__ 
     __shared__ int red[256];
     int n = 0;
     for (int b = threadIdx.x; b < B; b += 256) n += done[b] ? 0 : 1;
-    red[threadIdx.x] = n;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) unfinished[0] = red[0];
+    n = d3f_block_sum(n, red);
+    if (threadIdx.x == 0) unfinished[0] = n;
 }
 
 // criteria_host: THREE doubles on the host, [max_correspondence_distance, relative_fitness, relative_rmse], read before the call returns

@@ -72,8 +72,7 @@ __global__ void __launch_bounds__(256) nb_overlap_kernel(const NbElem* __restric
             for (int j = 0; j < 9; ++j) {
                 for (int t = rlo[j]; t < rhi[j]; ++t) {
                     const float4 sp = sorted[t];
-                    const float dx = __fsub_rn(qx, sp.x), dy = __fsub_rn(qy, sp.y), dz = __fsub_rn(qz, sp.z);
-                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                    const float d2 = rc_d2(qx, qy, qz, sp.x, sp.y, sp.z);
                     const int si = __float_as_int(sp.w);
                     if (d2 < r2 && (d2 < bd2 || (d2 == bd2 && si < bidx))) { bd2 = d2; bidx = si; }
                 }

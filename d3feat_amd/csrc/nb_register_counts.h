@@ -79,20 +79,12 @@ __device__ __forceinline__ int rc_nearest(const NbElem& e, const int* __restrict
     for (int j = 0; j < 9; ++j) {
         for (int t = rlo[j]; t < rhi[j]; ++t) {
             const float4 sp = sorted[t];
-            const float dx = __fsub_rn(qx, sp.x), dy = __fsub_rn(qy, sp.y), dz = __fsub_rn(qz, sp.z);
-            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+            const float d2 = rc_d2(qx, qy, qz, sp.x, sp.y, sp.z);
             const int si = __float_as_int(sp.w) - first;               // < 0: a row this count does not use
             if (si >= 0 && d2 < r2 && (d2 < bd2 || (d2 == bd2 && si < bidx))) { bd2 = d2; bidx = si; }
         }
     }
     return bidx;
-}
-
-// p = M x + t with the fmaf nest of nb_score_kernel
-__device__ __forceinline__ void rc_apply(const float* M, float x, float y, float z, float& qx, float& qy, float& qz) {
-    qx = fmaf(M[0], x, fmaf(M[1], y, fmaf(M[2], z, M[3])));
-    qy = fmaf(M[4], x, fmaf(M[5], y, fmaf(M[6], z, M[7])));
-    qz = fmaf(M[8], x, fmaf(M[9], y, fmaf(M[10], z, M[11])));
 }
 
 // grid (slices of RC_SLICE hypotheses, counts, pairs).  cnt / sd2 [P, n, max_validation]: every entry that rc_select_kernel reads has
@@ -149,14 +141,6 @@ __global__ void __launch_bounds__(256) rc_score_kernel(const NbElem* __restrict_
     }
 }
 
-// better(a, b): larger count, then smaller sumd2, then earlier place in the list (= earlier iteration)
-struct RcBest { int c; unsigned long long s; int v; };
-__device__ __forceinline__ bool rc_better(const RcBest& x, const RcBest& y) {
-    if (x.c != y.c) return x.c > y.c;
-    if (x.s != y.s) return x.s < y.s;
-    return x.v < y.v;
-}
-
 // grid (counts, pairs)
 __global__ void __launch_bounds__(256) rc_select_kernel(const NbElem* __restrict__ el, const int* __restrict__ soffs,
                                                         const int* __restrict__ cell_start, const int* __restrict__ cell_base,
@@ -173,18 +157,10 @@ __global__ void __launch_bounds__(256) rc_select_kernel(const NbElem* __restrict
             const RcBest x{L.cnt[pc * L.max_validation + v], L.sd2[pc * L.max_validation + v], v};
             if (rc_better(x, me)) me = x;
         }
-        __syncthreads();                                                 // the previous pair is done with red and M
-        red[threadIdx.x] = me;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s && rc_better(red[threadIdx.x + s], red[threadIdx.x])) red[threadIdx.x] = red[threadIdx.x + s];
-            __syncthreads();
-        }
-        const RcBest w = red[0];
+        const RcBest w = rc_block_best(me, red);                         // (its first barrier: the previous pair is done with red and M)
         int* near = out.nearest ? out.nearest + (size_t)p * prm.total + prm.off[c] : nullptr;
         if (V <= 0) {   // nothing validated: the identity, no correspondences
-            if (threadIdx.x < 12) out.T_out[pc * 12 + threadIdx.x] = (threadIdx.x % 5 == 0) ? 1.f : 0.f;
-            if (threadIdx.x == 0) { out.inliers[pc] = 0; out.sumd2[pc] = 0ull; out.best_iteration[pc] = -1; }
+            rc_store_none(out.T_out + pc * 12, out.inliers + pc, out.sumd2 + pc, out.best_iteration + pc);
             if (near)
                 for (int i = threadIdx.x; i < kc; i += 256) near[i] = -1;
             continue;

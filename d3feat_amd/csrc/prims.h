@@ -243,6 +243,22 @@ __device__ __forceinline__ void d3f_box_accum_block(unsigned* __restrict__ bbox,
     }
 }
 
+// ---- workgroup sum by a fixed tree ----------------------------------------------------------------------------------
+// Sum of v over the 256 threads of the workgroup (red: 256 T's of LDS); the result in every thread.  The order is part of the float64
+// results of its callers (d3f_pose_errors, d3f_validation_pairs): strides 128 .. 1, red[t] += red[t + s] for t < s -- no wave shuffles.
+// The first barrier ends an earlier use of red, so calls may follow one another.
+template <class T>
+__device__ __forceinline__ T d3f_block_sum(T v, T* red) {
+    __syncthreads();
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
+
 // ---- one-launch exclusive scan --------------------------------------------------------------------------------------
 __device__ __forceinline__ int d3f_block_excl_scan_256(int v, int* lds4, int* total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;

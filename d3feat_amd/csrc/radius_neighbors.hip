@@ -23,6 +23,7 @@
 //           ranks are stored straight into the output row.  first_only keeps a running (d2, index) minimum instead.
 //   Sizes come from the device lens arrays (capacity mode): Nq / Ns only bound grids and buffers.
 #include "prims.h"
+#include "rc_shared.h"
 #include <cstdlib>
 
 struct NbElem {
@@ -955,9 +956,8 @@ __global__ void __launch_bounds__(256) nb_score_kernel(const NbElem* __restrict_
     const int v = (int)(tid / Ns), i = (int)(tid % Ns);
     const float* M = T + (size_t)v * 12;
     const float sx = src[3 * (size_t)i], sy = src[3 * (size_t)i + 1], sz = src[3 * (size_t)i + 2];
-    const float qx = fmaf(M[0], sx, fmaf(M[1], sy, fmaf(M[2], sz, M[3])));
-    const float qy = fmaf(M[4], sx, fmaf(M[5], sy, fmaf(M[6], sz, M[7])));
-    const float qz = fmaf(M[8], sx, fmaf(M[9], sy, fmaf(M[10], sz, M[11])));
+    float qx, qy, qz;
+    rc_apply(M, sx, sy, sz, qx, qy, qz);
     const NbElem e = el[0];
     int cx, cy, cz;
     nb_cell_of(e, qx, qy, qz, cx, cy, cz);
@@ -975,8 +975,7 @@ __global__ void __launch_bounds__(256) nb_score_kernel(const NbElem* __restrict_
             const int lo = d3f_scan_at(cell_start, cell_base, rowbase + x0), hi = d3f_scan_at(cell_start, cell_base, rowbase + x1 + 1);
             for (int t = lo; t < hi; ++t) {
                 const float4 sp = sorted[t];
-                const float dx = __fsub_rn(qx, sp.x), dy = __fsub_rn(qy, sp.y), dz = __fsub_rn(qz, sp.z);
-                const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                const float d2 = rc_d2(qx, qy, qz, sp.x, sp.y, sp.z);
                 const int si = __float_as_int(sp.w);
                 if (d2 < r2 && (d2 < bd2 || (d2 == bd2 && si < bidx))) { bd2 = d2; bidx = si; }
             }

@@ -17,11 +17,50 @@
 // scoring of the validated hypotheses against the neighbour grid of radius_neighbors.hip (d3f_neighbor_grid_score).
 #include "prims.h"
 #include "rc_shared.h"
+#include <type_traits>
 
 // ---------------------------------------------------------------------------------------------------------------------
 // nearest feature: key[i] = min_j (||A_i - B_j||^2 bits << 32 | j)
 // ---------------------------------------------------------------------------------------------------------------------
 #define RG_TB 128   // B rows per LDS tile
+
+// f(std::integral_constant<int, C>()) for the descriptor width C of a call that has checked it: 16, 32 or 64
+template <class F>
+static inline void rg_dispatch_C(int C, F&& f) {
+    if (C == 16) f(std::integral_constant<int, 16>());
+    else if (C == 32) f(std::integral_constant<int, 32>());
+    else f(std::integral_constant<int, 64>());
+}
+
+// ||a - b||^2 of two descriptors of C floats: the fmaf chain over c ascending that every descriptor distance of this file is, bit for bit
+template <int C>
+__device__ __forceinline__ float rg_desc_d2(const float* a, const float* b) {
+    float d2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float d = a[c] - b[c];
+        d2 = fmaf(d, d, d2);
+    }
+    return d2;
+}
+
+// The rows [j0, j1) of B through the LDS tile, RG_TB at a time, the whole workgroup; a: this thread's descriptor.  best / bj come in
+// with the caller's start values and leave as the smallest d2 and its row.  (Both passes of rp_nn_pass; rg_feature_nn_kernel holds the
+// same loop written out, for its speed.)
+template <int C>
+__device__ __forceinline__ void rg_tile_scan(const float* a, const float* __restrict__ B, int j0, int j1, int ldb, float* tile,
+                                             float& best, int& bj) {
+    for (int t0 = j0; t0 < j1; t0 += RG_TB) {
+        const int nt = min(RG_TB, j1 - t0);
+        __syncthreads();
+        for (int e = threadIdx.x; e < nt * C; e += 256) tile[e] = B[(size_t)(t0 + e / C) * ldb + (e % C)];
+        __syncthreads();
+        for (int j = 0; j < nt; ++j) {
+            const float d2 = rg_desc_d2<C>(a, tile + j * C);
+            if (d2 < best) { best = d2; bj = t0 + j; }   // strict: ties keep the lowest column
+        }
+    }
+}
 
 template <int C>
 __global__ void __launch_bounds__(256) rg_feature_nn_kernel(const float* __restrict__ A, int Na, int lda,
@@ -36,18 +75,15 @@ __global__ void __launch_bounds__(256) rg_feature_nn_kernel(const float* __restr
     const int j0 = blockIdx.y * per, j1 = min(Nb, j0 + per);
     float best = 3.402823466e38f;
     int bj = 0x7fffffff;
+    // rg_tile_scan's loop, written out: through the helper this kernel compiles to other code and d3f_feature_nn measures 2 % (C = 64)
+    // to 35 % (C = 16, 1000 rows) slower on an MI355X (profiles/pair_plumbing_feature_nn.json)
     for (int t0 = j0; t0 < j1; t0 += RG_TB) {
         const int nt = min(RG_TB, j1 - t0);
         __syncthreads();
         for (int e = threadIdx.x; e < nt * C; e += 256) tile[e] = B[(size_t)(t0 + e / C) * ldb + (e % C)];
         __syncthreads();
         for (int j = 0; j < nt; ++j) {
-            float d2 = 0.f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float d = a[c] - tile[j * C + c];
-                d2 = fmaf(d, d, d2);
-            }
+            const float d2 = rg_desc_d2<C>(a, tile + j * C);
             if (d2 < best) { best = d2; bj = t0 + j; }   // strict: ties keep the lowest column
         }
     }
@@ -85,9 +121,7 @@ extern "C" int d3f_feature_nn(const float* A, int Na, int lda, const float* B, i
         if (by > by_max) by = by_max;
         if (by < 1) by = 1;
         dim3 grid(bx, by);
-        if (C == 16) rg_feature_nn_kernel<16><<<grid, 256, 0, stream>>>(A, Na, lda, B, Nb, ldb, key);
-        else if (C == 32) rg_feature_nn_kernel<32><<<grid, 256, 0, stream>>>(A, Na, lda, B, Nb, ldb, key);
-        else rg_feature_nn_kernel<64><<<grid, 256, 0, stream>>>(A, Na, lda, B, Nb, ldb, key);
+        rg_dispatch_C(C, [&](auto c) { rg_feature_nn_kernel<decltype(c)::value><<<grid, 256, 0, stream>>>(A, Na, lda, B, Nb, ldb, key); });
     }
     rg_unpack_kernel<<<d3f_cdiv(Na, 256), 256, 0, stream>>>(key, Na, idx, d2_out);
     D3F_LAUNCH_CHECK();
@@ -307,21 +341,7 @@ __device__ __forceinline__ void rp_nn_pass(const float* __restrict__ A, int Na, 
         for (int c = 0; c < C; ++c) a[c] = (i < Na) ? A[(size_t)i * lda + c] : 0.f;
         float best = 3.402823466e38f;
         int bj = -1;
-        for (int t0 = 0; t0 < Nb; t0 += RG_TB) {
-            const int nt = min(RG_TB, Nb - t0);
-            __syncthreads();
-            for (int e = threadIdx.x; e < nt * C; e += 256) tile[e] = B[(size_t)(t0 + e / C) * ldb + (e % C)];
-            __syncthreads();
-            for (int j = 0; j < nt; ++j) {
-                float d2 = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float d = a[c] - tile[j * C + c];
-                    d2 = fmaf(d, d, d2);
-                }
-                if (d2 < best) { best = d2; bj = t0 + j; }   // strict: ties keep the lowest column
-            }
-        }
+        rg_tile_scan<C>(a, B, 0, Nb, ldb, tile, best, bj);
         if (i < Na) out[i] = bj;
     }
     __syncthreads();
@@ -340,24 +360,14 @@ __device__ __forceinline__ int rp_block_prefix(bool flag, int* wsum, int& total)
     return base + __popcll(bal & d3f_lanemask_lt());
 }
 
-// p = M x + t with the fmaf nest of nb_score_kernel
-__device__ __forceinline__ void rp_apply(const float* __restrict__ M, float x, float y, float z, float& qx, float& qy, float& qz) {
-    qx = fmaf(M[0], x, fmaf(M[1], y, fmaf(M[2], z, M[3])));
-    qy = fmaf(M[4], x, fmaf(M[5], y, fmaf(M[6], z, M[7])));
-    qz = fmaf(M[8], x, fmaf(M[9], y, fmaf(M[10], z, M[11])));
-}
-// nb_score_kernel's squared distance: no contraction, (dx^2 + dy^2) + dz^2
-__device__ __forceinline__ float rp_d2(float qx, float qy, float qz, float x, float y, float z) {
-    const float dx = __fsub_rn(qx, x), dy = __fsub_rn(qy, y), dz = __fsub_rn(qz, z);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
+// (rc_apply, rc_d2: the transform and the metric of nb_score_kernel, rc_shared.h)
 // nearest of the n points pts[3 * j ..] strictly inside r2, lowest j on ties (the scan is ascending); -1 for none.  The grid walk of
 // nb_score_kernel visits a superset of the points inside the radius and keeps the same minimum.
 __device__ __forceinline__ int rp_nearest(const float* pts, int n, float qx, float qy, float qz, float r2, float& bd2) {
     int bidx = -1;
     bd2 = 3.4e38f;
     for (int j = 0; j < n; ++j) {
-        const float d2 = rp_d2(qx, qy, qz, pts[3 * j], pts[3 * j + 1], pts[3 * j + 2]);
+        const float d2 = rc_d2(qx, qy, qz, pts[3 * j], pts[3 * j + 1], pts[3 * j + 2]);
         if (d2 < r2 && d2 < bd2) { bd2 = d2; bidx = j; }
     }
     return bidx;
@@ -397,8 +407,8 @@ __global__ void __launch_bounds__(256) rp_match_kernel(const float* __restrict__
             if (mutual) { mutual[((size_t)p * Kmax + slot) * 2] = i; mutual[((size_t)p * Kmax + slot) * 2 + 1] = j; }
             if (gt) {   // gt takes the TARGET frame into the SOURCE frame (evaluate.py:70-77)
                 float qx, qy, qz;
-                rp_apply(gt + (size_t)p * 12, T[(size_t)j * ld], T[(size_t)j * ld + 1], T[(size_t)j * ld + 2], qx, qy, qz);
-                mine_gt += rp_d2(qx, qy, qz, S[(size_t)i * ld], S[(size_t)i * ld + 1], S[(size_t)i * ld + 2]) < thr2 ? 1 : 0;
+                rc_apply(gt + (size_t)p * 12, T[(size_t)j * ld], T[(size_t)j * ld + 1], T[(size_t)j * ld + 2], qx, qy, qz);
+                mine_gt += rc_d2(qx, qy, qz, S[(size_t)i * ld], S[(size_t)i * ld + 1], S[(size_t)i * ld + 2]) < thr2 ? 1 : 0;
             }
         }
     }
@@ -498,7 +508,7 @@ __global__ void __launch_bounds__(256) rp_score_kernel(const float* __restrict__
     for (int e = threadIdx.x; e < nv * a.n; e += 256) {
         const int v = e / a.n, i = e - v * a.n;
         float qx, qy, qz, bd2;
-        rp_apply(M + 12 * v, spt[3 * i], spt[3 * i + 1], spt[3 * i + 2], qx, qy, qz);
+        rc_apply(M + 12 * v, spt[3 * i], spt[3 * i + 1], spt[3 * i + 2], qx, qy, qz);
         if (rp_nearest(tpt, b.n, qx, qy, qz, r2, bd2) >= 0) {
             atomicAdd(&c_l[v], 1);
             atomicAdd(&s_l[v], (unsigned long long)((double)bd2 * 4294967296.0));
@@ -511,14 +521,7 @@ __global__ void __launch_bounds__(256) rp_score_kernel(const float* __restrict__
     }
 }
 
-// better(a, b): larger count, then smaller sumd2, then earlier place in the list (= earlier iteration)
-struct RpBest { int c; unsigned long long s; int v; };
-__device__ __forceinline__ bool rp_better(const RpBest& x, const RpBest& y) {
-    if (x.c != y.c) return x.c > y.c;
-    if (x.s != y.s) return x.s < y.s;
-    return x.v < y.v;
-}
-
+// (RcBest, rc_better, rc_block_best, rc_store_none: the choice of the winner, rc_shared.h)
 __global__ void __launch_bounds__(256) rp_select_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
                                                         const int* __restrict__ count, const int* __restrict__ pairs, int nk, int Kmax,
                                                         const float* __restrict__ Tlist, const int* __restrict__ itlist,
@@ -528,25 +531,18 @@ __global__ void __launch_bounds__(256) rp_select_kernel(const float* __restrict_
                                                         unsigned long long* __restrict__ sumd2, int* __restrict__ best_iteration,
                                                         int* __restrict__ nearest) {
     __shared__ float tpt[3 * D3F_PAIRS_KMAX];
-    __shared__ RpBest red[256];
+    __shared__ RcBest red[256];
     __shared__ float M[12];
     const int p = blockIdx.x, V = validations[p];
-    RpBest me{-1, ~0ull, 0x7fffffff};
+    RcBest me{-1, ~0ull, 0x7fffffff};
     for (int v = threadIdx.x; v < V; v += 256) {
-        const RpBest c{cnt[(size_t)p * max_validation + v], sd2[(size_t)p * max_validation + v], v};
-        if (rp_better(c, me)) me = c;
+        const RcBest c{cnt[(size_t)p * max_validation + v], sd2[(size_t)p * max_validation + v], v};
+        if (rc_better(c, me)) me = c;
     }
-    red[threadIdx.x] = me;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s && rp_better(red[threadIdx.x + s], red[threadIdx.x])) red[threadIdx.x] = red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const RpBest w = red[0];
+    const RcBest w = rc_block_best(me, red);
     int* near = nearest + (size_t)p * Kmax;
     if (V <= 0) {   // nothing validated: the identity, no correspondences
-        if (threadIdx.x < 12) T_out[(size_t)p * 12 + threadIdx.x] = (threadIdx.x % 5 == 0) ? 1.f : 0.f;
-        if (threadIdx.x == 0) { inliers[p] = 0; sumd2[p] = 0ull; best_iteration[p] = -1; }
+        rc_store_none(T_out + (size_t)p * 12, inliers + p, sumd2 + p, best_iteration + p);
         for (int i = threadIdx.x; i < Kmax; i += 256) near[i] = -1;
         return;
     }
@@ -560,7 +556,7 @@ __global__ void __launch_bounds__(256) rp_select_kernel(const float* __restrict_
         int j = -1;
         if (i < a.n) {
             float qx, qy, qz, bd2;
-            rp_apply(M, S[(size_t)i * ld], S[(size_t)i * ld + 1], S[(size_t)i * ld + 2], qx, qy, qz);
+            rc_apply(M, S[(size_t)i * ld], S[(size_t)i * ld + 1], S[(size_t)i * ld + 2], qx, qy, qz);
             j = rp_nearest(tpt, b.n, qx, qy, qz, r2, bd2);
         }
         near[i] = j;
@@ -601,9 +597,10 @@ extern "C" int d3f_register_pairs(const float* kp, int n_blocks, int K, int ld, 
     unsigned long long* sd2 = ar.take<unsigned long long>(pv);
     if (!ar.ok) return D3F_ERR_WORKSPACE;
     const float r = max_correspondence_distance, thr2 = distance_threshold * distance_threshold;
-    if (C == 16) rp_match_kernel<16><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, gt, thr2, nn_st, mutual_count, mutual, gt_inliers);
-    else if (C == 32) rp_match_kernel<32><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, gt, thr2, nn_st, mutual_count, mutual, gt_inliers);
-    else rp_match_kernel<64><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, gt, thr2, nn_st, mutual_count, mutual, gt_inliers);
+    rg_dispatch_C(C, [&](auto c) {
+        rp_match_kernel<decltype(c)::value><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, gt, thr2, nn_st,
+                                                                   mutual_count, mutual, gt_inliers);
+    });
     rp_hypotheses_kernel<<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Kmax, nn_st, ransac_n, r, edge_similarity,
                                                 checker_distance, seed, max_iteration, max_validation, Tlist, itlist, validations, iterations);
     rp_score_kernel<<<dim3(P, d3f_cdiv(max_validation, RP_SLICE)), 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, Kmax, Tlist,
@@ -631,11 +628,11 @@ extern "C" int d3f_register_pairs(const float* kp, int n_blocks, int K, int ld, 
 // d2 < thr * thr (the rounded product); every operation rounded on its own (no contraction), so a numpy restatement has the same bits.
 struct RpRepeatParams {
     double thr2;
-    int k[D3F_REPEAT_COUNTS_MAX];   // strictly ascending
-    int n, moved;                   // moved 0: gt takes the target frame into the source frame (target rows moved); 1: the source rows
+    RcCounts cnt;                   // k and n are read
+    int moved;                      // moved 0: gt takes the target frame into the source frame (target rows moved); 1: the source rows
 };
 
-__device__ __forceinline__ void rp_apply_f64(const double* __restrict__ M, double x, double y, double z, double& qx, double& qy, double& qz) {
+__device__ __forceinline__ void rp_move_f64(const double* __restrict__ M, double x, double y, double z, double& qx, double& qy, double& qz) {
     qx = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(M[0], x), __dmul_rn(M[1], y)), __dmul_rn(M[2], z)), M[3]);
     qy = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(M[4], x), __dmul_rn(M[5], y)), __dmul_rn(M[6], z)), M[7]);
     qz = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(M[8], x), __dmul_rn(M[9], y)), __dmul_rn(M[10], z)), M[11]);
@@ -649,7 +646,7 @@ __global__ void __launch_bounds__(256) rp_repeat_kernel(const float* __restrict_
     __shared__ double sx[D3F_PAIRS_KMAX], sy[D3F_PAIRS_KMAX], sz[D3F_PAIRS_KMAX];
     __shared__ double M[12];
     __shared__ int wsum[4 * D3F_REPEAT_COUNTS_MAX];
-    const int p = blockIdx.x, nk = prm.k[prm.n - 1];
+    const int p = blockIdx.x, nk = prm.cnt.k[prm.cnt.n - 1];
     const RpRows a = rp_rows(count, pairs, p, 0, n_blocks, K, nk), b = rp_rows(count, pairs, p, 1, n_blocks, K, nk);
     const float* S = kp + ((size_t)a.blk * K + a.r0) * ld;
     const float* T = kp + ((size_t)b.blk * K + b.r0) * ld;
@@ -659,7 +656,7 @@ __global__ void __launch_bounds__(256) rp_repeat_kernel(const float* __restrict_
     for (int j = threadIdx.x; j < a.n; j += 256) {
         const float* s = S + (size_t)(a.n - 1 - j) * ld;
         double x = (double)s[0], y = (double)s[1], z = (double)s[2];
-        if (prm.moved) rp_apply_f64(M, x, y, z, x, y, z);
+        if (prm.moved) rp_move_f64(M, x, y, z, x, y, z);
         sx[j] = x; sy[j] = y; sz[j] = z;
     }
     double qx[TS], qy[TS], qz[TS], best[TS];
@@ -671,13 +668,13 @@ __global__ void __launch_bounds__(256) rp_repeat_kernel(const float* __restrict_
         if (r < b.n) {
             const float* t = T + (size_t)(b.n - 1 - r) * ld;
             qx[s] = (double)t[0]; qy[s] = (double)t[1]; qz[s] = (double)t[2];
-            if (!prm.moved) rp_apply_f64(M, qx[s], qy[s], qz[s], qx[s], qy[s], qz[s]);
+            if (!prm.moved) rp_move_f64(M, qx[s], qy[s], qz[s], qx[s], qy[s], qz[s]);
         }
     }
     __syncthreads();
     int j = 0;
-    for (int c = 0; c < prm.n; ++c) {
-        const int kc = prm.k[c], je = min(kc, a.n), re = min(kc, b.n);   // a count beyond the source rows: the whole walk
+    for (int c = 0; c < prm.cnt.n; ++c) {
+        const int kc = prm.cnt.k[c], je = min(kc, a.n), re = min(kc, b.n);   // a count beyond the source rows: the whole walk
         for (; j < je; ++j) {
             const double x = sx[j], y = sy[j], z = sz[j];
 #pragma unroll
@@ -693,9 +690,9 @@ __global__ void __launch_bounds__(256) rp_repeat_kernel(const float* __restrict_
         if (d3f_lane() == 0) wsum[(threadIdx.x >> 6) * D3F_REPEAT_COUNTS_MAX + c] = hits;
     }
     __syncthreads();
-    if ((int)threadIdx.x < prm.n) {
+    if ((int)threadIdx.x < prm.cnt.n) {
         const int c = threadIdx.x;
-        repeat[(size_t)p * prm.n + c] = (wsum[c] + wsum[D3F_REPEAT_COUNTS_MAX + c]) + (wsum[2 * D3F_REPEAT_COUNTS_MAX + c] + wsum[3 * D3F_REPEAT_COUNTS_MAX + c]);
+        repeat[(size_t)p * prm.cnt.n + c] = (wsum[c] + wsum[D3F_REPEAT_COUNTS_MAX + c]) + (wsum[2 * D3F_REPEAT_COUNTS_MAX + c] + wsum[3 * D3F_REPEAT_COUNTS_MAX + c]);
     }
 }
 
@@ -704,14 +701,8 @@ __global__ void __launch_bounds__(256) rp_repeat_sum_kernel(const int* __restric
     for (int c = 0; c < n; ++c) {
         long long mine = 0;
         for (int p = threadIdx.x; p < P; p += 256) mine += repeat[(size_t)p * n + c];
-        red[threadIdx.x] = mine;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) totals[c] = red[0];
-        __syncthreads();
+        mine = d3f_block_sum(mine, red);
+        if (threadIdx.x == 0) totals[c] = mine;
     }
 }
 
@@ -719,24 +710,16 @@ extern "C" int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int
                                        const double* gt_dev, int moved, const double* threshold_host, const int* num_keypts_host,
                                        int n_counts, int* repeat_dev, int64_t* totals_dev, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (P < 0 || n_blocks < 1 || K < 1 || ld < 3 || n_counts < 1 || n_counts > D3F_REPEAT_COUNTS_MAX || (moved != 0 && moved != 1))
-        return D3F_ERR_ARG;
-    if (!threshold_host || !num_keypts_host) return D3F_ERR_ARG;
+    if (P < 0 || n_blocks < 1 || K < 1 || ld < 3 || (moved != 0 && moved != 1)) return D3F_ERR_ARG;
+    RpRepeatParams prm;
+    if (!threshold_host || !rc_counts(num_keypts_host, n_counts, D3F_PAIRS_KMAX, prm.cnt)) return D3F_ERR_ARG;
     const double thr = *threshold_host;
     if (!(thr > 0.0)) return D3F_ERR_ARG;   // NaN too
-    RpRepeatParams prm;
-    for (int c = 0; c < D3F_REPEAT_COUNTS_MAX; ++c) prm.k[c] = 0;
-    for (int c = 0; c < n_counts; ++c) {
-        const int k = num_keypts_host[c];
-        if (k < 1 || k > D3F_PAIRS_KMAX || (c > 0 && k <= num_keypts_host[c - 1])) return D3F_ERR_ARG;
-        prm.k[c] = k;
-    }
     prm.thr2 = thr * thr;
-    prm.n = n_counts;
     prm.moved = moved;
     if (P == 0) return D3F_OK;
     if (!kp || !count_dev || !pairs_dev || !gt_dev || !repeat_dev) return D3F_ERR_ARG;
-    const int rows = prm.k[n_counts - 1] < K ? prm.k[n_counts - 1] : K;   // most rows of a block any pair uses
+    const int rows = prm.cnt.k[n_counts - 1] < K ? prm.cnt.k[n_counts - 1] : K;   // most rows of a block any pair uses
     switch (d3f_cdiv(rows, 256)) {
         case 1: rp_repeat_kernel<1><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, gt_dev, prm, repeat_dev); break;
         case 2: rp_repeat_kernel<2><<<P, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, gt_dev, prm, repeat_dev); break;

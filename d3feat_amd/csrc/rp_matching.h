@@ -1,5 +1,5 @@
 // Feature-matching recall of every pair at every keypoint count (d3f_match_pairs; geometric_registration/evaluate.py:45-50, 67-82).
-// (included by registration.hip after the rp_* kernels: rp_rows, rp_apply, rp_d2 and RG_TB are theirs.)
+// (included by registration.hip after the rp_* kernels: rp_rows, rg_desc_d2 and RG_TB are theirs; RcCounts, rc_apply, rc_d2: rc_shared.h.)
 //
 // For each requested count k: the last min(count, k) rows of both blocks, the nearest descriptor in both directions, the mutually
 // nearest pairs and how many of them lie inside the threshold under the ground truth -- what rp_match_kernel computes for ONE count
@@ -19,12 +19,6 @@
 // nothing is cleared; no atomics, no workgroup waits for another, the launch count does not depend on P or on the counts.
 #pragma once
 
-struct MpParams {
-    int k[D3F_REPEAT_COUNTS_MAX];     // strictly ascending
-    int off[D3F_REPEAT_COUNTS_MAX];   // off[c] = k[0] + ... + k[c-1]
-    int n, total;                     // total = sum of k
-};
-
 // block pairs[p][which] and the rows it holds, clamp(count, 0, K); no rows for an index outside [0, n_blocks) (rp_rows)
 __device__ __forceinline__ RpRows mp_block(const int* __restrict__ count, const int* __restrict__ pairs, int p, int which, int n_blocks, int K) {
     return rp_rows(count, pairs, p, which, n_blocks, K, K);
@@ -33,7 +27,7 @@ __device__ __forceinline__ RpRows mp_block(const int* __restrict__ count, const 
 template <int C>
 __global__ void __launch_bounds__(256) mp_nearest_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
                                                          const int* __restrict__ count, const int* __restrict__ pairs, int P,
-                                                         MpParams prm, int* __restrict__ ws) {
+                                                         RcCounts prm, int* __restrict__ ws) {
     __shared__ __attribute__((aligned(16))) float tile[RG_TB * C];
     const int dir = blockIdx.y, kmax = prm.k[prm.n - 1];
     const int r = blockIdx.x * 256 + threadIdx.x;                                  // rank of this thread's query
@@ -68,12 +62,7 @@ __global__ void __launch_bounds__(256) mp_nearest_kernel(const float* __restrict
             while (j < nt) {                                                        // c < prm.n here: the last count ends the walk
                 const int je = min(nt, min(prm.k[c], no) - t0);
                 for (; j < je; ++j) {
-                    float d2 = 0.f;
-#pragma unroll
-                    for (int cc = 0; cc < C; ++cc) {
-                        const float d = a[cc] - tile[j * C + cc];
-                        d2 = fmaf(d, d, d2);
-                    }
+                    const float d2 = rg_desc_d2<C>(a, tile + j * C);
                     if (d2 <= best) { best = d2; bj = t0 + j; }                     // descending rows: ties end on the lowest row
                 }
                 flush(t0 + j);
@@ -86,9 +75,9 @@ __global__ void __launch_bounds__(256) mp_nearest_kernel(const float* __restrict
 // grid (counts, pairs).  st / ts: the two lists of mp_nearest_kernel for the pair.
 __global__ void __launch_bounds__(256) mp_count_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
                                                        const int* __restrict__ count, const int* __restrict__ pairs, int P,
-                                                       const float* __restrict__ gt, float thr2, MpParams prm, const int* __restrict__ ws,
+                                                       const float* __restrict__ gt, float thr2, RcCounts prm, const int* __restrict__ ws,
                                                        int* __restrict__ mutual_count, int* __restrict__ gt_inliers) {
-    __shared__ int red_m[256], red_g[256];
+    __shared__ int red[256];
     const int c = blockIdx.x, kc = prm.k[c];
     for (int p = blockIdx.y; p < P; p += gridDim.y) {
         const RpRows a = mp_block(count, pairs, p, 0, n_blocks, K), b = mp_block(count, pairs, p, 1, n_blocks, K);
@@ -106,45 +95,23 @@ __global__ void __launch_bounds__(256) mp_count_kernel(const float* __restrict__
                     const float* t = T + (size_t)(b.n - 1 - j) * ld;
                     const float* s = S + (size_t)(a.n - 1 - i) * ld;
                     float qx, qy, qz;
-                    rp_apply(gt + (size_t)p * 12, t[0], t[1], t[2], qx, qy, qz);
-                    ng += rp_d2(qx, qy, qz, s[0], s[1], s[2]) < thr2 ? 1 : 0;
+                    rc_apply(gt + (size_t)p * 12, t[0], t[1], t[2], qx, qy, qz);
+                    ng += rc_d2(qx, qy, qz, s[0], s[1], s[2]) < thr2 ? 1 : 0;
                 }
             }
         }
-        red_m[threadIdx.x] = nm;
-        red_g[threadIdx.x] = ng;
-        __syncthreads();
-        for (int s = 128; s > 0; s >>= 1) {
-            if ((int)threadIdx.x < s) { red_m[threadIdx.x] += red_m[threadIdx.x + s]; red_g[threadIdx.x] += red_g[threadIdx.x + s]; }
-            __syncthreads();
-        }
+        nm = d3f_block_sum(nm, red);                                                // (its first barrier: the previous pair is done with red)
+        ng = d3f_block_sum(ng, red);
         if (threadIdx.x == 0) {
-            mutual_count[(size_t)p * prm.n + c] = red_m[0];
-            if (gt) gt_inliers[(size_t)p * prm.n + c] = red_g[0];
+            mutual_count[(size_t)p * prm.n + c] = nm;
+            if (gt) gt_inliers[(size_t)p * prm.n + c] = ng;
         }
-        __syncthreads();
     }
-}
-
-// k, off, total from the host list; false when a count or n_counts is out of range or the counts do not strictly ascend
-static inline bool mp_params(const int* num_keypts_host, int n_counts, MpParams& prm) {
-    if (!num_keypts_host || n_counts < 1 || n_counts > D3F_REPEAT_COUNTS_MAX) return false;
-    prm.n = n_counts;
-    prm.total = 0;
-    for (int c = 0; c < D3F_REPEAT_COUNTS_MAX; ++c) prm.k[c] = prm.off[c] = 0;
-    for (int c = 0; c < n_counts; ++c) {
-        const int k = num_keypts_host[c];
-        if (k < 1 || k > D3F_MATCH_KMAX || (c > 0 && k <= num_keypts_host[c - 1])) return false;
-        prm.k[c] = k;
-        prm.off[c] = prm.total;
-        prm.total += k;
-    }
-    return true;
 }
 
 extern "C" size_t d3f_match_pairs_workspace_bytes(int P, const int* num_keypts_host, int n_counts) {
-    MpParams prm;
-    if (P < 0 || !mp_params(num_keypts_host, n_counts, prm)) return 0;
+    RcCounts prm;
+    if (P < 0 || !rc_counts(num_keypts_host, n_counts, D3F_MATCH_KMAX, prm)) return 0;
     return d3f_align((size_t)(P > 0 ? P : 1) * 2 * (size_t)prm.total * 4) + 256;
 }
 
@@ -152,9 +119,9 @@ extern "C" int d3f_match_pairs(const float* kp, int n_blocks, int K, int ld, int
                                const float* gt, float distance_threshold, const int* num_keypts_host, int n_counts, int* mutual_count,
                                int* gt_inliers, void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    MpParams prm;
+    RcCounts prm;
     if (P < 0 || n_blocks < 1 || K < 1 || (C != 16 && C != 32 && C != 64) || ld < C + 3) return D3F_ERR_ARG;
-    if (!mp_params(num_keypts_host, n_counts, prm) || !(distance_threshold == distance_threshold)) return D3F_ERR_ARG;
+    if (!rc_counts(num_keypts_host, n_counts, D3F_MATCH_KMAX, prm) || !(distance_threshold == distance_threshold)) return D3F_ERR_ARG;
     if ((gt != nullptr) != (gt_inliers != nullptr)) return D3F_ERR_ARG;
     if (P == 0) return D3F_OK;
     if (!kp || !count_dev || !pairs_dev || !mutual_count) return D3F_ERR_ARG;
@@ -166,9 +133,7 @@ extern "C" int d3f_match_pairs(const float* kp, int n_blocks, int K, int ld, int
     const int kmax = prm.k[n_counts - 1] < K ? prm.k[n_counts - 1] : K;   // most ranks of a block any pair uses
     const int pz = P < 65535 ? P : 65535;
     const dim3 grid(d3f_cdiv(kmax, 256), 2, pz);
-    if (C == 16) mp_nearest_kernel<16><<<grid, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, prm, ws);
-    else if (C == 32) mp_nearest_kernel<32><<<grid, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, prm, ws);
-    else mp_nearest_kernel<64><<<grid, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, prm, ws);
+    rg_dispatch_C(C, [&](auto c) { mp_nearest_kernel<decltype(c)::value><<<grid, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, prm, ws); });
     mp_count_kernel<<<dim3(n_counts, pz), 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, gt, thr2, prm, ws, mutual_count,
                                                           gt_inliers);
     D3F_LAUNCH_CHECK();

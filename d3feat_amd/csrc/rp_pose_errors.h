@@ -5,7 +5,7 @@
 // rounded on its own (the file is built with -ffp-contract=off; the intrinsics say so again), so that numpy restates it bit for bit:
 //   pe_rows_kernel    one thread per row i (pair i / per_pair, column i % per_pair): rte, rre_deg, flags
 //   pe_meters_kernel  one workgroup: per column the eight sums of the header, thread t adding rows p = t, t + 256, ... in ascending
-//                     order, then the LDS halving tree 128 .. 1 of vp_block_sum
+//                     order, then the LDS halving tree 128 .. 1 of d3f_block_sum
 // No atomics, no ticket, no memset, no workspace: every output element has exactly one writer.
 #define PE_PI 3.141592653589793238462643383279502884
 
@@ -47,9 +47,9 @@ __global__ void __launch_bounds__(256) pe_meters_kernel(const double* __restrict
             if (f & 2) { const double v = rre_deg[i]; rs = __dadd_rn(rs, v); rq = __dadd_rn(rq, __dmul_rn(v, v)); rn += 1.0; }
             if (f & 4) ok += 1.0;
         }
-        ts = vp_block_sum(ts, red); tq = vp_block_sum(tq, red); tn = vp_block_sum(tn, red);   // (counts: whole numbers below 2^53, exact)
-        rs = vp_block_sum(rs, red); rq = vp_block_sum(rq, red); rn = vp_block_sum(rn, red);
-        ok = vp_block_sum(ok, red);
+        ts = d3f_block_sum(ts, red); tq = d3f_block_sum(tq, red); tn = d3f_block_sum(tn, red);   // (counts: whole numbers below 2^53, exact)
+        rs = d3f_block_sum(rs, red); rq = d3f_block_sum(rq, red); rn = d3f_block_sum(rn, red);
+        ok = d3f_block_sum(ok, red);
         if (threadIdx.x == 0) {
             double* m = meters + (size_t)c * 8;
             m[0] = ts; m[1] = tq; m[2] = tn; m[3] = rs; m[4] = rq; m[5] = rn; m[6] = ok; m[7] = (double)P;

@@ -16,7 +16,7 @@
 
 // grid (counts, pairs)
 __global__ void __launch_bounds__(256) rc_nn_rows_kernel(int n_blocks, int K, const int* __restrict__ count, const int* __restrict__ pairs,
-                                                         int P, MpParams prm, const int* __restrict__ ranks, int* __restrict__ nn) {
+                                                         int P, RcCounts prm, const int* __restrict__ ranks, int* __restrict__ nn) {
     const int c = blockIdx.x, kc = prm.k[c];
     for (int p = blockIdx.y; p < P; p += gridDim.y) {
         const int ns = rp_rows(count, pairs, p, 0, n_blocks, K, kc).n, nt = rp_rows(count, pairs, p, 1, n_blocks, K, kc).n;
@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(256) rc_nn_rows_kernel(int n_blocks, int K, co
 // grid (counts, pairs)
 __global__ void __launch_bounds__(256) rc_hypotheses_kernel(const float* __restrict__ kp, int n_blocks, int K, int ld,
                                                             const int* __restrict__ count, const int* __restrict__ pairs, int P,
-                                                            MpParams prm, const int* __restrict__ nn, int n, float radius, float edge_sim,
+                                                            RcCounts prm, const int* __restrict__ nn, int n, float radius, float edge_sim,
                                                             float dist_thr, unsigned long long seed, int max_iteration,
                                                             int max_validation, float* __restrict__ Tlist, int* __restrict__ itlist,
                                                             int* __restrict__ validations, int* __restrict__ iterations) {
@@ -49,12 +49,12 @@ __global__ void __launch_bounds__(256) rc_hypotheses_kernel(const float* __restr
     }
 }
 
-static inline int rc_rows(int K, const MpParams& prm) { return prm.k[prm.n - 1] < K ? prm.k[prm.n - 1] : K; }   // most rows of a block any pair uses
+static inline int rc_rows(int K, const RcCounts& prm) { return prm.k[prm.n - 1] < K ? prm.k[prm.n - 1] : K; }   // most rows of a block any pair uses
 
 extern "C" size_t d3f_register_pairs_counts_workspace_bytes(int P, int n_blocks, int K, const int* num_keypts_host, int n_counts,
                                                             int max_validation) {
-    MpParams prm;
-    if (P < 0 || n_blocks < 1 || n_blocks > D3F_MAX_BATCH || K < 1 || max_validation < 1 || !mp_params(num_keypts_host, n_counts, prm)) return 0;
+    RcCounts prm;
+    if (P < 0 || n_blocks < 1 || n_blocks > D3F_MAX_BATCH || K < 1 || max_validation < 1 || !rc_counts(num_keypts_host, n_counts, D3F_MATCH_KMAX, prm)) return 0;
     const size_t p = (size_t)(P > 0 ? P : 1), pv = p * (size_t)n_counts * (size_t)max_validation;
     return d3f_align(p * 2 * (size_t)prm.total * 4) + d3f_align(p * (size_t)prm.total * 4) + d3f_align(pv * 48) + 2 * d3f_align(pv * 4) +
            d3f_align(pv * 8) + nb_rc_workspace_bytes(n_blocks, rc_rows(K, prm)) + 256;
@@ -67,9 +67,9 @@ extern "C" int d3f_register_pairs_counts(const float* kp, int n_blocks, int K, i
                                          int* validations, int* iterations, int* best_iteration, int* mutual_count, int* gt_inliers,
                                          int* nearest, void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    MpParams prm;
+    RcCounts prm;
     if (P < 0 || n_blocks < 1 || n_blocks > D3F_MAX_BATCH || K < 1 || (C != 16 && C != 32 && C != 64) || ld < C + 4) return D3F_ERR_ARG;
-    if (!mp_params(num_keypts_host, n_counts, prm) || ransac_n < 3 || ransac_n > RG_MAXN) return D3F_ERR_ARG;
+    if (!rc_counts(num_keypts_host, n_counts, D3F_MATCH_KMAX, prm) || ransac_n < 3 || ransac_n > RG_MAXN) return D3F_ERR_ARG;
     if (max_iteration < 0 || max_iteration > (1 << 30) || max_validation < 1 || max_validation > (1 << 20)) return D3F_ERR_ARG;
     if (!(max_correspondence_distance == max_correspondence_distance) || !(distance_threshold == distance_threshold)) return D3F_ERR_ARG;
     if (P == 0) return D3F_OK;
@@ -93,9 +93,7 @@ extern "C" int d3f_register_pairs_counts(const float* kp, int n_blocks, int K, i
     const float r = max_correspondence_distance, thr2 = distance_threshold * distance_threshold;
     const int pz = P < 65535 ? P : 65535;
     const dim3 grid(d3f_cdiv(rows, 256), 2, pz), per_count(n_counts, pz);
-    if (C == 16) mp_nearest_kernel<16><<<grid, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, prm, ranks);
-    else if (C == 32) mp_nearest_kernel<32><<<grid, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, prm, ranks);
-    else mp_nearest_kernel<64><<<grid, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, prm, ranks);
+    rg_dispatch_C(C, [&](auto c) { mp_nearest_kernel<decltype(c)::value><<<grid, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, prm, ranks); });
     mp_count_kernel<<<per_count, 256, 0, stream>>>(kp, n_blocks, K, ld, count_dev, pairs_dev, P, gt, thr2, prm, ranks, mutual_count,
                                                    gt ? gt_inliers : nullptr);
     rc_nn_rows_kernel<<<per_count, 256, 0, stream>>>(n_blocks, K, count_dev, pairs_dev, P, prm, ranks, nn);
@@ -103,11 +101,7 @@ extern "C" int d3f_register_pairs_counts(const float* kp, int n_blocks, int K, i
                                                         checker_distance, seed, max_iteration, max_validation, Tlist, itlist, validations,
                                                         iterations);
     D3F_LAUNCH_CHECK();
-    RcCounts rc;
-    for (int c = 0; c < D3F_REPEAT_COUNTS_MAX; ++c) { rc.k[c] = prm.k[c]; rc.off[c] = prm.off[c]; }
-    rc.n = prm.n;
-    rc.total = prm.total;
     const RcLists lists{Tlist, itlist, validations, cnt, sd2, max_validation};
     const RcOut out{T_out, inliers, (unsigned long long*)sumd2, best_iteration, nearest};
-    return nb_rc_score_select(kp, n_blocks, K, ld, count_dev, pairs_dev, P, rc, rows, r, lists, out, gws, gb, stream);
+    return nb_rc_score_select(kp, n_blocks, K, ld, count_dev, pairs_dev, P, prm, rows, r, lists, out, gws, gb, stream);
 }

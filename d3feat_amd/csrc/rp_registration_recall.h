@@ -8,7 +8,7 @@
 // numpy restates it bit for bit (tests/recall_np.py):
 //   rr_rows_kernel   one thread per row i (pair i / n, column i % n): error, flags
 //   rr_scene_kernel  one workgroup per scene: per column five int64 sums over the pairs of the scene, thread t taking the pairs
-//                    p0 + t, p0 + t + 256, ..., then the LDS halving tree of ss_block_sum
+//                    p0 + t, p0 + t + 256, ..., then the LDS halving tree of d3f_block_sum
 // All sums are integers: nothing depends on a summation order.  No atomics, no memset, no workspace: every output element has exactly
 // one writer; scene_start travels as a kernel argument, so the call is capturable.
 //
@@ -128,8 +128,8 @@ __global__ void __launch_bounds__(256) rr_scene_kernel(const int* __restrict__ f
             gtn += f & RR_GT ? 1 : 0;
             rsn += f & RR_RESULT ? 1 : 0;
         }
-        good = ss_block_sum(good, red); bad = ss_block_sum(bad, red); fpos = ss_block_sum(fpos, red);
-        gtn = ss_block_sum(gtn, red); rsn = ss_block_sum(rsn, red);
+        good = d3f_block_sum(good, red); bad = d3f_block_sum(bad, red); fpos = d3f_block_sum(fpos, red);
+        gtn = d3f_block_sum(gtn, red); rsn = d3f_block_sum(rsn, red);
         if (threadIdx.x == 0) {
             long long* o = figures + ((size_t)s * n + c) * 5;
             o[0] = good; o[1] = bad; o[2] = fpos; o[3] = gtn; o[4] = rsn;
@@ -141,17 +141,11 @@ extern "C" int d3f_registration_recall(const void* T_est, int logged, const doub
                                        const int* result_flag, const int* ids, int P, int n, const int* scene_start_host, int S,
                                        const double* err2_host, double* error, int* flags, long long* figures, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (P < 0 || n < 1 || n > D3F_REPEAT_COUNTS_MAX || S < 0 || S > SS_SCENES_MAX || (long long)P * n > 0x7fffffffll) return D3F_ERR_ARG;
-    if (!scene_start_host || !err2_host) return D3F_ERR_ARG;
+    if (P < 0 || n < 1 || n > D3F_REPEAT_COUNTS_MAX || (long long)P * n > 0x7fffffffll || !err2_host) return D3F_ERR_ARG;
     const double err2 = err2_host[0];
     if (!(err2 > 0.0)) return D3F_ERR_ARG;                            // NaN too
     SsStarts starts;
-    for (int s = 0; s <= S; ++s) {
-        starts.v[s] = scene_start_host[s];
-        if (s ? starts.v[s] < starts.v[s - 1] : starts.v[s] != 0) return D3F_ERR_ARG;
-    }
-    if (starts.v[S] != P) return D3F_ERR_ARG;
-    for (int s = S + 1; s <= SS_SCENES_MAX; ++s) starts.v[s] = P;
+    if (!ss_starts(scene_start_host, S, P, starts)) return D3F_ERR_ARG;
     if (P > 0 && (!T_est || !gt || !info || !gt_flag || !ids || !error || !flags)) return D3F_ERR_ARG;
     if (S > 0 && !figures) return D3F_ERR_ARG;
     const int rows = P * n;

@@ -22,6 +22,17 @@
 #define SS_E8 100000000ll
 
 struct SsStarts { int v[SS_SCENES_MAX + 1]; };
+// the S + 1 host ints of a call: S inside 0 .. SS_SCENES_MAX, ascending from 0 to P; the entries after S are P.  false otherwise.
+static inline bool ss_starts(const int* scene_start_host, int S, int P, SsStarts& starts) {
+    if (!scene_start_host || S < 0 || S > SS_SCENES_MAX) return false;
+    for (int s = 0; s <= S; ++s) {
+        starts.v[s] = scene_start_host[s];
+        if (s ? starts.v[s] < starts.v[s - 1] : starts.v[s] != 0) return false;
+    }
+    if (starts.v[S] != P) return false;
+    for (int s = S + 1; s <= SS_SCENES_MAX; ++s) starts.v[s] = P;
+    return true;
+}
 
 __global__ void __launch_bounds__(256) ss_sanitize_kernel(float* __restrict__ kp, long long rows, int ld, int log2C) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;                  // element i = row (i >> log2C), column (i mod C)
@@ -53,17 +64,6 @@ __global__ void __launch_bounds__(256) ss_rows_kernel(const int* __restrict__ mu
     ratio_e8[i] = gt_flag[i / n] ? ss_ratio_e8(gt_inliers[i], mutual_count[i]) : 0;
 }
 
-__device__ __forceinline__ long long ss_block_sum(long long v, long long* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 __global__ void __launch_bounds__(256) ss_scene_kernel(const int* __restrict__ gt_inliers, const int* __restrict__ gt_flag,
                                                        const int* __restrict__ ratio_e8, int n, SsStarts starts, double inlier_ratio,
                                                        long long* __restrict__ figures) {
@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(256) ss_scene_kernel(const int* __restrict__ g
         if (__ddiv_rn((double)m, 1e8) > inlier_ratio) correct += 1;   // every pair of the scene (evaluate_eth.py:154)
         if (gt_flag[p]) { gt += 1; inl += gt_inliers[i]; sum_m += m; }
     }
-    gt = ss_block_sum(gt, red); correct = ss_block_sum(correct, red); inl = ss_block_sum(inl, red); sum_m = ss_block_sum(sum_m, red);
+    gt = d3f_block_sum(gt, red); correct = d3f_block_sum(correct, red); inl = d3f_block_sum(inl, red); sum_m = d3f_block_sum(sum_m, red);
     if (threadIdx.x == 0) {
         long long* f = figures + ((size_t)s * n + c) * 4;
         f[0] = gt; f[1] = correct; f[2] = inl; f[3] = sum_m;
@@ -100,17 +100,11 @@ extern "C" int d3f_matching_summary(const int* mutual_count, const int* gt_inlie
                                     const int* scene_start_host, int S, const double* inlier_ratio_host, int* ratio_e8,
                                     long long* figures, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (P < 0 || n < 1 || n > D3F_REPEAT_COUNTS_MAX || S < 0 || S > SS_SCENES_MAX || (long long)P * n > 0x7fffffffll) return D3F_ERR_ARG;
-    if (!scene_start_host || !inlier_ratio_host) return D3F_ERR_ARG;
+    if (P < 0 || n < 1 || n > D3F_REPEAT_COUNTS_MAX || (long long)P * n > 0x7fffffffll || !inlier_ratio_host) return D3F_ERR_ARG;
     const double inlier_ratio = inlier_ratio_host[0];
     if (inlier_ratio != inlier_ratio) return D3F_ERR_ARG;
     SsStarts starts;
-    for (int s = 0; s <= S; ++s) {
-        starts.v[s] = scene_start_host[s];
-        if (s ? starts.v[s] < starts.v[s - 1] : starts.v[s] != 0) return D3F_ERR_ARG;
-    }
-    if (starts.v[S] != P) return D3F_ERR_ARG;
-    for (int s = S + 1; s <= SS_SCENES_MAX; ++s) starts.v[s] = P;
+    if (!ss_starts(scene_start_host, S, P, starts)) return D3F_ERR_ARG;
     if (P > 0 && (!mutual_count || !gt_inliers || !gt_flag || !ratio_e8)) return D3F_ERR_ARG;
     if (S > 0 && !figures) return D3F_ERR_ARG;
     const int rows = P * n;

@@ -1,6 +1,6 @@
 // Validation figures of every pair in one call (d3f_validation_pairs; models/KPFCNN_model.py:131-186 + utils/loss.py of the
 // reference: circle loss, contrastive loss, detection loss, accuracy, mean positive / negative distance; the split totals of
-// utils/trainer.py:442-452).  Forward only.  (included by registration.hip; needs nothing of the rp_* kernels.)
+// utils/trainer.py:442-452).  Forward only.  (included by registration.hip; of its kernels only rg_desc_d2 and rg_dispatch_C.)
 //
 // A pair is a stack [anchor; positive] of rows with n index pairs (ai, pi).  With D[i,j] = sqrt(|f[ai[i]] - f[pi[j]]|^2 + 1e-12) and
 // KD[i,j] the same over the points of ai[i] and ai[j], every figure is a sum over i of a function of four per-row numbers
@@ -83,20 +83,7 @@ __global__ void __launch_bounds__(256) vp_rows_kernel(const float* __restrict__ 
             float tng = 0.f, tse = 0.f;                            // at most 16 terms each in fp32, then widened
             const int je = min(16 * w + 16, nt);
             for (int j = 16 * w; j < je; ++j) {
-                const float4* b = (const float4*)(tile + j * C);
-                float d2 = 0.f;
-#pragma unroll
-                for (int c = 0; c < C / 4; ++c) {
-                    const float4 v = b[c];
-                    float d = a[4 * c] - v.x;
-                    d2 = fmaf(d, d, d2);
-                    d = a[4 * c + 1] - v.y;
-                    d2 = fmaf(d, d, d2);
-                    d = a[4 * c + 2] - v.z;
-                    d2 = fmaf(d, d, d2);
-                    d = a[4 * c + 3] - v.w;
-                    d2 = fmaf(d, d, d2);
-                }
+                const float d2 = rg_desc_d2<C>(a, tile + j * C);   // (tile is 16-byte aligned: 128-bit LDS reads)
                 const float D = __fsqrt_rn(d2 + 1e-12f);
                 const float dx = px - tpt[3 * j], dy = py - tpt[3 * j + 1], dz = pz - tpt[3 * j + 2];
                 const float kd = __fsqrt_rn(((dx * dx + dy * dy) + dz * dz) + 1e-12f);
@@ -127,18 +114,6 @@ __global__ void __launch_bounds__(256) vp_rows_kernel(const float* __restrict__ 
         }
         // (the next pair's first barrier orders these reads before anything is written to red_* again: two barriers lie between)
     }
-}
-
-// sum of v over the 256 threads by a fixed tree; the result in every thread
-__device__ __forceinline__ double vp_block_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
 }
 
 __global__ void __launch_bounds__(256) vp_pair_kernel(const float* __restrict__ score, int lds, int n_rows, const int* __restrict__ row0,
@@ -192,12 +167,12 @@ __global__ void __launch_bounds__(256) vp_pair_kernel(const float* __restrict__ 
             dpos += r.x;
             dneg += r.w;
         }
-        circle = vp_block_sum(circle, red);
-        contrastive = vp_block_sum(contrastive, red);
-        det = vp_block_sum(det, red);
-        dpos = vp_block_sum(dpos, red);
-        dneg = vp_block_sum(dneg, red);
-        acc = vp_block_sum(acc, red);
+        circle = d3f_block_sum(circle, red);
+        contrastive = d3f_block_sum(contrastive, red);
+        det = d3f_block_sum(det, red);
+        dpos = d3f_block_sum(dpos, red);
+        dneg = d3f_block_sum(dneg, red);
+        acc = d3f_block_sum(acc, red);
         if (threadIdx.x == 0) {
             const double dn = (double)n;
             const float fn = (float)n;
@@ -226,8 +201,8 @@ __global__ void __launch_bounds__(256) vp_totals_kernel(const float* __restrict_
             const float v = values[(size_t)p * 8 + k];
             if (k == 3 ? v > 0.f : v != 0.f) { s += (double)v; c += 1.0; }
         }
-        s = vp_block_sum(s, red);
-        c = vp_block_sum(c, red);                                    // (whole numbers below 2^53: exact)
+        s = d3f_block_sum(s, red);
+        c = d3f_block_sum(c, red);                                    // (whole numbers below 2^53: exact)
         if (threadIdx.x == 0) { sums[k] = s; counts[k] = (long long)c; }
     }
 }
@@ -262,15 +237,10 @@ extern "C" int d3f_validation_pairs(const float* desc, int ldd, int C, const flo
     double4* ws = ar.take<double4>((size_t)P * ws_ld);
     if (!ar.ok) return D3F_ERR_WORKSPACE;
     const dim3 grid(tiles, P < 65535 ? P : 65535);
-    if (C == 16)
-        vp_rows_kernel<16><<<grid, 256, 0, stream>>>(desc, ldd, points, ldp, n_rows, row0_dev, anc_dev, pos_dev, ld_idx, n_dev, P, nmax, safe_radius,
-                                                     keypts_num, neg_margin, log_scale, ws, ws_ld);
-    else if (C == 32)
-        vp_rows_kernel<32><<<grid, 256, 0, stream>>>(desc, ldd, points, ldp, n_rows, row0_dev, anc_dev, pos_dev, ld_idx, n_dev, P, nmax, safe_radius,
-                                                     keypts_num, neg_margin, log_scale, ws, ws_ld);
-    else
-        vp_rows_kernel<64><<<grid, 256, 0, stream>>>(desc, ldd, points, ldp, n_rows, row0_dev, anc_dev, pos_dev, ld_idx, n_dev, P, nmax, safe_radius,
-                                                     keypts_num, neg_margin, log_scale, ws, ws_ld);
+    rg_dispatch_C(C, [&](auto c) {
+        vp_rows_kernel<decltype(c)::value><<<grid, 256, 0, stream>>>(desc, ldd, points, ldp, n_rows, row0_dev, anc_dev, pos_dev, ld_idx, n_dev, P, nmax,
+                                                                     safe_radius, keypts_num, neg_margin, log_scale, ws, ws_ld);
+    });
     vp_pair_kernel<<<P < 65535 ? P : 65535, 256, 0, stream>>>(score, lds, n_rows, row0_dev, anc_dev, pos_dev, ld_idx, n_dev, P, nmax, keypts_num,
                                                               det_loss_weight, pos_margin, neg_margin, log_scale, ws, ws_ld, values, status);
     vp_totals_kernel<<<1, 256, 0, stream>>>(values, P, sums, (long long*)counts);

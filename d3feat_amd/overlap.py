@@ -38,25 +38,19 @@ def stack_fragments(clouds, poses=None, device=None):
     return torch.from_numpy(np.ascontiguousarray(pts)).to(dev), ops.as_lens([len(c) for c in out], dev)
 
 
-class PairOverlap:
+class PairOverlap(registration._PairResult):
     """Result of overlap_pairs: DEVICE tensors, one row per pair.  count i32[P] (points of the source with a target point strictly
     inside the threshold; -1: a fragment index outside the stack), src_len i32[P] (points of the source), nearest i32[P, ld] when
     asked for (per source point the index inside the target of its nearest point, -1: none; -1 from src_len on)."""
+    FIELDS = ("count", "src_len", "nearest")
 
     def __init__(self, P, ld, device):
         self.P, self.ld = P, ld
+        self.key = (P, ld is not None)
         self.count = torch.empty((P,), dtype=torch.int32, device=device)
         self.src_len = torch.empty((P,), dtype=torch.int32, device=device)
         self.nearest = torch.empty((P, ld), dtype=torch.int32, device=device) if ld is not None else None
         self.grid = None
-
-    _cache = None
-
-    def _host(self):
-        # one read-back of the whole result, kept until the next overlap_pairs(out=self)
-        if self._cache is None:
-            self._cache = {k: getattr(self, k).cpu().numpy() for k in ("count", "src_len", "nearest") if getattr(self, k) is not None}
-        return self._cache
 
     def ratios(self):
         """f64[P]: count / src_len, the overlap ratio of cal_overlap.py:116; 0 for an empty source."""
@@ -113,21 +107,17 @@ def overlap_pairs(points, lens, pairs=None, threshold=OVERLAP_3DMATCH["threshold
         grid = ops.NeighborGrid(points, lens, thr)
     elif grid.Ns != N or grid.B != n or grid.supports.data_ptr() != points.data_ptr():
         raise ValueError("overlap_pairs: the grid was not built over these points")
-    if out is None:
-        out = PairOverlap(P, max(max(ops.host_lens(lens)), 1) if nearest else None, dev)
-    elif not isinstance(out, PairOverlap) or (out.P, out.nearest is not None) != (P, bool(nearest)) or out.count.device != dev:
-        raise ValueError("overlap_pairs: out= was made for another call")
-    elif nearest and getattr(lens, "host_lens", None) is not None and max(lens.host_lens) > out.ld:
+    out = registration._reuse("overlap_pairs", out, PairOverlap, (P, bool(nearest)), dev,
+                              lambda: PairOverlap(P, max(max(ops.host_lens(lens)), 1) if nearest else None, dev))
+    if nearest and getattr(lens, "host_lens", None) is not None and max(lens.host_lens) > out.ld:
         # (lengths known on the host only: a device-only lens tensor is not read back here, the kernel then keeps to the row)
         raise ValueError("overlap_pairs: out= holds %d matches per pair, the longest fragment %d points" % (out.ld, max(lens.host_lens)))
-    out._cache = None
     out.grid = grid                                            # (a captured call keeps reading this grid's memory)
     # length of every pair's source (plumbing for ratios(); a fragment index outside the stack: 0)
     a = pairs[:, 0].long()
     torch.mul(lens[a.clamp(0, n - 1)], ((a >= 0) & (a < n)).to(torch.int32), out=out.src_len)
     st = ops._stream(dev)
-    for p0 in range(0, P, registration.PAIRS_PER_CALL):
-        s = slice(p0, min(p0 + registration.PAIRS_PER_CALL, P))
+    for s in registration._chunks(P):
         rc = lib.d3f_overlap_pairs(grid.mem.data_ptr(), grid.nbytes, N, n, pairs[s].data_ptr(), s.stop - s.start, thr,
                                    out.count[s].data_ptr(), out.nearest[s].data_ptr() if nearest else None,
                                    out.ld if nearest else 0, st)

@@ -48,6 +48,121 @@ def _f32(a, device):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
 
 
+# ---- plumbing of the one-call entry points (here and in overlap.py / validation.py): each rule once -----------------------------------
+PAIRS_PER_CALL = 4096
+
+
+def _blocks(fn, kp, count, pairs, min_ld):
+    """The keypoint blocks of a call: kp f32[n_blocks, K, ld >= min_ld], count i32[n_blocks], pairs i32[P, 2], device, contiguous.
+    -> kp, count, pairs, n_blocks, K, ld, P, device."""
+    kp = ops._req(kp, torch.float32, "kp", 3)
+    count = ops._req(count, torch.int32, "count", 1)
+    pairs = ops._req(pairs, torch.int32, "pairs", 2)
+    if not kp.is_contiguous() or not count.is_contiguous() or not pairs.is_contiguous() or pairs.shape[1] != 2:
+        raise ValueError("%s: kp, count and pairs must be contiguous, pairs [P, 2]" % fn)
+    n_blocks, K, ld = kp.shape
+    if count.shape[0] != n_blocks or n_blocks < 1 or K < 1 or ld < min_ld:
+        raise ValueError("%s: kp %s, count %s" % (fn, tuple(kp.shape), tuple(count.shape)))
+    return kp, count, pairs, n_blocks, K, ld, pairs.shape[0], kp.device
+
+
+def _counts(fn, num_keypts, kmax):
+    """The keypoint counts of a sweep -> (list of ints, the ctypes array the library reads)."""
+    ks = [int(k) for k in num_keypts]
+    if not 1 <= len(ks) <= _lib.REPEAT_COUNTS_MAX or any(not 1 <= k <= kmax for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError("%s: num_keypts %s must be 1 to %d strictly ascending counts in 1..%d" % (fn, ks, _lib.REPEAT_COUNTS_MAX, kmax))
+    return ks, (_lib.C.c_int * len(ks))(*ks)
+
+
+def _gt32(fn, gt, P):
+    """The float32 ground truth of P pairs: device f32[P, 3, 4], contiguous."""
+    gt = ops._req(gt, torch.float32, "gt", 3)
+    if tuple(gt.shape) != (P, 3, 4) or not gt.is_contiguous():
+        raise ValueError("%s: gt of shape %s for %d pairs" % (fn, tuple(gt.shape), P))
+    return gt
+
+
+def _scene_starts(fn, scene_start, P):
+    """S + 1 host ints, scene s owning the pairs scene_start[s] .. scene_start[s + 1] - 1 -> (list, the ctypes array the library reads)."""
+    starts = [int(v) for v in np.asarray(scene_start).reshape(-1)]
+    S = len(starts) - 1
+    if not 0 <= S <= _lib.SCENES_MAX or starts[0] != 0 or starts[-1] != P or any(b < a for a, b in zip(starts, starts[1:])):
+        raise ValueError("%s: scene_start %s must hold 1 to %d ascending ints from 0 to P = %d" % (fn, starts, _lib.SCENES_MAX + 1, P))
+    return starts, (_lib.C.c_int * (S + 1))(*starts)
+
+
+def _chunks(P, per_call=None):
+    """The slices of P pairs, per_call (PAIRS_PER_CALL as it is now) at a time."""
+    per_call = per_call or PAIRS_PER_CALL
+    for p0 in range(0, P, per_call):
+        yield slice(p0, min(p0 + per_call, P))
+
+
+def _ptr(t):
+    """The address of a tensor; None for no tensor and for an empty one, which has no address."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+class _PairResult:
+    """Base of the device-result objects.  FIELDS: the tensors _host() reads back (a None one is left out), HOST: further ones; every
+    constructor sets key -- what a later call with out=self must ask for again.  device: where the first of FIELDS is."""
+    FIELDS = HOST = ()
+    key = None
+    _cache = None
+    device = property(lambda self: getattr(self, self.FIELDS[0]).device)
+
+    def _read(self, name):
+        return getattr(self, name).cpu().numpy()
+
+    def _host(self):
+        # one read-back of the whole result, kept until the next call with out=self
+        if self._cache is None:
+            self._cache = {k: self._read(k) for k in self.FIELDS + self.HOST if getattr(self, k) is not None}
+        return self._cache
+
+
+def _reuse(fn, out, cls, key, device, make):
+    """The result object of a call: make() without `out`, else `out` itself if it is a `cls` made for the same key on the same device.
+    Its read-back is forgotten either way."""
+    if out is None:
+        out = make()
+    elif not isinstance(out, cls) or out.key != key or out.device != device:
+        raise _another_call(fn)
+    out._cache = None
+    return out
+
+
+def _another_call(fn):
+    return ValueError("%s: out= was made for another call" % fn)
+
+
+def _ransac_dict(h, at, near=None):
+    """The dict ransac_feature_matching returns (plus best_iteration), from row `at` of a read-back h; near: the winner's target row of
+    every source row, for correspondence_set."""
+    Ns, cnt = int(h["ns"][at]), np.int64(h["inliers"][at])
+    sd2 = np.float64(h["sumd2"][at]) / 4294967296.0
+    M = np.eye(4)
+    M[:3, :4] = h["T"][at].astype(np.float64)
+    out = dict(transformation=M, fitness=float(cnt) / Ns if Ns else 0.0, inlier_rmse=float(np.sqrt(sd2 / np.maximum(cnt, 1))))
+    if near is not None:
+        out["correspondence_set"] = _correspondence_set(near[:Ns])
+    out.update(iterations=int(h["iterations"][at]), validations=int(h["validations"][at]), best_iteration=int(h["best_iteration"][at]))
+    return out
+
+
+def _correspondence_set(near):
+    sel = np.nonzero(near >= 0)[0]
+    return np.stack([sel, near[sel]], 1).astype(np.int64)
+
+
+def _gt_figures(out, h, at, k):
+    """gt_inliers and inlier_ratio = gt_inliers / k (k: the mutual matches; 0.0 without one), when the call had gt."""
+    if "gt_inliers" in h:
+        out["gt_inliers"] = int(h["gt_inliers"][at])
+        out["inlier_ratio"] = out["gt_inliers"] / k if k else 0.0
+    return out
+
+
 def feature_nn(A, B, return_d2=False, device=None):
     """idx[i] = argmin_j ||A_i - B_j||^2 (ties to the lowest j).  A [n,C], B [m,C], C in {16,32,64} -> int32 [n] (device)."""
     lib = _lib.load()
@@ -170,7 +285,6 @@ def register_keypoints(src_records, tgt_records, num_keypts=None, device=None, *
 # evaluate.py:93-99: the call the reference makes for every pair (compat/open3d spells it for one pair)
 EVALUATE_3DMATCH = dict(max_correspondence_distance=0.05, ransac_n=3, edge_similarity=0.9, checker_distance=0.05,
                         max_iteration=50000, max_validation=1000)
-PAIRS_PER_CALL = 4096
 
 
 def scene_pairs(n, device=None):
@@ -195,17 +309,19 @@ def stack_keypoints(blocks, K=None, device=None):
     return kp, count
 
 
-class PairRegistration:
+class PairRegistration(_PairResult):
     """Result of register_pairs: DEVICE tensors, one row per pair.
     T f32[P,3,4] ([R | t] of the winner, identity without one), inliers i32[P], sumd2 i64[P] (2^-32 units), validations i32[P],
     iterations i32[P], best_iteration i32[P] (-1: none), mutual_count i32[P], nearest i32[P,Kmax] (target row of every source row
     under the winner, -1: none); mutual i32[P,Kmax,2] / gt_inliers i32[P] when asked for.  Rows are numbered inside the rows a
     pair uses (the last min(count, num_keypts) of a block)."""
     FIELDS = ("T", "inliers", "sumd2", "validations", "iterations", "best_iteration", "mutual_count", "nearest", "mutual", "gt_inliers")
+    HOST = ("ns", "nt")
 
     def __init__(self, P, Kmax, device, correspondences, gt):
         i32 = dict(dtype=torch.int32, device=device)
         self.P, self.Kmax = P, Kmax
+        self.key = (P, Kmax, bool(correspondences), bool(gt))
         self.T = torch.empty((P, 3, 4), dtype=torch.float32, device=device)
         self.inliers, self.validations, self.iterations = (torch.empty((P,), **i32) for _ in range(3))
         self.best_iteration, self.mutual_count = torch.empty((P,), **i32), torch.empty((P,), **i32)
@@ -215,33 +331,14 @@ class PairRegistration:
         self.gt_inliers = torch.empty((P,), **i32) if gt else None
         self.ns = self.nt = None
 
-    def _host(self):
-        # one read-back of the whole result, kept until the next register_pairs(out=self)
-        if self._cache is None:
-            self._cache = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS + ("ns", "nt") if getattr(self, k) is not None}
-        return self._cache
-
-    _cache = None
-
     def host(self, p):
         """The dict register_keypoints returns for pair p (plus best_iteration, and inlier_ratio when gt was given)."""
         h = self._host()
-        Ns, cnt = int(h["ns"][p]), np.int64(h["inliers"][p])
-        sd2 = np.float64(h["sumd2"][p]) / 4294967296.0
-        near = h["nearest"][p, :Ns]
-        sel = np.nonzero(near >= 0)[0]
-        M = np.eye(4)
-        M[:3, :4] = h["T"][p].astype(np.float64)
-        out = dict(transformation=M, fitness=float(cnt) / Ns if Ns else 0.0, inlier_rmse=float(np.sqrt(sd2 / np.maximum(cnt, 1))),
-                   correspondence_set=np.stack([sel, near[sel]], 1).astype(np.int64), iterations=int(h["iterations"][p]),
-                   validations=int(h["validations"][p]), best_iteration=int(h["best_iteration"][p]))
+        out = _ransac_dict(h, p, h["nearest"][p])
         k = int(h["mutual_count"][p])
         if "mutual" in h:
             out["correspondences"] = h["mutual"][p, :k].astype(np.int64)
-        if "gt_inliers" in h:
-            out["gt_inliers"] = int(h["gt_inliers"][p])
-            out["inlier_ratio"] = out["gt_inliers"] / k if k else 0.0
-        return out
+        return _gt_figures(out, h, p, k)
 
 
 def register_pairs(kp, count, pairs, max_correspondence_distance, num_keypts=None, ransac_n=4, edge_similarity=0.9,
@@ -254,40 +351,27 @@ def register_pairs(kp, count, pairs, max_correspondence_distance, num_keypts=Non
     are ransac_feature_matching's.  gt f32[P, 3, 4] (target -> source) adds gt_inliers (evaluate.py:70-77, distance_threshold);
     correspondences=True adds the mutually closest pairs themselves.  -> PairRegistration (device tensors; .host(p) for a dict)."""
     lib = _lib.load()
-    kp = ops._req(kp, torch.float32, "kp", 3)
-    count = ops._req(count, torch.int32, "count", 1)
-    pairs = ops._req(pairs, torch.int32, "pairs", 2)
-    dev = kp.device
-    if not kp.is_contiguous() or not count.is_contiguous() or not pairs.is_contiguous() or pairs.shape[1] != 2:
-        raise ValueError("register_pairs: kp, count and pairs must be contiguous, pairs [P, 2]")
-    n_blocks, K, ld = kp.shape
+    kp, count, pairs, n_blocks, K, ld, P, dev = _blocks("register_pairs", kp, count, pairs, 0)
     C = ld - 4
     Kmax = min(K, int(num_keypts)) if num_keypts is not None else K
-    if count.shape[0] != n_blocks or n_blocks < 1 or Kmax < 1:
+    if Kmax < 1:
         raise ValueError("register_pairs: kp %s, count %s, num_keypts %s" % (tuple(kp.shape), tuple(count.shape), num_keypts))
     if Kmax > _lib.PAIRS_KMAX or C not in (16, 32, 64) or not 3 <= int(ransac_n) <= 8:
         raise ValueError("register_pairs takes up to %d rows per block, descriptors of 16, 32 or 64 floats and ransac_n in 3..8 (got %d "
                          "rows, %d floats, ransac_n %s): use register_keypoints for one pair of larger blocks"
                          % (_lib.PAIRS_KMAX, Kmax, C, ransac_n))
-    P = pairs.shape[0]
     if gt is not None:
-        gt = ops._req(gt, torch.float32, "gt", 3)
-        if tuple(gt.shape) != (P, 3, 4) or not gt.is_contiguous():
-            raise ValueError("register_pairs: gt of shape %s for %d pairs" % (tuple(gt.shape), P))
-    if out is None:
-        out = PairRegistration(P, Kmax, dev, correspondences, gt is not None)
-    elif (out.P, out.Kmax, out.mutual is not None, out.gt_inliers is not None) != (P, Kmax, bool(correspondences), gt is not None):
-        raise ValueError("register_pairs: out= was made for another call")
-    out._cache = None
+        gt = _gt32("register_pairs", gt, P)
+    out = _reuse("register_pairs", out, PairRegistration, (P, Kmax, bool(correspondences), gt is not None), dev,
+                 lambda: PairRegistration(P, Kmax, dev, correspondences, gt is not None))
     # rows each pair uses (plumbing for host(): fitness = inliers / Ns)
     used = count.clamp(0, Kmax)
     out.ns, out.nt = used[pairs[:, 0].long()], used[pairs[:, 1].long()]
     st = ops._stream(dev)
     nk, mv = int(num_keypts) if num_keypts is not None else 0, int(max_validation)
-    for p0 in range(0, P, PAIRS_PER_CALL):
-        n = min(PAIRS_PER_CALL, P - p0)
+    for s in _chunks(P):
+        n = s.stop - s.start
         ws = ops.workspace(lib.d3f_register_pairs_workspace_bytes(n, K, nk, mv), dev)
-        s = slice(p0, p0 + n)
         rc = lib.d3f_register_pairs(
             kp.data_ptr(), n_blocks, K, ld, C, count.data_ptr(), pairs[s].data_ptr(), n, nk, float(max_correspondence_distance),
             int(ransac_n), float(edge_similarity or 0.0), float(checker_distance or 0.0), int(max_iteration), mv, int(seed),
@@ -305,25 +389,19 @@ REPEATABILITY_3DMATCH = dict(distance_threshold=0.1, moved="target")           #
 REPEATABILITY_KITTI = dict(distance_threshold=0.5, moved="source")             # evaluate_kitti_our.py:18-22,43
 
 
-class PairRepeatability:
+class PairRepeatability(_PairResult):
     """Result of repeatability_pairs: DEVICE tensors repeat i32[P, n] (target keypoints with a source keypoint inside the threshold,
     per pair and count) and totals i64[n] (their sums over the pairs); num_keypts is the tuple of the n counts."""
+    FIELDS = ("repeat", "totals")
 
     def __init__(self, P, num_keypts, device):
         self.P, self.num_keypts = P, tuple(num_keypts)
+        self.key = (P, self.num_keypts)
         n, chunks = len(self.num_keypts), max(-(-P // PAIRS_PER_CALL), 1)
         self.repeat = torch.empty((P, n), dtype=torch.int32, device=device)
         self.totals = torch.zeros((n,), dtype=torch.int64, device=device)
         # more than PAIRS_PER_CALL pairs: the totals of every call, added up in row order (integers)
         self.chunk_totals = torch.empty((chunks, n), dtype=torch.int64, device=device) if chunks > 1 else None
-
-    _cache = None
-
-    def _host(self):
-        # one read-back of the whole result, kept until the next repeatability_pairs(out=self)
-        if self._cache is None:
-            self._cache = dict(repeat=self.repeat.cpu().numpy(), totals=self.totals.cpu().numpy())
-        return self._cache
 
     def ratios(self):
         """f64[P, n]: repeat / num_keypts, the figure the reference appends per pair (the count itself, whatever the blocks hold)."""
@@ -357,36 +435,18 @@ def repeatability_pairs(kp, count, pairs, gt, num_keypts=REPEATABILITY_COUNTS, d
     f64[P,3,4] tensor so that it is read in place).  num_keypts: strictly ascending, 1 .. 1024, at most 16 of them.
     -> PairRepeatability (device tensors; .ratios() / .scene() for the reference's figures)."""
     lib = _lib.load()
-    kp = ops._req(kp, torch.float32, "kp", 3)
-    count = ops._req(count, torch.int32, "count", 1)
-    pairs = ops._req(pairs, torch.int32, "pairs", 2)
-    dev = kp.device
-    if not kp.is_contiguous() or not count.is_contiguous() or not pairs.is_contiguous() or pairs.shape[1] != 2:
-        raise ValueError("repeatability_pairs: kp, count and pairs must be contiguous, pairs [P, 2]")
-    n_blocks, K, ld = kp.shape
-    if count.shape[0] != n_blocks or n_blocks < 1 or K < 1 or ld < 3:
-        raise ValueError("repeatability_pairs: kp %s, count %s" % (tuple(kp.shape), tuple(count.shape)))
-    ks = [int(k) for k in num_keypts]
-    if (not 1 <= len(ks) <= _lib.REPEAT_COUNTS_MAX or any(not 1 <= k <= _lib.PAIRS_KMAX for k in ks)
-            or any(b <= a for a, b in zip(ks, ks[1:]))):
-        raise ValueError("repeatability_pairs: num_keypts %s must be 1 to %d strictly ascending counts in 1..%d"
-                         % (ks, _lib.REPEAT_COUNTS_MAX, _lib.PAIRS_KMAX))
+    kp, count, pairs, n_blocks, K, ld, P, dev = _blocks("repeatability_pairs", kp, count, pairs, 3)
+    ks, c_ks = _counts("repeatability_pairs", num_keypts, _lib.PAIRS_KMAX)
     if moved not in ("target", "source"):
         raise ValueError("repeatability_pairs: moved=%r (\"target\" or \"source\")" % (moved,))
     thr = float(distance_threshold)
     if not thr > 0.0:
         raise ValueError("repeatability_pairs: distance_threshold %r" % (distance_threshold,))
-    P = pairs.shape[0]
     gt = _gt_f64(gt, P, dev)
-    if out is None:
-        out = PairRepeatability(P, ks, dev)
-    elif not isinstance(out, PairRepeatability) or (out.P, out.num_keypts) != (P, tuple(ks)) or out.repeat.device != dev:
-        raise ValueError("repeatability_pairs: out= was made for another call")
-    out._cache = None
+    out = _reuse("repeatability_pairs", out, PairRepeatability, (P, tuple(ks)), dev, lambda: PairRepeatability(P, ks, dev))
     st = ops._stream(dev)
-    c_thr, c_ks, n = _lib.C.c_double(thr), (_lib.C.c_int * len(ks))(*ks), len(ks)
-    for i, p0 in enumerate(range(0, P, PAIRS_PER_CALL)):
-        s = slice(p0, min(p0 + PAIRS_PER_CALL, P))
+    c_thr, n = _lib.C.c_double(thr), len(ks)
+    for i, s in enumerate(_chunks(P)):
         totals = out.totals if out.chunk_totals is None else out.chunk_totals[i]
         rc = lib.d3f_repeatability_pairs(kp.data_ptr(), n_blocks, K, ld, count.data_ptr(), pairs[s].data_ptr(), s.stop - s.start,
                                          gt[s].data_ptr(), 1 if moved == "source" else 0, _lib.C.addressof(c_thr),
@@ -401,23 +461,17 @@ def repeatability_pairs(kp, count, pairs, gt, num_keypts=REPEATABILITY_COUNTS, d
 MATCHING_COUNTS = (250, 500, 1000, 2500, 5000)                                 # the sweep of evaluate.py:46's num_keypts
 
 
-class PairMatching:
+class PairMatching(_PairResult):
     """Result of match_pairs: DEVICE tensors mutual_count i32[P, n] (mutually nearest descriptor pairs, per pair and count) and
     gt_inliers i32[P, n] (those inside the distance threshold under gt; None without gt); num_keypts is the tuple of the n counts."""
+    FIELDS = ("mutual_count", "gt_inliers")
 
     def __init__(self, P, num_keypts, device, gt):
         self.P, self.num_keypts = P, tuple(num_keypts)
+        self.key = (P, self.num_keypts, bool(gt))
         n = len(self.num_keypts)
         self.mutual_count = torch.empty((P, n), dtype=torch.int32, device=device)
         self.gt_inliers = torch.empty((P, n), dtype=torch.int32, device=device) if gt else None
-
-    _cache = None
-
-    def _host(self):
-        # one read-back of the whole result, kept until the next match_pairs(out=self)
-        if self._cache is None:
-            self._cache = {k: getattr(self, k).cpu().numpy() for k in ("mutual_count", "gt_inliers") if getattr(self, k) is not None}
-        return self._cache
 
     def ratios(self):
         """f64[P, n]: gt_inliers / mutual_count (evaluate.py:81), 0.0 for a pair without a mutual match (as PairRegistration.host)."""
@@ -450,39 +504,19 @@ def match_pairs(kp, count, pairs, gt=None, num_keypts=MATCHING_COUNTS, distance_
     them: two launches per PAIRS_PER_CALL pairs, no read-back and no host decision (capturable: pass the previous result as `out`).
     num_keypts: strictly ascending, 1 .. 8192, at most 16 of them.  -> PairMatching (device tensors; .ratios() / .rows())."""
     lib = _lib.load()
-    kp = ops._req(kp, torch.float32, "kp", 3)
-    count = ops._req(count, torch.int32, "count", 1)
-    pairs = ops._req(pairs, torch.int32, "pairs", 2)
-    dev = kp.device
-    if not kp.is_contiguous() or not count.is_contiguous() or not pairs.is_contiguous() or pairs.shape[1] != 2:
-        raise ValueError("match_pairs: kp, count and pairs must be contiguous, pairs [P, 2]")
-    n_blocks, K, ld = kp.shape
+    kp, count, pairs, n_blocks, K, ld, P, dev = _blocks("match_pairs", kp, count, pairs, 0)
     C = ld - 4
-    if count.shape[0] != n_blocks or n_blocks < 1 or K < 1 or C not in (16, 32, 64):
+    if C not in (16, 32, 64):
         raise ValueError("match_pairs: kp %s (descriptors of 16, 32 or 64 floats), count %s" % (tuple(kp.shape), tuple(count.shape)))
-    ks = [int(k) for k in num_keypts]
-    if (not 1 <= len(ks) <= _lib.REPEAT_COUNTS_MAX or any(not 1 <= k <= _lib.MATCH_KMAX for k in ks)
-            or any(b <= a for a, b in zip(ks, ks[1:]))):
-        raise ValueError("match_pairs: num_keypts %s must be 1 to %d strictly ascending counts in 1..%d"
-                         % (ks, _lib.REPEAT_COUNTS_MAX, _lib.MATCH_KMAX))
+    ks, c_ks = _counts("match_pairs", num_keypts, _lib.MATCH_KMAX)
     thr = float(distance_threshold)
     if thr != thr:
         raise ValueError("match_pairs: distance_threshold %r" % (distance_threshold,))
-    P = pairs.shape[0]
     if gt is not None:
-        gt = ops._req(gt, torch.float32, "gt", 3)
-        if tuple(gt.shape) != (P, 3, 4) or not gt.is_contiguous():
-            raise ValueError("match_pairs: gt of shape %s for %d pairs" % (tuple(gt.shape), P))
-    if out is None:
-        out = PairMatching(P, ks, dev, gt is not None)
-    elif (not isinstance(out, PairMatching) or (out.P, out.num_keypts, out.gt_inliers is not None) != (P, tuple(ks), gt is not None)
-          or out.mutual_count.device != dev):
-        raise ValueError("match_pairs: out= was made for another call")
-    out._cache = None
-    st = ops._stream(dev)
-    c_ks, n = (_lib.C.c_int * len(ks))(*ks), len(ks)
-    for p0 in range(0, P, PAIRS_PER_CALL):
-        s = slice(p0, min(p0 + PAIRS_PER_CALL, P))
+        gt = _gt32("match_pairs", gt, P)
+    out = _reuse("match_pairs", out, PairMatching, (P, tuple(ks), gt is not None), dev, lambda: PairMatching(P, ks, dev, gt is not None))
+    st, n = ops._stream(dev), len(ks)
+    for s in _chunks(P):
         ws = ops.workspace(lib.d3f_match_pairs_workspace_bytes(s.stop - s.start, _lib.C.addressof(c_ks), n), dev)
         rc = lib.d3f_match_pairs(kp.data_ptr(), n_blocks, K, ld, C, count.data_ptr(), pairs[s].data_ptr(), s.stop - s.start,
                                  gt[s].data_ptr() if gt is not None else None, thr, _lib.C.addressof(c_ks), n,
@@ -493,17 +527,19 @@ def match_pairs(kp, count, pairs, gt=None, num_keypts=MATCHING_COUNTS, distance_
 
 
 # ---- RANSAC registration of every pair at every count in one call (geometric_registration/evaluate.py:45-50,67-99) -----------------
-class PairRegistrationCounts:
+class PairRegistrationCounts(_PairResult):
     """Result of register_pairs_counts: DEVICE tensors, one row per pair and count (num_keypts is the tuple of the n counts).
     T f32[P,n,3,4] ([R | t] of the winner, identity without one), inliers / validations / iterations / best_iteration (-1: none) /
     mutual_count i32[P,n], sumd2 i64[P,n] (2^-32 units), gt_inliers i32[P,n] when gt was given, nearest i32[P, sum of the counts] when
     asked for: entries offsets[c] .. offsets[c] + num_keypts[c] - 1 are the target rows of the source rows under the winner of count c
     (-1: none).  Rows are numbered inside the rows a pair uses at that count (the last min(count, num_keypts[c]) of a block)."""
     FIELDS = ("T", "inliers", "sumd2", "validations", "iterations", "best_iteration", "mutual_count", "gt_inliers", "nearest")
+    HOST = ("ns", "nt")
 
     def __init__(self, P, num_keypts, device, gt, nearest):
         i32 = dict(dtype=torch.int32, device=device)
         self.P, self.num_keypts = P, tuple(num_keypts)
+        self.key = (P, self.num_keypts, bool(gt), bool(nearest))
         n = len(self.num_keypts)
         self.offsets = tuple(int(x) for x in np.concatenate([[0], np.cumsum(self.num_keypts)[:-1]]))
         self.T = torch.empty((P, n, 3, 4), dtype=torch.float32, device=device)
@@ -513,14 +549,6 @@ class PairRegistrationCounts:
         self.gt_inliers = torch.empty((P, n), **i32) if gt else None
         self.nearest = torch.empty((P, sum(self.num_keypts)), **i32) if nearest else None
         self.ns = self.nt = None
-
-    _cache = None
-
-    def _host(self):
-        # one read-back of the whole result, kept until the next register_pairs_counts(out=self)
-        if self._cache is None:
-            self._cache = {k: getattr(self, k).cpu().numpy() for k in self.FIELDS + ("ns", "nt") if getattr(self, k) is not None}
-        return self._cache
 
     def at(self, c):
         """The device tensors of count num_keypts[c], shaped as PairRegistration's: a dict name -> tensor ([P, ...] views)."""
@@ -534,22 +562,11 @@ class PairRegistrationCounts:
         """The dict PairRegistration.host(p) returns, for pair p at count num_keypts[c] (`correspondences` needs register_pairs;
         `correspondence_set` needs nearest=True)."""
         h = self._host()
-        Ns, cnt = int(h["ns"][p, c]), np.int64(h["inliers"][p, c])
-        sd2 = np.float64(h["sumd2"][p, c]) / 4294967296.0
-        M = np.eye(4)
-        M[:3, :4] = h["T"][p, c].astype(np.float64)
-        out = dict(transformation=M, fitness=float(cnt) / Ns if Ns else 0.0, inlier_rmse=float(np.sqrt(sd2 / np.maximum(cnt, 1))),
-                   iterations=int(h["iterations"][p, c]), validations=int(h["validations"][p, c]),
-                   best_iteration=int(h["best_iteration"][p, c]), mutual_count=int(h["mutual_count"][p, c]))
+        out = _ransac_dict(h, (p, c))
+        out["mutual_count"] = int(h["mutual_count"][p, c])
         if "nearest" in h:
-            near = h["nearest"][p, self.offsets[c]:self.offsets[c] + Ns]
-            sel = np.nonzero(near >= 0)[0]
-            out["correspondence_set"] = np.stack([sel, near[sel]], 1).astype(np.int64)
-        if "gt_inliers" in h:
-            k = out["mutual_count"]
-            out["gt_inliers"] = int(h["gt_inliers"][p, c])
-            out["inlier_ratio"] = out["gt_inliers"] / k if k else 0.0
-        return out
+            out["correspondence_set"] = _correspondence_set(h["nearest"][p, self.offsets[c]:self.offsets[c] + int(h["ns"][p, c])])
+        return _gt_figures(out, h, (p, c), out["mutual_count"])
 
 
 def register_pairs_counts(kp, count, pairs, max_correspondence_distance, num_keypts=MATCHING_COUNTS, ransac_n=4, edge_similarity=0.9,
@@ -567,43 +584,24 @@ def register_pairs_counts(kp, count, pairs, max_correspondence_distance, num_key
     the winner's correspondences.  num_keypts: strictly ascending, 1 .. 8192, at most 16 of them.
     -> PairRegistrationCounts (device tensors; .host(p, c) for a dict, .at(c) for the tensors of one count)."""
     lib = _lib.load()
-    kp = ops._req(kp, torch.float32, "kp", 3)
-    count = ops._req(count, torch.int32, "count", 1)
-    pairs = ops._req(pairs, torch.int32, "pairs", 2)
-    dev = kp.device
-    if not kp.is_contiguous() or not count.is_contiguous() or not pairs.is_contiguous() or pairs.shape[1] != 2:
-        raise ValueError("register_pairs_counts: kp, count and pairs must be contiguous, pairs [P, 2]")
-    n_blocks, K, ld = kp.shape
+    kp, count, pairs, n_blocks, K, ld, P, dev = _blocks("register_pairs_counts", kp, count, pairs, 0)
     C = ld - 4
-    if count.shape[0] != n_blocks or not 1 <= n_blocks <= _lib.MAX_BATCH or K < 1 or C not in (16, 32, 64) or not 3 <= int(ransac_n) <= 8:
+    if n_blocks > _lib.MAX_BATCH or C not in (16, 32, 64) or not 3 <= int(ransac_n) <= 8:
         raise ValueError("register_pairs_counts takes 1 to %d blocks, descriptors of 16, 32 or 64 floats and ransac_n in 3..8 (got kp %s, "
                          "count %s, ransac_n %s)" % (_lib.MAX_BATCH, tuple(kp.shape), tuple(count.shape), ransac_n))
-    ks = [int(k) for k in num_keypts]
-    if (not 1 <= len(ks) <= _lib.REPEAT_COUNTS_MAX or any(not 1 <= k <= _lib.MATCH_KMAX for k in ks)
-            or any(b <= a for a, b in zip(ks, ks[1:]))):
-        raise ValueError("register_pairs_counts: num_keypts %s must be 1 to %d strictly ascending counts in 1..%d"
-                         % (ks, _lib.REPEAT_COUNTS_MAX, _lib.MATCH_KMAX))
-    P = pairs.shape[0]
+    ks, c_ks = _counts("register_pairs_counts", num_keypts, _lib.MATCH_KMAX)
     if gt is not None:
-        gt = ops._req(gt, torch.float32, "gt", 3)
-        if tuple(gt.shape) != (P, 3, 4) or not gt.is_contiguous():
-            raise ValueError("register_pairs_counts: gt of shape %s for %d pairs" % (tuple(gt.shape), P))
-    if out is None:
-        out = PairRegistrationCounts(P, ks, dev, gt is not None, nearest)
-    elif (not isinstance(out, PairRegistrationCounts) or out.T.device != dev
-          or (out.P, out.num_keypts, out.gt_inliers is not None, out.nearest is not None) != (P, tuple(ks), gt is not None, bool(nearest))):
-        raise ValueError("register_pairs_counts: out= was made for another call")
-    out._cache = None
+        gt = _gt32("register_pairs_counts", gt, P)
+    out = _reuse("register_pairs_counts", out, PairRegistrationCounts, (P, tuple(ks), gt is not None, bool(nearest)), dev,
+                 lambda: PairRegistrationCounts(P, ks, dev, gt is not None, nearest))
     # rows each pair uses at each count (plumbing for host(): fitness = inliers / Ns)
     used = torch.stack([count.clamp(0, min(K, k)) for k in ks], 1)                  # (device only: nothing to copy under capture)
     valid = (pairs >= 0) & (pairs < n_blocks)
     rows = used[pairs.clamp(0, n_blocks - 1).long()] * valid[:, :, None]           # [P, 2, n]
     out.ns, out.nt = rows[:, 0], rows[:, 1]
     st = ops._stream(dev)
-    c_ks, n, mv = (_lib.C.c_int * len(ks))(*ks), len(ks), int(max_validation)
-    per_call = max(PAIRS_PER_CALL // n, 1)
-    for p0 in range(0, P, per_call):
-        s = slice(p0, min(p0 + per_call, P))
+    n, mv = len(ks), int(max_validation)
+    for s in _chunks(P, max(PAIRS_PER_CALL // n, 1)):
         m = s.stop - s.start
         ws = ops.workspace(lib.d3f_register_pairs_counts_workspace_bytes(m, n_blocks, K, _lib.C.addressof(c_ks), n, mv), dev)
         rc = lib.d3f_register_pairs_counts(
@@ -635,29 +633,30 @@ def frame_pairs(n_pairs, device=None):
     return torch.from_numpy(a).to(_dev(device))
 
 
-class PairPoseErrors:
+class PairPoseErrors(_PairResult):
     """Result of pose_errors: DEVICE tensors rte f64[P, n] (metres), rre_deg f64[P, n] (degrees, NaN kept), flags i32[P, n] (bit 0:
     rte under its threshold, bit 1: rre under its threshold and no NaN, bit 2: both = success) and sums f64[n, 8] (per column the
     sums of d3f_pose_errors' meters: rte sum / square sum / number, the same of rre_deg, successes, P); n is 1 for a [P, 3, 4] input
     (the tensors are then [P]).  .meters(c) turns the sums into the reference's AverageMeter figures."""
+    FIELDS = ("rte", "rre_deg", "flags", "sums")
 
     def __init__(self, P, per_pair, flat, device):
         self.P, self.per_pair, self.flat = P, per_pair, flat
+        self.key = (P, per_pair, flat)
         shape = (P,) if flat else (P, per_pair)
         self.rte = torch.empty(shape, dtype=torch.float64, device=device)
         self.rre_deg = torch.empty(shape, dtype=torch.float64, device=device)
         self.flags = torch.empty(shape, dtype=torch.int32, device=device)
         self.sums = torch.empty((per_pair, 8), dtype=torch.float64, device=device)
 
-    _cache = None
+    def _read(self, name):
+        a = super()._read(name)
+        return a if name == "sums" else a.reshape(self.P, self.per_pair)
 
     def host(self):
         """One read-back of the whole result, kept until the next pose_errors(out=self): dict of numpy arrays rte, rre_deg, flags
         ([P, n], a column per count) and sums [n, 8]."""
-        if self._cache is None:
-            two = lambda t: t.cpu().numpy().reshape(self.P, self.per_pair)
-            self._cache = dict(rte=two(self.rte), rre_deg=two(self.rre_deg), flags=two(self.flags), sums=self.sums.cpu().numpy())
-        return self._cache
+        return self._host()
 
     def meters(self, c=0):
         """{"rte" | "rre" | "success": dict(sum, count, avg, var)} of column c: the AverageMeters of tester.py:252 after the last pair
@@ -698,11 +697,7 @@ def pose_errors(T, gt, rte_threshold=KITTI_SUCCESS["rte_threshold"], rre_thresho
     thr = (float(rte_threshold), float(rre_threshold))
     if not (thr[0] > 0.0 and thr[1] > 0.0):
         raise ValueError("pose_errors: thresholds %r, %r" % (rte_threshold, rre_threshold))
-    if out is None:
-        out = PairPoseErrors(P, n, flat, dev)
-    elif not isinstance(out, PairPoseErrors) or (out.P, out.per_pair, out.flat) != (P, n, flat) or out.rte.device != dev:
-        raise ValueError("pose_errors: out= was made for another call")
-    out._cache = None
+    out = _reuse("pose_errors", out, PairPoseErrors, (P, n, flat), dev, lambda: PairPoseErrors(P, n, flat, dev))
     if P == 0:
         out.sums.zero_()                                         # (plumbing: the meters of no pairs; an empty tensor has no address)
         return out
@@ -734,7 +729,7 @@ def register_kitti_pairs(kp, count, gt, voxel_size, seed=0, out=None):
         raise ValueError("register_kitti_pairs: %d keypoint blocks, not two per pair" % kp.shape[0])
     P = kp.shape[0] // 2
     if out is not None and not isinstance(out, KittiRegistration):
-        raise ValueError("register_kitti_pairs: out= was made for another call")
+        raise _another_call("register_kitti_pairs")
     pairs = out.pairs if out is not None else frame_pairs(P, kp.device)
     reg = register_pairs(kp, count, pairs, seed=seed, out=out.registration if out is not None else None, **EVALUATE_KITTI(voxel_size))
     err = pose_errors(reg.T, gt, out=out.errors if out is not None else None, **KITTI_SUCCESS)
@@ -759,28 +754,29 @@ def sanitize_descriptors(kp):
     return kp
 
 
-class SceneMatching:
+class SceneMatching(_PairResult):
     """Result of matching_summary: DEVICE tensors ratio_e8 i32[P, n] (per pair and count the inlier ratio at the 8 decimals of the
     reference's result file, times 1e8; 0 for a pair gt.log does not list) and figures i64[S, n, 4] (per scene and count: ground-truth
     pairs, pairs above inlier_ratio, sum of gt_inliers and sum of ratio_e8 over the ground-truth pairs).  .scenes(), .overall() and
     .rows(c) share one read-back."""
+    FIELDS = ("ratio_e8", "figures", "gt_inliers", "gt_flag")
 
     def __init__(self, P, n, scene_start, inlier_ratio, device):
         self.P, self.n, self.scene_start, self.inlier_ratio = P, n, tuple(int(v) for v in scene_start), float(inlier_ratio)
+        self.key = (P, n, self.scene_start, self.inlier_ratio)
         self.S = len(self.scene_start) - 1
         self.ratio_e8 = torch.empty((P, n), dtype=torch.int32, device=device)
         self.figures = torch.empty((self.S, n, 4), dtype=torch.int64, device=device)
         self.gt_inliers = self.gt_flag = None                   # the inputs of the call, kept for the read-back
 
-    _cache = None
+    def _read(self, name):
+        a = super()._read(name)
+        return a.reshape(self.P, self.n) if name == "gt_inliers" else a
 
     def host(self):
         """One read-back of the whole result, kept until the next matching_summary(out=self): dict of numpy arrays ratio_e8 [P, n],
         figures [S, n, 4], gt_inliers [P, n] and gt_flag [P]."""
-        if self._cache is None:
-            self._cache = dict(ratio_e8=self.ratio_e8.cpu().numpy(), figures=self.figures.cpu().numpy(),
-                               gt_inliers=self.gt_inliers.cpu().numpy().reshape(self.P, self.n), gt_flag=self.gt_flag.cpu().numpy())
-        return self._cache
+        return self._host()
 
     def scenes(self):
         """[scene][count] -> dict(correct, gt, recall, ave_num_inliers, ave_inlier_ratio): the keys and conventions of
@@ -847,25 +843,16 @@ def matching_summary(mutual_count, gt_inliers=None, gt_flag=None, scene_start=No
             or not (mutual_count.is_contiguous() and gt_inliers.is_contiguous() and gt_flag.is_contiguous())):
         raise ValueError("matching_summary: mutual_count %s, gt_inliers %s, gt_flag %s (contiguous [P, n], [P, n], [P])"
                          % (tuple(mutual_count.shape), tuple(gt_inliers.shape), tuple(gt_flag.shape)))
-    starts = [int(v) for v in np.asarray(scene_start).reshape(-1)]
-    S = len(starts) - 1
-    if (not 0 <= S <= _lib.SCENES_MAX or starts[0] != 0 or starts[-1] != P or any(b < a for a, b in zip(starts, starts[1:]))):
-        raise ValueError("matching_summary: scene_start %s must hold 1 to %d ascending ints from 0 to P = %d" % (starts, _lib.SCENES_MAX + 1, P))
+    starts, c_starts = _scene_starts("matching_summary", scene_start, P)
     ratio = float(inlier_ratio)
     if ratio != ratio:
         raise ValueError("matching_summary: inlier_ratio %r" % (inlier_ratio,))
     dev = mutual_count.device
-    if out is None:
-        out = SceneMatching(P, n, starts, ratio, dev)
-    elif (not isinstance(out, SceneMatching) or (out.P, out.n, out.scene_start, out.inlier_ratio) != (P, n, tuple(starts), ratio)
-          or out.ratio_e8.device != dev):
-        raise ValueError("matching_summary: out= was made for another call")
-    out._cache = None
+    out = _reuse("matching_summary", out, SceneMatching, (P, n, tuple(starts), ratio), dev, lambda: SceneMatching(P, n, starts, ratio, dev))
     out.gt_inliers, out.gt_flag = gt_inliers, gt_flag
-    c_starts, c_ratio = (_lib.C.c_int * (S + 1))(*starts), _lib.C.c_double(ratio)
-    ptr = lambda t: t.data_ptr() if t.numel() else None          # (an empty tensor has no address)
-    rc = lib.d3f_matching_summary(ptr(mutual_count), ptr(gt_inliers), ptr(gt_flag), P, n, _lib.C.addressof(c_starts), S,
-                                  _lib.C.addressof(c_ratio), ptr(out.ratio_e8), ptr(out.figures), ops._stream(dev))
+    c_ratio = _lib.C.c_double(ratio)
+    rc = lib.d3f_matching_summary(_ptr(mutual_count), _ptr(gt_inliers), _ptr(gt_flag), P, n, _lib.C.addressof(c_starts), out.S,
+                                  _lib.C.addressof(c_ratio), _ptr(out.ratio_e8), _ptr(out.figures), ops._stream(dev))
     _lib.check(rc, "matching_summary")
     return out
 
@@ -886,7 +873,7 @@ def match_scenes(kp, count, pairs, gt, gt_flag, scene_start, num_keypts=EVALUATE
     sanitize_descriptors(kp) -- IN PLACE, skipped with nan_to_num=False --, match_pairs and matching_summary, no read-back in between
     (capturable: pass the previous result as `out`).  -> SceneMatches (.matching, .summary)."""
     if out is not None and not isinstance(out, SceneMatches):
-        raise ValueError("match_scenes: out= was made for another call")
+        raise _another_call("match_scenes")
     if nan_to_num:
         sanitize_descriptors(kp)
     m = match_pairs(kp, count, pairs, gt, num_keypts=num_keypts, distance_threshold=distance_threshold,
@@ -907,32 +894,32 @@ def _round_half_away(x):
     return f + (1 if x - f >= 0.5 else 0)
 
 
-class SceneRecall:
+class SceneRecall(_PairResult):
     """Result of registration_recall: DEVICE tensors error f64[P, n] (the transformation error p of mrComputeTransformationError where
     the pair has a result and a ground truth and is not consecutive, 0 elsewhere; NaN kept), flags i32[P, n] (bit 0: good, bit 1:
     counted in rs_num, bit 2: false positive, bit 3: counted in gt_num) and figures i64[S, n, 5] (per scene and count: good, bad,
     false_pos, gt_num, rs_num); n is 1 for a [P, 3, 4] / [P, 4, 4] input (error and flags are then [P]).  .host(), .scenes(),
     .overall(c) and .failed(c) share one read-back."""
+    FIELDS = ("error", "flags", "figures", "ids")
 
     def __init__(self, P, n, flat, scene_start, err2, logged, device):
         self.P, self.n, self.flat, self.scene_start = P, n, flat, tuple(int(v) for v in scene_start)
         self.err2, self.logged, self.S = float(err2), bool(logged), len(self.scene_start) - 1
+        self.key = (P, n, flat, self.scene_start, self.err2, self.logged)
         shape = (P,) if flat else (P, n)
         self.error = torch.empty(shape, dtype=torch.float64, device=device)
         self.flags = torch.empty(shape, dtype=torch.int32, device=device)
         self.figures = torch.empty((self.S, n, 5), dtype=torch.int64, device=device)
         self.ids = None                                         # an input of the call, kept for the read-back
 
-    _cache = None
+    def _read(self, name):
+        a = super()._read(name)
+        return a if name == "figures" else a.reshape(self.P, 2 if name == "ids" else self.n)
 
     def host(self):
         """One read-back of the whole result, kept until the next registration_recall(out=self): dict of numpy arrays error [P, n],
         flags [P, n], figures [S, n, 5] and ids [P, 2]."""
-        if self._cache is None:
-            two = lambda t: t.cpu().numpy().reshape(self.P, self.n)
-            self._cache = dict(error=two(self.error), flags=two(self.flags), figures=self.figures.cpu().numpy(),
-                               ids=self.ids.cpu().numpy().reshape(self.P, 2))
-        return self._cache
+        return self._host()
 
     def scenes(self):
         """[scene][count] -> dict(good, bad, false_pos, gt_num, rs_num, recall, precision): the integers of `figures`, recall = good /
@@ -1001,25 +988,17 @@ def registration_recall(T, gt, info, gt_flag, ids, scene_start, err2=RECALL_3DMA
             or not all(t.is_contiguous() for t in (gt, info, gt_flag, ids) + ((result_flag,) if result_flag is not None else ()))):
         raise ValueError("registration_recall: gt %s, info %s, gt_flag %s, ids %s for T %s (contiguous [P, 4, 4], [P, 6, 6], [P], [P, 2])"
                          % (tuple(gt.shape), tuple(info.shape), tuple(gt_flag.shape), tuple(ids.shape), tuple(T.shape)))
-    starts = [int(v) for v in np.asarray(scene_start).reshape(-1)]
-    S = len(starts) - 1
-    if not 0 <= S <= _lib.SCENES_MAX or starts[0] != 0 or starts[-1] != P or any(b < a for a, b in zip(starts, starts[1:])):
-        raise ValueError("registration_recall: scene_start %s must hold 1 to %d ascending ints from 0 to P = %d" % (starts, _lib.SCENES_MAX + 1, P))
+    starts, c_starts = _scene_starts("registration_recall", scene_start, P)
     e2 = float(err2)
     if not e2 > 0.0:
         raise ValueError("registration_recall: err2 %r" % (err2,))
-    if out is None:
-        out = SceneRecall(P, n, flat, starts, e2, logged, dev)
-    elif (not isinstance(out, SceneRecall) or out.error.device != dev
-          or (out.P, out.n, out.flat, out.scene_start, out.err2, out.logged) != (P, n, flat, tuple(starts), e2, bool(logged))):
-        raise ValueError("registration_recall: out= was made for another call")
-    out._cache = None
+    out = _reuse("registration_recall", out, SceneRecall, (P, n, flat, tuple(starts), e2, bool(logged)), dev,
+                 lambda: SceneRecall(P, n, flat, starts, e2, logged, dev))
     out.ids = ids
-    c_starts, c_err2 = (_lib.C.c_int * (S + 1))(*starts), _lib.C.c_double(e2)
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None      # (an empty tensor has no address)
-    rc = lib.d3f_registration_recall(ptr(T), 1 if logged else 0, ptr(gt), ptr(info), ptr(gt_flag), ptr(result_flag), ptr(ids), P, n,
-                                     _lib.C.addressof(c_starts), S, _lib.C.addressof(c_err2), ptr(out.error), ptr(out.flags),
-                                     ptr(out.figures), ops._stream(dev))
+    c_err2 = _lib.C.c_double(e2)
+    rc = lib.d3f_registration_recall(_ptr(T), 1 if logged else 0, _ptr(gt), _ptr(info), _ptr(gt_flag), _ptr(result_flag), _ptr(ids), P, n,
+                                     _lib.C.addressof(c_starts), out.S, _lib.C.addressof(c_err2), _ptr(out.error), _ptr(out.flags),
+                                     _ptr(out.figures), ops._stream(dev))
     _lib.check(rc, "registration_recall")
     return out
 
@@ -1046,13 +1025,13 @@ def register_scenes(kp, count, pairs, gt, info, gt_flag, ids, scene_start, num_k
     read-back in between (capturable: pass the previous result as `out`).  T and the matching figures are bit-equal to the
     stand-alone calls.  -> SceneRegistration (.registration, .matching, .recall): both recalls of every scene at every count."""
     if out is not None and not isinstance(out, SceneRegistration):
-        raise ValueError("register_scenes: out= was made for another call")
+        raise _another_call("register_scenes")
     gt = ops._req(gt, torch.float64, "gt", 3)
     if tuple(gt.shape[1:]) != (4, 4):
         raise ValueError("register_scenes: gt of shape %s ([P, 4, 4])" % (tuple(gt.shape),))
     many = isinstance(num_keypts, (tuple, list))
     if out is not None and isinstance(out.registration, PairRegistrationCounts) != many:
-        raise ValueError("register_scenes: out= was made for another call")
+        raise _another_call("register_scenes")
     if nan_to_num:
         sanitize_descriptors(kp)
     if out is not None:

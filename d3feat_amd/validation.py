@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .registration import _PairResult, _reuse
 
 VALIDATION_3DMATCH = dict(safe_radius=0.1, keypts_num=256, det_loss_weight=1.0)      # training_3DMatch.py
 VALIDATION_KITTI = dict(safe_radius=1.0, keypts_num=1024, det_loss_weight=1.0)       # training_KITTI.py
@@ -22,17 +23,19 @@ FIGURES = ("circle", "contrastive", "det", "accuracy", "d_pos", "d_neg")        
 SKIP = (0.0, 0.0, -1.0, 0.0, 0.0)                                                    # KPFCNN_model.py:179-184
 
 
-class PairValidation:
+class PairValidation(_PairResult):
     """Result of validation_pairs: DEVICE tensors.  values f32[P, 8] (circle, contrastive, det, accuracy, d_pos, d_neg, accurate rows,
     n), status i32[P] (0; _lib.VP_INDEX_RANGE: an index outside the pair's rows; _lib.VP_COUNT_RANGE: n outside 0 .. the list length /
     1024 -- both give the skip tuple), sums f64[6] / counts i64[6]: per figure the sum over the pairs where it is != 0 (accuracy: > 0)
     and how many those are.  loss: which descriptor loss is THE desc_loss of means() / line(): 'circle_loss' (what the model class
     uses, KPFCNN_model.py:157) or 'desc_loss' (the contrastive entry of LOSS_CHOICES)."""
+    FIELDS = ("values", "status", "sums", "counts")
 
     def __init__(self, P, device, loss="circle_loss"):
         if loss not in ("circle_loss", "desc_loss"):
             raise ValueError("PairValidation: loss %r is neither 'circle_loss' nor 'desc_loss'" % (loss,))
         self.P, self.loss = P, loss
+        self.key = (P,)
         self.values = torch.empty((P, 8), dtype=torch.float32, device=device)
         self.status = torch.empty((P,), dtype=torch.int32, device=device)
         self.sums = torch.empty((6,), dtype=torch.float64, device=device)
@@ -158,12 +161,8 @@ def validation_pairs(features, scores, points, anc_idx, pos_idx, n=None, row0=No
             raise ValueError("validation_pairs: row0 holds %d offsets for %d pairs (P + 1 are needed)" % (row0.numel(), P))
     if ld < 1:                                                   # no index pairs at all: n = 0 for every pair, the skip tuple
         anc_idx = pos_idx = torch.zeros((P, 1), dtype=torch.int32, device=dev)
-    if out is None:
-        out = PairValidation(P, dev, loss)
-    elif not isinstance(out, PairValidation) or out.P != P or out.values.device != dev:
-        raise ValueError("validation_pairs: out= was made for another call")
-    else:
-        out.loss = loss
+    out = _reuse("validation_pairs", out, PairValidation, (P,), dev, lambda: PairValidation(P, dev, loss))
+    out.loss = loss
     ldi = max(ld, 1)
     ws = ops.workspace(lib.d3f_validation_pairs_workspace_bytes(P, ldi), dev)
     rc = lib.d3f_validation_pairs(features.data_ptr(), ldd, C, scores.data_ptr(), lds, points.data_ptr(), ldp, N, row0.data_ptr(),
