@@ -103,6 +103,9 @@ SIGNATURES = {
     "d3f_validation_pairs_workspace_bytes": (_sz, [_i, _i]),
     "d3f_validation_pairs": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _f, _f, _f, _f] + [_vp] * 5
                              + [_sz, _vp]),
+    "d3f_loss_gradients_workspace_bytes": (_sz, [_i, _i, _i]),
+    "d3f_loss_gradients": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _f, _i, _f, _f, _f, _f, _i, _vp, _i, _vp, _i,
+                                _vp, _vp, _vp, _sz, _vp]),
     "d3f_pose_errors": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_sanitize_descriptors": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "d3f_matching_summary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),

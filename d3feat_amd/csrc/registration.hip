@@ -747,6 +747,11 @@ extern "C" int d3f_repeatability_pairs(const float* kp, int n_blocks, int K, int
 #include "rp_validation.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Gradient of desc_loss + det_loss of every pair with respect to the descriptor and score rows, five launches (d3f_loss_gradients)
+// ---------------------------------------------------------------------------------------------------------------------
+#include "rp_loss_grad.h"
+
+// ---------------------------------------------------------------------------------------------------------------------
 // KITTI test metric (RTE, RRE, success, the running meters) of every estimate in two launches (d3f_pose_errors)
 // ---------------------------------------------------------------------------------------------------------------------
 #include "rp_pose_errors.h"

@@ -1,6 +1,6 @@
 // Validation figures of every pair in one call (d3f_validation_pairs; models/KPFCNN_model.py:131-186 + utils/loss.py of the
 // reference: circle loss, contrastive loss, detection loss, accuracy, mean positive / negative distance; the split totals of
-// utils/trainer.py:442-452).  Forward only.  (included by registration.hip; of its kernels only rg_desc_d2 and rg_dispatch_C.)
+// utils/trainer.py:442-452).  The forward; its gradient is rp_loss_grad.h, which runs these kernels first.  (included by registration.hip; of its kernels only rg_desc_d2 and rg_dispatch_C.)
 //
 // A pair is a stack [anchor; positive] of rows with n index pairs (ai, pi).  With D[i,j] = sqrt(|f[ai[i]] - f[pi[j]]|^2 + 1e-12) and
 // KD[i,j] the same over the points of ai[i] and ai[j], every figure is a sum over i of a function of four per-row numbers

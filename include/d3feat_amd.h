@@ -719,7 +719,7 @@ int d3f_overlap_pairs(const void* grid, size_t grid_bytes, int N, int B, const i
                       int* count_dev, int* nearest_dev, int ld_nearest, void* stream);
 
 /* Validation figures of P pairs in three launches, whatever P is (models/KPFCNN_model.py:131-186 with utils/loss.py of the reference:
- * what its model class evaluates per validation pair, and utils/trainer.py:442-452, 467-471: the means over a split).  Forward only.
+ * what its model class evaluates per validation pair, and utils/trainer.py:442-452, 467-471: the means over a split).  The forward; d3f_loss_gradients adds the gradient.
  * Pair p is the stack [anchor; positive] held by rows row0_dev[p] .. row0_dev[p + 1] of three row arrays, each a base pointer and a
  * leading dimension in floats, so that column views of one block of [xyz | descriptor | score] records need no copy:
  *   desc f32[n_rows, ldd] (C = 16 / 32 / 64 columns read), score f32[n_rows, lds] (one column), points f32[n_rows, ldp] (three).
@@ -756,6 +756,46 @@ int d3f_validation_pairs(const float* desc, int ldd, int C, const float* score, 
                          float safe_radius, int keypts_num, float det_loss_weight, float pos_margin, float neg_margin,
                          float log_scale, float* values, int* status_dev, double* sums_dev, int64_t* counts_dev, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* Loss gradients of P training pairs in five launches, whatever P is: the gradient of desc_loss + det_loss (models/KPFCNN_model.py:
+ * 143-191 with utils/loss.py of the reference; the regularisation term of :188-191 depends on the weights only and is not part of it)
+ * with respect to the rows of desc and score, together with the forward's values and status.  The inputs, the skip rule, the status
+ * and D, KD, FN, fp, cn, z, lse are those of d3f_validation_pairs, computed by the same kernels: values / status_dev are bit-equal to
+ * what that call writes.  contrastive = 0: desc_loss is the circle loss (what the model class uses); 1: the contrastive loss.
+ * With n = n_dev[p], q = pos_margin, m = neg_margin, L = log_scale, w = det_loss_weight, and for row i
+ *   T_i      = the columns j whose entry D[i,j] + 1e5 [i == j] is bit-equal to cn_i; share[i,j] = [j in T_i] / |T_i| (the equal split
+ *              of reduce_min's gradient; index pairs drawn with replacement make such ties the rule);
+ *   sab_i    = (s[ai[i]] + s[pi[i]]) + 1e-6;   live[i,j] = i != j and not FN[i,j] and D[i,j] < m;
+ *   sg_i     = sigmoid(L (fp_i - q) + lse_i),
+ * G = d loss / d D is the sum of
+ *   circle       G[i,i] += sg_i / n;   where live: G[i,j] -= (sg_i / n) exp(z[i,j] - lse_i) (m - D[i,j])   (the factor max(0, m - D) of
+ *                loss.py:176 is under stop_gradient: dz/dD = -L (m - D), and the 1 / L of :179 cancels the L)
+ *   contrastive  G[i,i] += [fp_i - q >= 0] / n;   G[i,j] -= share[i,j] [m - cn_i >= 0] / n   (tf.maximum passes the gradient to its
+ *                first argument on equality)
+ *   det, w != 0  G[i,i] += w sab_i / n;   G[i,j] -= share[i,j] w sab_i / n   (the diagonal column too when n = 1: the two cancel)
+ * and with a_i = f[ai[i]], p_j = f[pi[j]]:
+ *   d a_i = sum_j (G[i,j] / D[i,j]) (a_i - p_j);   d p_j = sum_i (G[i,j] / D[i,j]) (p_j - a_i);
+ *   the entry i adds w (fp_i - cn_i) / n to the score gradient of ai[i] and of pi[i].
+ * grad_desc f32[n_rows, ldg] (C columns written) and grad_score f32[n_rows, ldgs] (one column): row r of a pair receives the sum over
+ * the list entries that name it (tf.gather's gradient: duplicates add, a row may be named by both lists), the anchor entries in list
+ * order, then the positive entries in list order.  EVERY word of the C + 1 columns of all n_rows rows is written: zeros for the rows
+ * no list names, for a pair under the skip rule and for a pair whose status is not 0; the buffers need not be cleared, and may be
+ * column views of a record block.  The pairs' rows must not overlap (they cannot when row0_dev is non-decreasing).
+ * D, KD, the exponentials and the sums over j and i are fp32 (per wave an fmaf chain over ascending columns, the four waves of a
+ * 64-entry tile added in wave order); the four numbers of a row that G is made of are float64, rounded once.  n x n is never stored.
+ * No memset, no atomics, no read-back; every sum runs in an order that depends on (n, P, the lists) only: two calls give equal bits,
+ * and a call of P pairs gives the bits of P calls of one pair.  Capturable.
+ * workspace >= d3f_loss_gradients_workspace_bytes(P, ld_idx, C): (52 + 8 C) bytes per pair and index of min(ld_idx,
+ * D3F_VALIDATION_NMAX) rounded up to 64, else D3F_ERR_WORKSPACE; the function returns 0 for sizes the call refuses.
+ * D3F_ERR_ARG before anything touches the device: what d3f_validation_pairs refuses, ldg < C, ldgs < 1, contrastive not 0 / 1, a NULL
+ * pointer (with P == 0 only the two outputs are needed: they are zeroed by one launch).
+ * Asynchronous on `stream`, no allocation, no synchronisation. */
+size_t d3f_loss_gradients_workspace_bytes(int P, int ld_idx, int C);
+int d3f_loss_gradients(const float* desc, int ldd, int C, const float* score, int lds, const float* points, int ldp, int n_rows,
+                       const int* row0_dev, const int* anc_dev, const int* pos_dev, int ld_idx, const int* n_dev, int P,
+                       float safe_radius, int keypts_num, float det_loss_weight, float pos_margin, float neg_margin, float log_scale,
+                       int contrastive, float* grad_desc, int ldg, float* grad_score, int ldgs, float* values, int* status_dev,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* The KITTI test metric of P * per_pair estimated transforms in two launches (utils/tester.py:326-344 of the reference: relative
  * translation error, relative rotation error, success under both thresholds, and the sums of its three AverageMeters).
