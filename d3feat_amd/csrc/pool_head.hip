@@ -516,6 +516,9 @@ extern "C" int d3f_detect_head(const float* x, int N, int ldx, int C, const int*
     return D3F_OK;
 }
 
+// the head's backward and the transposed neighbour table (d3f_detect_head_backward, d3f_neighbor_transpose)
+#include "ph_head_backward.h"
+
 // ------------------------------------------------------------------------------------------------
 // Stand-alone epilogue: out = act(x * col_scale + col_shift + residual)  (network_blocks.py:149-160, :185-186)
 // ------------------------------------------------------------------------------------------------

@@ -61,3 +61,16 @@ def detection_head(features, inputs):
     ib = inputs.get('in_batches')
     group = ib.group if isinstance(ib, ops.StackGroups) else 0
     return ops.detect_head(features, inputs['neighbors'][0], lens_dev, include_zero, stack_group=group)
+
+
+def detection_head_backward(features, inputs, grad_features, grad_scores, transpose=None):
+    """The backward of detection_head: from the gradients with respect to its two outputs (either may be None; strided column views
+    of a record block are taken as they are) to the gradient with respect to the un-normalised `features`.  stack_group and the
+    include-zero vector come from `inputs` exactly as in the forward; inputs['in_batches_padded'], when present, is read as the
+    number of pad slots per cloud.  transpose: ops.neighbor_transpose(inputs['neighbors'][0], lens) when the caller keeps it."""
+    lens_dev = ops.as_lens(inputs['stack_lengths'], features.device)
+    include_zero = inputs.get('in_batches_padded')
+    ib = inputs.get('in_batches')
+    group = ib.group if isinstance(ib, ops.StackGroups) else 0
+    return ops.detect_head_backward(features, inputs['neighbors'][0], lens_dev, include_zero, grad_features, grad_scores,
+                                    stack_group=group, transpose=transpose)

@@ -1173,6 +1173,118 @@ def detect_head(x, neighbors, stack_lengths_dev, include_zero_dev, stack_group=0
     return _tag(desc, x), _tag(score, x)
 
 
+def _typed(t, dtype, name, ndim=None):
+    """_req without the device check: the shape checks of an entry point come before "there is no CPU path"."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor on a GPU (got %s)" % (name, type(t)))
+    if t.dtype != dtype:
+        raise TypeError("%s must be %s (got %s)" % (name, dtype, t.dtype))
+    if ndim is not None and t.dim() != ndim:
+        raise ValueError("%s must be %d-D (got shape %s)" % (name, ndim, tuple(t.shape)))
+    return t
+
+
+def _head_arguments(what, x, neighbors, stack_lengths_dev):
+    """The checks detect_head_backward and neighbor_transpose share, before the device is asked -> (nb, ldi, lens)."""
+    nb, ldi = _rows(_typed(neighbors, torch.int32, "neighbors"), "neighbors")
+    lens = _typed(stack_lengths_dev, torch.int32, "stack_lengths_dev", 1)
+    if not lens.is_contiguous():
+        raise ValueError("%s: stack_lengths_dev must be contiguous" % what)
+    if not 1 <= lens.numel() <= 255:
+        raise ValueError("%s: %d clouds (1 .. 255)" % (what, lens.numel()))
+    if nb.shape[0] * nb.shape[1] > (1 << 31) - 8192:
+        raise ValueError("%s: %d x %d neighbour slots (at most 2^31 - 8192)" % (what, nb.shape[0], nb.shape[1]))
+    if x is not None and x.shape[0] != nb.shape[0]:
+        raise ValueError("%s: %d feature rows, %d neighbour rows" % (what, x.shape[0], nb.shape[0]))
+    return nb, ldi, lens
+
+
+def _on_device(what, **tensors):
+    """There is no CPU path: after the shape checks, before the library is asked."""
+    for name, t in tensors.items():
+        if t is not None and not t.is_cuda:
+            raise _lib.D3FeatLibraryError("%s: %s is on %s: d3feat_amd has no CPU path" % (what, name, t.device))
+
+
+def neighbor_transpose(neighbors, stack_lengths_dev):
+    """The transposed neighbour table (d3f_neighbor_transpose, include/d3feat_amd.h) -> (start i32[N + 1], edges i32[N * K]) on the
+    device: row j's segment edges[start[j] : start[j + 1]] holds the edges e = i * K + k with neighbors[i, k] == j in ascending e --
+    np.argsort(kind="stable") of the valid edges.  Nine launches, no read-back, capturable."""
+    lib = _lib.load()
+    nb, ldi, lens = _head_arguments("neighbor_transpose", None, neighbors, stack_lengths_dev)
+    _on_device("neighbor_transpose", neighbors=nb, stack_lengths_dev=lens)
+    dev = nb.device
+    N, K = nb.shape
+    start = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+    edges = torch.empty((max(N * K, 1),), dtype=torch.int32, device=dev)
+    nbytes = lib.d3f_neighbor_transpose_workspace_bytes(N, K)
+    ws = workspace(nbytes, dev)
+    with _timed("neighbor_transpose", dict(N=N, K=K), dev):
+        rc = lib.d3f_neighbor_transpose(nb.data_ptr(), N, ldi, K, lens.data_ptr(), lens.numel(), start.data_ptr(), edges.data_ptr(),
+                                        ws.data_ptr(), nbytes, _stream(dev))
+    _lib.check(rc, "neighbor_transpose")
+    return start, edges[:N * K]
+
+
+def detect_head_backward(x, neighbors, stack_lengths_dev, include_zero_dev, grad_desc, grad_score, stack_group=0, transpose=None,
+                         out=None):
+    """Backward of detect_head -> gx f32[N, C], the gradient with respect to x, from the gradients with respect to the rows of desc
+    (grad_desc f32[N, C]) and of score (grad_score f32[N] or [N, 1]); either may be None (zero), both may be strided column views of
+    a record block (validation.loss_gradients_records(out_records=...)).  transpose: (start, edges) of neighbor_transpose for the
+    same `neighbors`; built here when None.  include_zero_dev, when given, is read as the NUMBER of pad slots of every cloud's row of
+    in_batches.  The definition, the tie rules and the summation orders: include/d3feat_amd.h (d3f_detect_head_backward).  Rows at
+    or beyond sum(stack_lengths_dev) of `out` are left alone.  Six launches, no read-back, capturable."""
+    lib = _lib.load()
+    x, ldx = _rows(_typed(x, torch.float32, "x"), "x")
+    nb, ldi, lens = _head_arguments("detect_head_backward", x, neighbors, stack_lengths_dev)
+    dev = x.device
+    N, Cc = x.shape
+    if not 1 <= Cc <= 128:
+        raise ValueError("detect_head_backward: C = %d (1 .. 128)" % Cc)
+    if int(stack_group) < 0:
+        raise ValueError("detect_head_backward: stack_group = %r" % (stack_group,))
+    gd = ldg = gs = ldgs = None
+    if grad_desc is not None:
+        gd, ldg = _rows(_typed(grad_desc, torch.float32, "grad_desc"), "grad_desc")
+        if tuple(gd.shape) != (N, Cc):
+            raise ValueError("detect_head_backward: grad_desc is %s, x %s" % (tuple(gd.shape), (N, Cc)))
+    if grad_score is not None:
+        gs = _typed(grad_score, torch.float32, "grad_score")
+        if gs.dim() == 1:
+            gs = gs.unsqueeze(1)
+        if gs.dim() != 2 or tuple(gs.shape) != (N, 1):
+            raise ValueError("detect_head_backward: grad_score is %s, wanted %d rows of one column" % (tuple(grad_score.shape), N))
+        ldgs = int(max(gs.stride(0), 1)) if N > 1 else 1
+    if include_zero_dev is not None:
+        include_zero_dev = _typed(include_zero_dev, torch.int32, "include_zero_dev", 1)
+        if include_zero_dev.numel() != lens.numel() or not include_zero_dev.is_contiguous():
+            raise ValueError("detect_head_backward: include_zero_dev must be contiguous, one entry per cloud")
+    if out is not None:
+        out, ldo = _rows(_typed(out, torch.float32, "out"), "out")
+        if tuple(out.shape) != (N, Cc):
+            raise ValueError("detect_head_backward: out is %s, x %s" % (tuple(out.shape), (N, Cc)))
+    _on_device("detect_head_backward", x=x, neighbors=nb, stack_lengths_dev=lens, include_zero_dev=include_zero_dev, grad_desc=gd,
+               grad_score=gs, out=out)
+    if transpose is None:
+        transpose = neighbor_transpose(nb, lens)
+    start = _typed(transpose[0], torch.int32, "transpose[0]", 1)
+    edges = _typed(transpose[1], torch.int32, "transpose[1]", 1)
+    if start.numel() != N + 1 or edges.numel() < N * nb.shape[1] or not (start.is_contiguous() and edges.is_contiguous()):
+        raise ValueError("detect_head_backward: transpose must be (start i32[N + 1], edges i32[N * K]) of the same neighbours")
+    _on_device("detect_head_backward", start=start, edges=edges)
+    if out is None:
+        out, ldo = torch.empty((N, Cc), dtype=torch.float32, device=dev), Cc
+    B = lens.numel()
+    nbytes = lib.d3f_detect_head_backward_workspace_bytes(N, Cc, B)
+    ws = workspace(nbytes, dev)
+    with _timed("detect_head_backward", dict(N=N, K=nb.shape[1], C=Cc), dev):
+        rc = lib.d3f_detect_head_backward(x.data_ptr(), N, ldx, Cc, nb.data_ptr(), ldi, nb.shape[1], lens.data_ptr(), _ptr(include_zero_dev),
+                                          int(stack_group), B, start.data_ptr(), edges.data_ptr(), _ptr(gd), ldg or 0, _ptr(gs), ldgs or 0,
+                                          out.data_ptr(), ldo, ws.data_ptr(), nbytes, _stream(dev))
+    _lib.check(rc, "detect_head_backward")
+    return _tag(out, x)
+
+
 class RawRecords:
     """A cloud still in its file encoding (utils.ply.read_ply_records / utils.results.read_kitti_records): raw bytes + record
     layout.  FragmentEngine.submit takes it wherever it takes a float32 [n,3] cloud and decodes it on the GPU, straight into

@@ -797,6 +797,65 @@ int d3f_loss_gradients(const float* desc, int ldd, int C, const float* score, in
                        int contrastive, float* grad_desc, int ldg, float* grad_score, int ldgs, float* values, int* status_dev,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* The transposed neighbour table: for every row, the edges that name it, in a fixed order.  The scatter of every backward through a
+ * neighbour gather (the head's neighbour mean below; a KPConv's support features) becomes a gather in a defined order through it.
+ *   idx i32[N, ld_idx] (K columns), lens_dev i32[B]: n = min(N, sum(lens_dev)) is read on the device, N is the capacity.
+ *   Edge e = i * K + k (i < n, k < K) is VALID when 0 <= idx[i, k] < n -- the head's shadow rule: negative entries, n, anything above n.
+ *   start i32[N + 1]: start[j] .. start[j + 1] is row j's segment of `edges`; every start[j] with j >= n is the number of valid edges.
+ *   edges i32[N * K]: row j's segment holds the valid edges with idx[i, k] == j in ascending e (a row that names j twice appears
+ *     twice); words at or beyond the number of valid edges are left alone.
+ * The table IS np.argsort(keys, kind="stable") over the valid edges, integer for integer.  Built by a stable radix sort of (named row,
+ * e) and one bisection per row: nine launches whatever N, K and B are, no atomic on global memory, no memset, no read-back; capturable.
+ * D3F_ERR_ARG before anything touches the device: N < 0, K < 0, N * K > 2^31 - 8192 (the sort addresses whole 8192-slot tiles with
+ * 32-bit positions), ld_idx < K, B < 1 or > D3F_MAX_BATCH, a NULL start or lens_dev, a NULL edges or idx with N * K > 0.
+ * workspace >= d3f_neighbor_transpose_workspace_bytes(N, K) (about 16 bytes per slot of idx), else D3F_ERR_WORKSPACE; the function
+ * returns 0 for sizes the call refuses. */
+size_t d3f_neighbor_transpose_workspace_bytes(int N, int K);
+int d3f_neighbor_transpose(const int* idx, int N, int ld_idx, int K, const int* lens_dev, int B, int* start, int* edges, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
+/* Backward of d3f_detect_head (models/D3Feat.py:65-115): from the gradients with respect to the rows of desc (gdesc f32[n, ldg], C
+ * columns) and of score (gscore f32[n, ldgs], one column) -- either may be NULL and counts as zero; both may be column views of a
+ * record block, as d3f_loss_gradients writes them -- to gx f32[n, ldgx], the gradient with respect to x.  x, idx, lens_dev,
+ * include_zero_dev, stack_group, B and the capacity N as in d3f_detect_head, C <= 128; start / edges: the table
+ * d3f_neighbor_transpose made of the same idx.  Every word of the first n rows' C columns of gx is written; rows at or beyond n are
+ * left alone.
+ * With the forward's quantities -- m_b, den_b = m_b + 1e-6, y = x / den_b, the valid neighbours, num_i = max(#{valid neighbours with
+ * a non-zero row sum}, 1) (a constant: count_nonzero has no gradient), mean = S / num, d = y - mean, alpha = softplus(d) (with the
+ * forward's shortcuts), w_i = max_c y, beta = y / (1e-6 + w_i), a = alpha beta, s_i = max_c a --
+ *   1. T_i = {c : a[i,c] == s_i}, bit-equal in this kernel's arithmetic;  ga[i,c] = gscore_i / |T_i| on T_i, else 0 (the equal split of
+ *      reduce_max, the rule d3f_loss_gradients uses for reduce_min);
+ *   2. g_d = ga beta sigmoid(d);  g_beta = ga alpha;
+ *   3. gy[i,c] = g_d[i,c] + g_beta[i,c] / (1e-6 + w_i), and on W_i = {c : y[i,c] == w_i} plus gw_i / |W_i| with
+ *      gw_i = -sum_c g_beta[i,c] y[i,c] / (1e-6 + w_i)^2;
+ *   4. gS[i,:] = -g_d[i,:] / num_i;  gy[j,:] += sum over row j's segment of `edges`, in ascending e, of gS[e / K, :];
+ *   5. gx[i,c] = gy[i,c] / den_b;
+ *   6. per cloud gden_b = -sum_{i in b, c} gy[i,c] y[i,c] / den_b, split equally among the entries that tie for m_b and added to gx
+ *      there: the real entries with x == m_b, plus pads_b * C zeros when pads_b > 0 and m_b == 0 -- each shadow slot of the cloud's row
+ *      of in_batches gathers a whole zero ROW of C entries.  pads_b (datasets/common.py:453-496) = longest - len_b, plus 1 when all
+ *      clouds of the stack (of the stack_group) are equally long; when include_zero_dev is given its entry is read as that number
+ *      (the forward keeps reading it as a flag);
+ *   7. with ss = sum_c x^2 and desc = x rsqrt(ss):  gx += rsqrt(ss) (gdesc - desc (desc . gdesc)) where ss >= 1e-10, else
+ *      gx += gdesc rsqrt(1e-10).
+ * Summation orders: the segment sum of 4 is ONE fp32 chain per channel, started at zero, in ascending e, added to the row's own
+ * terms at the end.  The sum of 6 is float64: per row, lane l of 32 adds gy y of channels l, l + 32, ... in ascending order and the 32
+ * lane sums are combined by xor-butterfly over 16, 8, 4, 2, 1; per cloud, thread t of 256 adds the rows t, t + 256, ... counted from
+ * the cloud's first row, in ascending order, and the 256 sums are halved (sum[t] += sum[t + o], o = 128, 64, ..., 1): a tree that
+ * depends on the cloud's own length only.  The channel sums of 3 and 7 are the fp32 xor-butterfly of the forward.  No float atomic,
+ * and no workgroup waits for another: two calls give equal bits, and a concatenation of independent stacks under stack_group gives
+ * the bits of the stacks run alone provided neighbours stay inside their own cloud (the head's contract).
+ * Six launches (the forward's two per-cloud maximum launches, then: per-row terms, segment gather, per-cloud tree, finish); all sizes
+ * are read on the device; no memset, no read-back; capturable.
+ * D3F_ERR_ARG before anything touches the device: what d3f_detect_head refuses, N * K > 2^31 - 8192 (no table exists beyond),
+ * ldgx < C, ldg < C (gdesc given), ldgs < 1 (gscore given), a NULL x, lens_dev, start or gx, a NULL idx or edges with K > 0 (N == 0 is D3F_OK).  workspace >=
+ * d3f_detect_head_backward_workspace_bytes(N, C, B): (8 C + 12) bytes per row of capacity, else D3F_ERR_WORKSPACE; the function
+ * returns 0 for sizes the call refuses. */
+size_t d3f_detect_head_backward_workspace_bytes(int N, int C, int B);
+int d3f_detect_head_backward(const float* x, int N, int ldx, int C, const int* idx, int ld_idx, int K, const int* lens_dev,
+                             const int* include_zero_dev, int stack_group, int B, const int* start, const int* edges,
+                             const float* gdesc, int ldg, const float* gscore, int ldgs, float* gx, int ldgx, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* The KITTI test metric of P * per_pair estimated transforms in two launches (utils/tester.py:326-344 of the reference: relative
  * translation error, relative rotation error, success under both thresholds, and the sums of its three AverageMeters).
  *   T_est f32[P * per_pair, 12], row-major [R | t]; gt f32[P, 12] in the SAME direction as T_est: source -> target, the direction of
