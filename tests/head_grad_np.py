@@ -308,7 +308,12 @@ def torch_gradients(x, nb, lens, gdesc=None, gscore=None, group=0, pads=None, dt
 
 
 # ---- the case grid shared by tools/make_golden_head_grad.py and the two test files ------------------------------------------------------
-# name: (seed, C, K, lens, group, pads, dup, plant, head_case keywords).  At most about a hundred rows each.
+# name: (seed, C, K, lens, group, pads, dup, plant, head_case keywords).  At most about a hundred rows each (the 129- and 255-cloud
+# stacks: some 300 to 600).
+LENS_B255 = tuple(1 + i % 3 for i in range(254)) + (0,)                          # 255 clouds of 1 to 3 rows, the last empty: 507 rows
+# 255 clouds of 0 to 3 rows, half of them empty, clouds 100 .. 104 -- one whole group of five -- among them
+LENS_B255G5 = tuple(0 if (i % 3 == 0 or 100 <= i < 105) else (7 * i) % 4 for i in range(255))
+LENS_B129 = tuple(1 + (5 * i) % 8 for i in range(129))                           # 129 clouds of 1 to 8 rows: 577 rows
 GRID = {
     "c1": (11, 1, 17, (40, 30), 0, None, None, (), {}),
     "c20": (12, 20, 17, (40, 30), 0, None, None, (), {}),
@@ -333,6 +338,11 @@ GRID = {
     "negzero": (31, 20, 17, (30, 20), 0, None, None, ((33, 2, 0.0), (41, 7, 0.0)), dict(negative=(1,))),
     # explicit pad counts where the COUNT matters: the maximum of cloud 1 is the zero row, 3 C + 2 ties (derived: 10 C + 2; as a flag: C + 2)
     "negzero_pads": (31, 20, 17, (30, 20), 0, (0, 3), None, ((33, 2, 0.0), (41, 7, 0.0)), dict(negative=(1,))),
+    # stacks of D3F_MAX_BATCH = 255 clouds (one thread per cloud in the maximum's first kernel, d3f_find_elem's steps of 128 / 64 / 32
+    # from 129 / 65 / 33 clouds on); the clouds are kept this short: stacks of some 1100 rows find no clean seed in 64 tries
+    "b255": (32, 20, 5, LENS_B255, 0, None, None, (), {}),
+    "b255g5": (33, 32, 5, LENS_B255G5, 5, None, None, (), {}),
+    "b129": (34, 20, 9, LENS_B129, 0, None, None, (), {}),
 }
 STORED = ("c1", "c20", "c32", "dup", "negzero", "b6g2")       # cases whose float64 gradients the fixture holds
 EVALS = ("desc", "score", "both")                              # (gdesc, 0), (0, gscore), (gdesc, gscore)

@@ -145,6 +145,9 @@ TRANSPOSE = {
     "empty_cloud": lambda: (_neighbours(8, (30, 0, 20), 9), (30, 0, 20), 0),
     "empty_stack": lambda: (_neighbours(9, (0, 0), 4, N=6), (0, 0), 0),
     "tiles": lambda: (_neighbours(10, (600, 500), 65), (600, 500), 0),               # 71,500 edges: nine 8192-item tiles, two digit passes
+    "b255": lambda: (_neighbours(12, hg.LENS_B255, 5), hg.LENS_B255, 0),             # D3F_MAX_BATCH lengths summed by the key kernel
+    # 66,000 rows: keys of 17 bits, THREE 8-bit digit passes -- the finishing kernel reads the other buffer pair (four need 2^24 rows)
+    "rows_66000": lambda: (_neighbours(13, (40000, 26000), 2), (40000, 26000), 1),   # ld_idx = K + 1
 }
 
 
@@ -179,6 +182,10 @@ def test_transposed_table_is_the_stable_argsort(device, name):
         assert ws_[6] - ws_[5] >= 300 and ws_[8] == ws_[7]
     if name == "tiles":
         assert N * K > 8 * 8192 and len(we_) > 6 * 8192
+    passes = (max(n.bit_length(), 1) + 7) // 8                                       # 32 - clz(n) significant bits, 8 per digit pass
+    assert passes == {"rows_66000": 3, "tiles": 2, "empty_stack": 1}.get(name, passes)
+    if name == "b255":
+        assert len(lens) == 255 and lens[-1] == 0 and n == 507
 
 
 def test_transpose_through_ops(device):
@@ -206,7 +213,14 @@ def test_backward_against_float64(device, name):
     (negzero, (0, gscore): 1.82e-7), at most 0.21 of the tolerance (b3g1, (gdesc, 0): 5.09e-8 against 2.38e-7).  Per entry relatively
     on the all-non-positive cloud: 7.70e-5 (neg, (0, gscore): 7.70e-5 -- sums of gS terms of both signs at 1e12 cancel; the tolerance
     there is the 1e-4 cap, of which this is 0.77).  At C = 1 the identically-zero (gdesc, 0) rows came back at 9.4e-7 absolute against
-    the bound 1.5e-5."""
+    the bound 1.5e-5.
+
+    b255 / b255g5 / b129: stacks of 255 and 129 clouds of a few rows each (one thread per cloud in head_max_init_kernel, its serial
+    prefix and group scans, d3f_find_elem's steps of 128 / 64 / 32, whole empty groups of five), by the same rule.  Measured: at
+    most 1.36e-7 of the largest entry (b255g5, (0, gscore); float32 torch 1.09e-7), clamp rows of b129 1.21e-7; no comparison uses more
+    than 0.17 of its tolerance (b129's clamp rows, (gdesc, 0)), the ordinary rows at most 0.035.  Each of the three cases takes under
+    0.1 s (--durations inside the whole suite: b129 0.07 s, b255 and b255g5 0.04 s; the transposed table rows_66000 0.01 s, b255 under
+    0.005 s)."""
     c = hg.grid_case(name)
     st = _stack(device, c)
     for ev in hg.EVALS:

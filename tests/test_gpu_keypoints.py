@@ -132,6 +132,46 @@ def test_topk_stack_of_fragments_with_and_without_row_map(device, keep, K):
         assert np.array_equal(_bits(kp[j, :int(c[j])].cpu().numpy()), _bits(results[0][0][j, :int(c[j])]))
 
 
+@pytest.mark.parametrize("keep", [1, 5])
+def test_topk_stack_of_255_clouds(device, keep):
+    """A stack of D3F_MAX_BATCH = 255 clouds: 51 fragments of five clouds of 0 to 40 rows -- shorter than, as long as and longer than
+    K = 16 -- with one cloud of 5000 rows among them; keep = 1 keeps the first cloud of every fragment, keep = 5 all of them.  With and
+    without a per-cloud row_map; every kept cloud against the stable argsort tail.  0.01 s (keep = 1) and 0.02 s (keep = 5) on an
+    MI355X inside the full suite."""
+    from d3feat_amd import keypoints
+    B, group, K = 255, 5, 16
+    rng = np.random.default_rng(255 + keep)
+    lens = [int(x) for x in rng.integers(0, 41, B)]
+    lens[0], lens[5], lens[10], lens[130], lens[254] = 16, 0, 17, 5000, 40        # (clouds 0, 5, 10, 130 are kept at keep = 1 too)
+    assert min(lens) == 0 and sorted(set(lens))[-2] == 40 and lens.count(0) >= 2
+    s = (np.round(rng.standard_normal(sum(lens)) * 3.0) / 3.0).astype(np.float32)      # many ties: the reference row decides
+    rec = _records(rng, s)
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    row_map = np.concatenate([starts[b] + rng.permutation(lens[b]) for b in range(B)]).astype(np.int32)
+    internal = np.empty_like(rec)
+    internal[:] = rec[row_map]                       # input row m holds reference row row_map[m]
+    lens_dev = torch.tensor(lens, dtype=torch.int32, device=device)
+    kept = [f * group + c for f in range(B // group) for c in range(keep)]
+    assert len(kept) == 51 * keep and 130 in kept
+    results = []
+    for arr, rm in ((rec, None), (internal, torch.from_numpy(row_map).to(device))):
+        t = torch.from_numpy(arr).to(device)
+        out = torch.full((len(kept), K, 36), float(SENTINEL), dtype=torch.float32, device=device)
+        idx = torch.full((len(kept), K), -7, dtype=torch.int32, device=device)
+        _, cnt, _ = keypoints.topk(t[:, :3].contiguous(), t[:, 3:35].contiguous(), t[:, 35].contiguous(), K, lens=lens_dev, group=group,
+                                   keep=keep, row_map=rm, out=out, idx=idx, n_cap=5000)
+        results.append((out.cpu().numpy(), cnt.cpu().numpy(), idx.cpu().numpy()))
+    for out, cnt, idx in results:
+        assert cnt.tolist() == [min(lens[b], K) for b in kept]
+        for j, b in enumerate(kept):
+            _check_cloud(out[j], int(cnt[j]), idx[j], rec[starts[b]:starts[b + 1]], K, (j, b))
+    # the record-block front end on the same stack
+    kp, c = keypoints.topk_records(torch.from_numpy(rec).to(device), K, lens=lens, group=group, keep=keep)
+    assert np.array_equal(c.cpu().numpy(), results[0][1])
+    for j in range(len(kept)):
+        assert np.array_equal(_bits(kp[j, :int(c[j])].cpu().numpy()), _bits(results[0][0][j, :int(c[j])]))
+
+
 @pytest.mark.parametrize("name", ["network_3dmatch_4k.npz", "network_3dmatch.npz", "network_kitti.npz"])
 def test_topk_on_the_network_fixtures(device, name):
     """First cloud of the committed network outputs (real duplicated scores): indices equal the stable expression, and the score

@@ -11,11 +11,14 @@ K = 0 goes through the C ABI: torch reports a NULL address for a tensor without 
 matrix.
 
 Cost on an MI355X: the 111 cases take 2.4 s run alone and 0.6 s of the full GPU suite's 278 s (only the three large-stride cases
-allocate more than a few MB: 0.2 GB and 0.1 GB for pooling, 4 GiB for the head, freed in the test)."""
+allocate more than a few MB: 0.2 GB and 0.1 GB for pooling, 4 GiB for the head, freed in the test).  The eight cases on stacks of
+129 / 255 clouds (six of test_detect_head, two of test_pack_descriptors_to_255_clouds) came after that count: inside the full suite
+head_kernel<1>-B255-g0 takes 0.07 s, every other one 0.01 s or less."""
 import numpy as np
 import pytest
 import torch
 
+import head_grad_np as hg
 from conftest import bits
 
 pytestmark = pytest.mark.gpu
@@ -431,6 +434,39 @@ def test_pack_descriptors_to(device, C, group, mode):
             assert sum(kept) > 0 and np.any(np.all(want_out[:n] == S, 1))       # some rows really were redirected
 
 
+@pytest.mark.parametrize("lens", [hg.LENS_B255G5, hg.LENS_B255], ids=["many-empty-clouds", "last-cloud-empty"])
+def test_pack_descriptors_to_255_clouds(device, lens):
+    """pack_rows_kernel on a stack of D3F_MAX_BATCH = 255 clouds (sStart[D3F_MAX_BATCH + 1] filled to its last word, d3f_find_elem's
+    steps of 128 / 64 / 32): fragments of 5 clouds, keep 2, a destination per fragment -- three fragments without one (address 0) --
+    and a row map that permutes the rows inside each cloud.  Destinations, guard rows and the redirected rows of `out` as
+    test_pack_descriptors_to holds them."""
+    C, group, keep, B = 32, 5, 2, 255
+    rng = np.random.default_rng(255)
+    assert len(lens) == B
+    n = int(sum(lens))
+    xyz, desc, score = _pack_inputs(rng, n, C)
+    starts = np.concatenate([[0], np.cumsum(lens)])
+    row_map = np.concatenate([starts[b] + rng.permutation(lens[b]) for b in range(B)]).astype(np.int32)
+    nfrag = B // group
+    kept = [int(sum(lens[f * group:f * group + keep])) for f in range(nfrag)]
+    want_out = np.full((n, C + 4), S, np.float32)
+    want_dst = [None if f in (0, 17, nfrag - 1) else np.full((kept[f] + 8, C + 4), S, np.float32) for f in range(nfrag)]
+    _pack_ref(xyz, desc, score, n, want_out, lens, group, keep, want_dst, row_map)
+    out = torch.full((n, C + 4), float(S), device=device)
+    dsts = [None if w is None else torch.full(w.shape, float(S), device=device) for w in want_dst]
+    dst = torch.tensor([0 if d is None else d.data_ptr() for d in dsts], dtype=torch.int64, device=device)
+    rc = _pack_abi(device, _t(xyz, device), _view(desc, device, C + 8, 4), _t(score, device), C, n, out, None,
+                   _t(np.asarray(lens, np.int32), device), group, keep, dst, _t(row_map, device))
+    assert rc == 0
+    assert np.array_equal(bits(out.cpu().numpy()), bits(want_out))
+    for f, (d, w) in enumerate(zip(dsts, want_dst)):
+        if w is not None:
+            assert np.array_equal(bits(d.cpu().numpy()), bits(w)), f
+    redirected = np.all(want_out == S, 1)
+    assert 0 < redirected.sum() < n and redirected.sum() == sum(k for k, w in zip(kept, want_dst) if w is not None)
+    assert max(kept) >= 3 and not np.all(want_out[starts[(nfrag - 1) * group]:] == S)   # the last fragment went to `out`
+
+
 def test_pack_descriptors_to_through_ops(device):
     """ops.pack_descriptors(lens, group, keep, dst, row_map) forwards every operand (C = 32, the shipped width, group 2 keep 1)."""
     from d3feat_amd import ops
@@ -598,6 +634,15 @@ HEAD = [
     ("head_kernel<2>-B2-negative", 48, 20, (45, 70), 0, dict(negative=(0, 1)), {}, True),
     ("head32<true>-B2-scaled-1e3", 32, 30, (70, 45), 0, dict(scale={1: 1e3}), {}, False),
     ("head_kernel<4>-B2-scaled-1e3", 128, 17, (70, 45), 0, dict(scale={0: 1e3}), {}, False),
+    # stacks of up to D3F_MAX_BATCH = 255 clouds (the stacks of head_grad_np.GRID's b255 / b255g5 / b129): head_max_init_kernel's thread
+    # per cloud and its serial prefix and group scans, head_max_kernel's grid (chunks <= ceil(512 / B), B), d3f_find_elem's steps of
+    # 128 / 64 / 32 (from 129 / 65 / 33 clouds on) in the head kernels; groups that divide B and groups that do not; whole empty groups
+    ("head_kernel<1>-B255-g0", 20, 5, hg.LENS_B255, 0, {}, {}, False),
+    ("head32<true>-B255-g5-empty-groups", 32, 5, hg.LENS_B255G5, 5, {}, {}, False),
+    ("head_kernel<1>-B129-g0", 20, 9, hg.LENS_B129, 0, {}, {}, False),
+    ("head32<true>-B255-g4-not-dividing", 32, 5, hg.LENS_B255, 4, {}, {}, False),
+    ("head_kernel<2>-B129-g8-not-dividing-capacity-abi", 64, 9, hg.LENS_B129, 8, {}, dict(cap=5), False),
+    ("head32<true>-B255-g7-not-dividing-empty-groups", 32, 5, hg.LENS_B255G5, 7, {}, {}, False),
 ]
 
 

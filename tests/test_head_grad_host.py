@@ -21,7 +21,8 @@ def test_restatement_against_torch_float64_autograd():
     all-non-positive cloud with two planted exact zeros (pads * C + 2 ties for the maximum 0), the duplicated-column stack, explicit
     pad counts -- and ties of size >= 2 exercised in each of T, W and the cloud maximum."""
     tT = tW = tM = 0
-    for name in ("c1", "c20", "c32", "c33", "c64", "c128", "k0", "k1", "b1", "b3empty", "eqlen", "negzero", "negzero_pads", "dup", "pads"):
+    for name in ("c1", "c20", "c32", "c33", "c64", "c128", "k0", "k1", "b1", "b3empty", "eqlen", "negzero", "negzero_pads", "dup", "pads",
+                 "b255", "b255g5", "b129"):
         c = hg.grid_case(name)
         for ev in hg.EVALS:
             gd, gs = hg.seeds_of(c, ev)
@@ -115,7 +116,11 @@ def test_fixture_against_the_restatement():
         # (at most 3.8e-7 of the largest entry when made; C = 1, both: 1.5e-6 -- the descriptor path's rounding around an exact zero)
         assert (z["err32"][at][real] <= 2e-6 * z["largest"][at][real]).all() and (z["err32_clamp"][at] <= 1e-6 * z["largest_clamp"][at]).all(), name
         if c["C"] > 1:                                     # without the clamp rows an ordinary row's entries are of order 1, not 1e5
-            assert (z["largest"][at] < 50).all() and (z["largest_clamp"][at][[0, 2]] > 1e4).all(), name
+            assert (z["largest"][at] < 50).all(), name
+            if max(c["lens"]) >= 6:                        # (head_case plants a clamp row in every cloud of six rows or more)
+                assert (z["largest_clamp"][at][[0, 2]] > 1e4).all(), name
+            else:
+                assert not z["largest_clamp"][at].any() and not z["err32_clamp"][at].any(), name
         assert (name in hg.NEGATIVE_ROWS) == bool(np.isfinite(z["err32_rel"][at]).all())
         for e, ev in enumerate(hg.EVALS):
             if "gx_%s_%s" % (name, ev) not in z.files:
