@@ -21,6 +21,13 @@
 //    reduction; kpconv_c1_fused_kernel (lanes = neighbours) serves aggregation 'closest'.
 //  * kpconv_agg_scalar: any other Cin, one thread per (query, channel).
 // Queries are visited in the cell-sorted order of the neighbour grid when the caller passes it (q_order).
+//
+// Where the neighbour loop lives: kpconv_agg_vec4, kpconv_fused32_kernel, kpconv_fused_kernel and kpconv_deform.hip's
+// kpconv_deform_agg_vec4 run the same loop, and its pieces exist once, in kp_shared.h: the thread's query (kp_query), the accumulators
+// (KpAcc, KP_ZEROED_ACC), the pair fetched a chunk ahead (kp_pair_index, kp_pair_fetch), the influence routines (kp_influences,
+// kp_influences_t), the LDS image of the influences (kp_store_w / kp_load_w) and phase B (kp_phase_b).  A kernel here holds its LDS
+// layout, phase A's bookkeeping (neighbour count, which lanes hold a pair) and what follows the loop; a change to the loop itself
+// is made in kp_shared.h and reaches all four.
 #include "common.h"
 #include "kp_shared.h"
 #include <cstdlib>
@@ -36,67 +43,13 @@ struct KpParams {
     int aggregation;  // 0 sum, 1 closest
 };
 
-// influences of one neighbour (relative position r) for all kernel points
-__device__ __forceinline__ void kp_influences(const KpParams& P, float rx, float ry, float rz, float* w) {
-    float best = 3.4e38f;
-    int bestp = 0;
-#pragma unroll
-    for (int p = 0; p < KP_MAXP; ++p) {
-        if (p < P.num_kp) {
-            const float dx = rx - P.kp[3 * p], dy = ry - P.kp[3 * p + 1], dz = rz - P.kp[3 * p + 2];
-            const float d2 = dx * dx + dy * dy + dz * dz;
-            float v;
-            // v_sqrt_f32 (1 ulp) and a reciprocal multiply instead of the correctly rounded sqrt / divide sequences:
-            // ~1e-7 relative on a weight in [0,1], four orders below the 1e-4 parity bar, and 3x fewer VALU instructions
-            if (P.influence == 1) v = fmaxf(1.0f - __builtin_amdgcn_sqrtf(d2 + 1e-10f) * P.inv_2extent, 0.0f);
-            else if (P.influence == 0) v = 1.0f;
-            else { const float sig = P.extent * 0.3f; v = expf(-d2 / (2.0f * sig * sig + 1e-9f)); }
-            w[p] = v;
-            if (d2 < best) { best = d2; bestp = p; }
-        } else {
-            w[p] = 0.f;
-        }
-    }
-    if (P.aggregation == 1) {
-#pragma unroll
-        for (int p = 0; p < KP_MAXP; ++p)
-            if (p != bestp) w[p] = 0.f;
-    }
-}
-
-// The configuration every shipped model uses (linear influence, 'sum' aggregation, 15 kernel points -- parameters.txt:
-// KP_influence = linear, convolution_mode = sum, num_kernel_points = 15) as straight-line code: 15 x {3 subtractions,
-// 3 multiply-adds, add, v_sqrt, multiply-subtract, max}, no mode branches, the kernel points read as scalar operands.
-// FAST = false keeps the general function above (other modes / fewer kernel points).
-// These kernels are bound by VALU issue (r03 x14: 597 vector instructions per 8-neighbour chunk and wavefront, 285 of them the
-// aggregation's FMAs), so the influences are computed two kernel points at a time with the packed fp32 forms (v_pk_add / v_pk_mul /
-// v_pk_fma_f32: two IEEE operations per lane and issue slot, the same roundings as the scalar sequence -> bit-identical results).
-typedef float kp_f2 __attribute__((ext_vector_type(2)));
+// the rigid operator's influences (kp_shared.h): every neighbour counts, the kernel points are the kernel-argument arrays
 template <bool FAST>
 __device__ __forceinline__ void kp_influences_t(const KpParams& P, float rx, float ry, float rz, float* w) {
-    if (FAST) {
-        const kp_f2 rx2 = {rx, rx}, ry2 = {ry, ry}, rz2 = {rz, rz};
-        const kp_f2 one = {1.0f, 1.0f}, ninv = {-P.inv_2extent, -P.inv_2extent}, tiny = {1e-10f, 1e-10f};
-#pragma unroll
-        for (int p = 0; p < KP_MAXP - 2; p += 2) {
-            const kp_f2 kx = {P.kx[p], P.kx[p + 1]}, ky = {P.ky[p], P.ky[p + 1]}, kz = {P.kz[p], P.kz[p + 1]};
-            const kp_f2 dx = rx2 - kx, dy = ry2 - ky, dz = rz2 - kz;
-            const kp_f2 d2 = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx)) + tiny;
-            const kp_f2 sq = {__builtin_amdgcn_sqrtf(d2.x), __builtin_amdgcn_sqrtf(d2.y)};
-            const kp_f2 v = __builtin_elementwise_fma(sq, ninv, one);      // fma(-sqrt, 1/(2 extent), 1) as the scalar form
-            w[p] = fmaxf(v.x, 0.0f);
-            w[p + 1] = fmaxf(v.y, 0.0f);
-        }
-        {
-            constexpr int p = KP_MAXP - 2;
-            const float dx = rx - P.kx[p], dy = ry - P.ky[p], dz = rz - P.kz[p];
-            const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-            w[p] = fmaxf(fmaf(-__builtin_amdgcn_sqrtf(d2 + 1e-10f), P.inv_2extent, 1.0f), 0.0f);
-        }
-        w[KP_MAXP - 1] = 0.f;
-    } else {
-        kp_influences(P, rx, ry, rz, w);
-    }
+    kp_influences_t<FAST, false>(P, P.inv_2extent, P.kx, P.ky, P.kz, rx, ry, rz, w);
+}
+__device__ __forceinline__ void kp_influences(const KpParams& P, float rx, float ry, float rz, float* w) {
+    kp_influences_t<false>(P, rx, ry, rz, w);
 }
 static inline KpParams kp_make_params(const float* kp_host, int num_kp, float KP_extent, int influence, int aggregation) {
     KpParams P;
@@ -106,30 +59,8 @@ static inline KpParams kp_make_params(const float* kp_host, int num_kp, float KP
     P.aggregation = aggregation;
     return P;
 }
-static inline bool kp_fast_config(int num_kp, int influence, int aggregation) {
-    return num_kp == KP_MAXP - 1 && influence == 1 && aggregation == 0;
-}
 
-// Phase-A operands of one (query, neighbour) pair, fetched AHEAD of their chunk so that no chunk starts with a chain of dependent
-// round trips (index -> support point): the index of chunk j + 1 is requested at the top of chunk j (it depends on nothing), the
-// point and row flag it names at the top of chunk j's phase B (the index has had phase A to arrive) and land under phase B's
-// gathers and FMAs.  A shadow neighbour (index outside [0, Ns)) reads row 0 and is moved to 1e6 -- the reference's own shadow
-// point (kernels/convolution_ops.py:186-188): every influence of the shipped (linear) configuration is exactly 0, no branch.
-struct KpPair {
-    int id;              // neighbour index, -1: shadow
-    float x, y, z;       // support point
-    bool pos;            // row flag of the support (the neighbour-count test)
-};
-__device__ __forceinline__ KpPair kp_pair_fetch(int id, int Ns, const float* __restrict__ s, const unsigned char* __restrict__ rowpos) {
-    KpPair r;
-    const bool ok = id >= 0 && id < Ns;
-    const unsigned row = ok ? (unsigned)id : 0u;
-    const float* sp = s + 3u * row;
-    r.x = sp[0]; r.y = sp[1]; r.z = sp[2];
-    r.pos = rowpos[row] != 0;
-    r.id = ok ? id : -1;
-    return r;
-}
+// phase A of the rigid kernels: the influences of a fetched pair (kp_pair_fetch) -> does it count as a neighbour
 template <bool FAST>
 __device__ __forceinline__ bool kp_pair_influences(const KpParams& P, const KpPair& pr, float qx, float qy, float qz, float* w) {
     const bool ok = pr.id >= 0;
@@ -214,62 +145,30 @@ kpconv_agg_vec4(const float* __restrict__ q, int Nq, const float* __restrict__ s
     __shared__ int lcnt[TQ];
     const int tid = threadIdx.x;
     const int ql = tid / LQ, cl = tid % LQ;  // query-in-block, channel group
-    // q_order: a spatially coherent visiting order (cell-sorted): the TQ queries of a workgroup then share most of their
-    // neighbours, whose feature rows are fetched once into L1 / L2 instead of TQ times from all over the cloud
-    const int qslot = tile * TQ + ql;
-    const int qg = (q_order && qslot < Nq) ? q_order[qslot] : qslot;
+    const KpQuery Q = kp_query(tile * TQ + ql, Nq, q_order, q, idx, ld_idx);
     const int Cin = LQ * 4;
     if (tid < TQ) lcnt[tid] = 0;
-    float acc[KP_MAXP - 1][4];
-#pragma unroll
-    for (int p = 0; p < KP_MAXP - 1; ++p) acc[p][0] = acc[p][1] = acc[p][2] = acc[p][3] = 0.f;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    if (qg < Nq) { qx = q[3 * (size_t)qg]; qy = q[3 * (size_t)qg + 1]; qz = q[3 * (size_t)qg + 2]; }
-    const int* idrow = idx + (qg < Nq ? __umul24((unsigned)qg, (unsigned)ld_idx) : 0u);   // (rows, leading dimensions < 2^24: kp_fits_u24)
-    KpPair pr = kp_pair_fetch(kp_pair_index(idrow, qg < Nq, cl, K, Ns), Ns, s, rowpos);     // chunk 0's pair
+    KP_ZEROED_ACC(acc);
+    KpPair pr = kp_pair_fetch<true>(kp_pair_index(Q.idrow, Q.live, cl, K, Ns), Ns, s, rowpos);   // chunk 0's pair
     __syncthreads();
     for (int k0 = 0; k0 < K; k0 += KC) {
-        const int id_next = kp_pair_index(idrow, qg < Nq, k0 + KC + cl, K, Ns);              // in flight during phase A
+        const int id_next = kp_pair_index(Q.idrow, Q.live, k0 + KC + cl, K, Ns);             // in flight during phase A
         // ---- phase A: thread = (query ql, neighbour k0 + cl) ----
         {
             float w[KP_MAXP];
-            const bool positive = kp_pair_influences<FAST>(P, pr, qx, qy, qz, w);
+            const bool positive = kp_pair_influences<FAST>(P, pr, Q.x, Q.y, Q.z, w);
             kp_count_positive<LQ>(positive, ql, cl, lcnt);
             lidx[ql * KC + cl] = pr.id;
             kp_store_w(&lw[ql * WS + cl * 16], cl, w);
         }
         __syncthreads();
-        pr = kp_pair_fetch(id_next, Ns, s, rowpos);                                          // in flight during phase B
-        // ---- phase B: thread = (query ql, channels 4*cl .. 4*cl+3) ----
-        const int kend = min(KC, K - k0);
-        // feature rows are requested in groups of up to eight before any is consumed: the gathers are independent, so their
-        // latencies overlap instead of adding up (the kernel is bound by these round trips, not by the FMAs)
-        constexpr int PF = KC < 8 ? KC : 8;
-        for (int kg = 0; kg < kend; kg += PF) {
-            float4 fv[PF];
-            int ids[PF];
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                ids[u] = (kg + u < kend) ? lidx[ql * KC + kg + u] : -1;
-                fv[u] = kp_gather4(fbuf, ids[u], ldf, 4 * cl);
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                if (!__any(ids[u] >= 0)) continue;   // (wavefront-uniform) shadow slot for every query of the wavefront: nothing to add
-                float w[16];
-                kp_load_w(&lw[ql * WS + (kg + u) * 16], kg + u, w);
-#pragma unroll
-                for (int p = 0; p < KP_MAXP - 1; ++p) {
-                    acc[p][0] = fmaf(w[p], fv[u].x, acc[p][0]);
-                    acc[p][1] = fmaf(w[p], fv[u].y, acc[p][1]);
-                    acc[p][2] = fmaf(w[p], fv[u].z, acc[p][2]);
-                    acc[p][3] = fmaf(w[p], fv[u].w, acc[p][3]);
-                }
-            }
-        }
+        pr = kp_pair_fetch<true>(id_next, Ns, s, rowpos);                                    // in flight during phase B
+        // ---- phase B: thread = (query ql, channels 4*cl .. 4*cl+3), up to eight feature rows in flight ----
+        kp_phase_b<(KC < 8 ? KC : 8), 0>(fbuf, ldf, &lidx[ql * KC], &lw[ql * WS], min(KC, K - k0), cl, acc);
         __syncthreads();
     }
-    if (qg < Nq) {
+    if (Q.live) {
+        const int qg = Q.g;
         float* o = wf + (size_t)qg * P.num_kp * Cin + 4 * cl;
 #pragma unroll
         for (int p = 0; p < KP_MAXP - 1; ++p)
@@ -777,55 +676,25 @@ kpconv_fused32_kernel(const float* __restrict__ q, int Nq, const float* __restri
     int* lq = lcnt + KF_TQ;                                 // [32] global query index of each tile row
     const int tid = threadIdx.x;
     const int ql = tid / KF_LQ, cl = tid % KF_LQ;
-    const int qslot = tile * KF_TQ + ql;
-    const int qg = (q_order && qslot < Nq) ? q_order[qslot] : qslot;
+    const KpQuery Q = kp_query(tile * KF_TQ + ql, Nq, q_order, q, idx, ld_idx);
     if (tid < KF_TQ) lcnt[tid] = 0;
-    if (cl == 0) lq[ql] = qslot < Nq ? qg : -1;
-    float acc[KP_MAXP - 1][4];
-#pragma unroll
-    for (int p = 0; p < KP_MAXP - 1; ++p) acc[p][0] = acc[p][1] = acc[p][2] = acc[p][3] = 0.f;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    if (qslot < Nq) { qx = q[3 * (size_t)qg]; qy = q[3 * (size_t)qg + 1]; qz = q[3 * (size_t)qg + 2]; }
-    const int* idrow = idx + (qslot < Nq ? __umul24((unsigned)qg, (unsigned)ld_idx) : 0u);   // (rows, leading dimensions < 2^24)
-    KpPair pr = kp_pair_fetch(kp_pair_index(idrow, qslot < Nq, cl, K, Ns), Ns, s, rowpos);  // chunk 0's pair
+    if (cl == 0) lq[ql] = Q.live ? Q.g : -1;
+    KP_ZEROED_ACC(acc);
+    KpPair pr = kp_pair_fetch<true>(kp_pair_index(Q.idrow, Q.live, cl, K, Ns), Ns, s, rowpos);  // chunk 0's pair
     __syncthreads();
     for (int k0 = 0; k0 < K; k0 += KF_LQ) {
-        const int id_next = kp_pair_index(idrow, qslot < Nq, k0 + KF_LQ + cl, K, Ns);       // in flight during phase A
+        const int id_next = kp_pair_index(Q.idrow, Q.live, k0 + KF_LQ + cl, K, Ns);         // in flight during phase A
         {   // ---- phase A: thread = (query ql, neighbour k0 + cl) ----
             float w[KP_MAXP];
-            const bool positive = kp_pair_influences<FAST>(P, pr, qx, qy, qz, w);
+            const bool positive = kp_pair_influences<FAST>(P, pr, Q.x, Q.y, Q.z, w);
             kp_count_positive<KF_LQ>(positive, ql, cl, lcnt);
             lidx[ql * KF_LQ + cl] = pr.id;
             kp_store_w(&lw[ql * KF_WS + cl * 16], cl, w);
         }
         __syncthreads();
-        pr = kp_pair_fetch(id_next, Ns, s, rowpos);                                         // in flight during phase B
-        // ---- phase B: thread = (query ql, channels 4*cl .. 4*cl+3) ----
-        // all eight feature rows of the chunk are requested before any is consumed: the gathers are independent, so their
-        // latencies overlap instead of adding up (the kernel is bound by these round trips, not by the FMAs)
-#pragma unroll
-        for (int k1 = 0; k1 < KF_LQ; k1 += PF) {
-            float4 fv[PF];
-            int ids[PF];
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                ids[u] = lidx[ql * KF_LQ + k1 + u];
-                fv[u] = kp_gather4(fbuf, ids[u], ldf, 4 * cl);
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                if (!__any(ids[u] >= 0)) continue;   // (wavefront-uniform) shadow slot for every query of the wavefront: nothing to add
-                float w[16];
-                kp_load_w(&lw[ql * KF_WS + (k1 + u) * 16], k1 + u, w);
-#pragma unroll
-                for (int p = 0; p < KP_MAXP - 1; ++p) {
-                    acc[p][0] = fmaf(w[p], fv[u].x, acc[p][0]);
-                    acc[p][1] = fmaf(w[p], fv[u].y, acc[p][1]);
-                    acc[p][2] = fmaf(w[p], fv[u].z, acc[p][2]);
-                    acc[p][3] = fmaf(w[p], fv[u].w, acc[p][3]);
-                }
-            }
-        }
+        pr = kp_pair_fetch<true>(id_next, Ns, s, rowpos);                                   // in flight during phase B
+        // ---- phase B: thread = (query ql, channels 4*cl .. 4*cl+3); the whole chunk of eight slots, unmasked and unrolled ----
+        kp_phase_b<PF, KF_LQ>(fbuf, ldf, &lidx[ql * KF_LQ], &lw[ql * KF_WS], KF_LQ, cl, acc);
         __syncthreads();
     }
     auto write_tile = [&](float* wft, int p0, int np) {
@@ -954,24 +823,18 @@ kpconv_fused_kernel(const float* __restrict__ q, int Nq, const float* __restrict
     float* wft = region;
     const int tid = threadIdx.x;
     const int ql = tid / LQ, cl = tid % LQ;
-    const int qslot = tile * KG_TQ + ql;
-    const int qg = (q_order && qslot < Nq) ? q_order[qslot] : qslot;
+    const KpQuery Q = kp_query(tile * KG_TQ + ql, Nq, q_order, q, idx, ld_idx);
     if (tid < KG_TQ) lcnt[tid] = 0;
-    if (cl == 0) lq[ql] = qslot < Nq ? qg : -1;
-    float acc[KP_MAXP - 1][4];
-#pragma unroll
-    for (int p = 0; p < KP_MAXP - 1; ++p) acc[p][0] = acc[p][1] = acc[p][2] = acc[p][3] = 0.f;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    if (qslot < Nq) { qx = q[3 * (size_t)qg]; qy = q[3 * (size_t)qg + 1]; qz = q[3 * (size_t)qg + 2]; }
-    const int* idrow = idx + (qslot < Nq ? __umul24((unsigned)qg, (unsigned)ld_idx) : 0u);   // (rows, leading dimensions < 2^24)
-    const bool pair_lane = cl < KC && qslot < Nq;
-    KpPair pr = kp_pair_fetch(kp_pair_index(idrow, pair_lane, cl, K, Ns), Ns, s, rowpos);  // chunk 0's pair
+    if (cl == 0) lq[ql] = Q.live ? Q.g : -1;
+    KP_ZEROED_ACC(acc);
+    const bool pair_lane = cl < KC && Q.live;
+    KpPair pr = kp_pair_fetch<true>(kp_pair_index(Q.idrow, pair_lane, cl, K, Ns), Ns, s, rowpos);  // chunk 0's pair
     __syncthreads();
     for (int k0 = 0; k0 < K; k0 += KC) {
-        const int id_next = kp_pair_index(idrow, pair_lane, k0 + KC + cl, K, Ns);           // in flight during phase A
+        const int id_next = kp_pair_index(Q.idrow, pair_lane, k0 + KC + cl, K, Ns);         // in flight during phase A
         {   // ---- phase A: thread = (query ql, neighbour k0 + cl) ----
             float w[KP_MAXP];
-            const bool positive = kp_pair_influences<true>(P, pr, qx, qy, qz, w);
+            const bool positive = kp_pair_influences<true>(P, pr, Q.x, Q.y, Q.z, w);
             kp_count_positive<LQ>(positive, ql, cl, lcnt);
             if (cl < KC) {
                 lidx[ql * KC + cl] = pr.id;
@@ -979,31 +842,9 @@ kpconv_fused_kernel(const float* __restrict__ q, int Nq, const float* __restrict
             }
         }
         __syncthreads();
-        pr = kp_pair_fetch(id_next, Ns, s, rowpos);                                         // in flight during phase B
-        // ---- phase B: thread = (query ql, channels 4*cl .. 4*cl+3); PF feature rows requested before any is consumed ----
-        const int kend = min(KC, K - k0);
-        for (int kg = 0; kg < kend; kg += PF) {
-            float4 fv[PF];
-            int ids[PF];
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                ids[u] = (kg + u < kend) ? lidx[ql * KC + kg + u] : -1;
-                fv[u] = kp_gather4(fbuf, ids[u], ldf, 4 * cl);
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                if (!__any(ids[u] >= 0)) continue;   // (wavefront-uniform) shadow slot for every query of the wavefront: nothing to add
-                float w[16];
-                kp_load_w(&lw[ql * WS + (kg + u) * 16], kg + u, w);
-#pragma unroll
-                for (int p = 0; p < KP_MAXP - 1; ++p) {
-                    acc[p][0] = fmaf(w[p], fv[u].x, acc[p][0]);
-                    acc[p][1] = fmaf(w[p], fv[u].y, acc[p][1]);
-                    acc[p][2] = fmaf(w[p], fv[u].z, acc[p][2]);
-                    acc[p][3] = fmaf(w[p], fv[u].w, acc[p][3]);
-                }
-            }
-        }
+        pr = kp_pair_fetch<true>(id_next, Ns, s, rowpos);                                   // in flight during phase B
+        // ---- phase B: thread = (query ql, channels 4*cl .. 4*cl+3), PF feature rows in flight ----
+        kp_phase_b<PF, 0>(fbuf, ldf, &lidx[ql * KC], &lw[ql * WS], min(KC, K - k0), cl, acc);
         __syncthreads();
     }
     // ---- contraction: out[16 x Cout] = wf[16 x 15*Cin] @ K_values, the wf tile through LDS in passes of HP kernel points ----
@@ -1353,26 +1194,13 @@ extern "C" int d3f_kpconv_aggregate(const float* q, int Nq, const float* s, int 
         D3F_LAUNCH_CHECK();
         return D3F_OK;
     }
-#define D3F_AGG(LQ_)                                                                                                        \
-    do {                                                                                                                    \
-        if (fast) kpconv_agg_vec4<LQ_, true><<<d3f_cdiv(Nq, 256 / LQ_), 256, 0, stream>>>(q, Nq, s, Ns, idx, ld_idx, K, f, ldf, \
-                                                                                          rowpos, P, wf, inv_cnt, Nq_dev, Ns_dev, q_order); \
-        else kpconv_agg_vec4<LQ_, false><<<d3f_cdiv(Nq, 256 / LQ_), 256, 0, stream>>>(q, Nq, s, Ns, idx, ld_idx, K, f, ldf,   \
-                                                                                       rowpos, P, wf, inv_cnt, Nq_dev, Ns_dev, q_order); \
-    } while (0)
-    if (vec && Cin == 4) D3F_AGG(1);
-    else if (vec && Cin == 8) D3F_AGG(2);
-    else if (vec && Cin == 16) D3F_AGG(4);
-    else if (vec && Cin == 32) D3F_AGG(8);
-    else if (vec && Cin == 64) D3F_AGG(16);
-    else if (vec && Cin == 128) D3F_AGG(32);
-    else if (vec && Cin == 256) D3F_AGG(64);
-    else if (vec && Cin == 512) D3F_AGG(128);
-    else if (vec && Cin == 1024) D3F_AGG(256);
-    else
+    bool on_ladder = vec;
+    if (vec)       // TQ = 256 / LQ queries per 256-thread workgroup
+        KP_LADDER(on_ladder, kpconv_agg_vec4, 256, Cin, fast, Nq, stream, q, Nq, s, Ns, idx, ld_idx, K, f, ldf, rowpos, P, wf, inv_cnt,
+                  Nq_dev, Ns_dev, q_order);
+    if (!on_ladder)
         kpconv_agg_scalar<<<d3f_cdiv((long long)Nq * Cin, 256), 256, 0, stream>>>(q, Nq, s, Ns, idx, ld_idx, K, f, ldf,
                                                                                    Cin, rowpos, P, wf, inv_cnt, Nq_dev, Ns_dev);
-#undef D3F_AGG
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }

@@ -22,9 +22,13 @@
 //    phases, chunks of KC = LQ neighbours, buffer-resource gathers, q_order and Nq_dev / Ns_dev.  LDS per query (KPD_DS = 68
 //    floats): x'[16] y'[16] z'[16] mod[16] + 4 floats that de-phase the b128 broadcasts of adjacent queries (a 16-lane group of
 //    ds_read_b128 that holds 16 different queries then touches 16 different 16-byte slots of the 256-byte bank row).
-//    FAST: linear / sum / 15 points as straight-line packed fp32 code (kp_influences_t's sequence with 1 / KP_extent).
+//    FAST: linear / sum / 15 points as straight-line packed fp32 code.
 //  * kpconv_deform_agg_scalar: any other Cin, alignment or address range; one thread per (query, channel), the deformed points in
 //    registers.
+// The neighbour loop is the rigid operator's, and so is its code (kp_shared.h): kp_query, kp_pair_fetch<false> (no row flag is loaded),
+// kp_influences / kp_influences_t with RANGE = true, inv_scale = 1 / KP_extent and the query's own points, kp_phase_b, and the
+// Cin -> LQ launch ladder (KP_LADDER).  This file holds what is the deformable operator's own: the parameters, the staging of the
+// deformed points, phase A's range filter and the modulations of the epilogue.
 #include "common.h"
 #include "kp_shared.h"
 
@@ -48,9 +52,6 @@ static inline KpdParams kpd_make_params(const float* kp_host, int num_kp, float 
     P.num_kp = num_kp; P.extent = KP_extent; P.inv_extent = 1.0f / KP_extent; P.e2 = (float)((double)KP_extent * (double)KP_extent);
     P.influence = influence; P.aggregation = aggregation; P.off_scale = off_scale; P.modulated = modulated;
     return P;
-}
-static inline bool kpd_fast_config(int num_kp, int influence, int aggregation) {
-    return num_kp == KP_MAXP - 1 && influence == 1 && aggregation == 0;
 }
 
 // deformed kernel point p of one query and its modulation: a product and an add per coordinate, as the reference's
@@ -81,84 +82,6 @@ __device__ __forceinline__ void kpd_load16(const float* __restrict__ src, float*
     v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w; v[12] = d.x; v[13] = d.y; v[14] = d.z; v[15] = d.w;
 }
 
-// influences of one neighbour (relative position r) for the deformed points kx / ky / kz -> is it in range of any of them
-__device__ __forceinline__ bool kpd_influences(const KpdParams& P, const float* kx, const float* ky, const float* kz, float rx, float ry,
-                                               float rz, float* w) {
-    float best = 3.4e38f;
-    int bestp = 0;
-    bool in = false;
-#pragma unroll
-    for (int p = 0; p < KP_MAXP; ++p) {
-        if (p < P.num_kp) {
-            const float dx = rx - kx[p], dy = ry - ky[p], dz = rz - kz[p];
-            const float d2 = dx * dx + dy * dy + dz * dz;
-            const bool near = d2 < P.e2;
-            in = in || near;
-            float v;
-            if (P.influence == 1) v = fmaxf(1.0f - __builtin_amdgcn_sqrtf(d2 + 1e-10f) * P.inv_extent, 0.0f);
-            else if (P.influence == 0) v = near ? 1.0f : 0.0f;
-            else { const float sig = P.extent * 0.3f; v = expf(-d2 / (2.0f * sig * sig + 1e-9f)); }
-            w[p] = v;
-            if (d2 < best) { best = d2; bestp = p; }
-        } else {
-            w[p] = 0.f;
-        }
-    }
-    if (P.aggregation == 1) {
-#pragma unroll
-        for (int p = 0; p < KP_MAXP; ++p)
-            if (p != bestp) w[p] = 0.f;
-    }
-    return in;
-}
-typedef float kpd_f2 __attribute__((ext_vector_type(2)));
-template <bool FAST>
-__device__ __forceinline__ bool kpd_influences_t(const KpdParams& P, const float* kx, const float* ky, const float* kz, float rx, float ry,
-                                                 float rz, float* w) {
-    if (FAST) {
-        const kpd_f2 rx2 = {rx, rx}, ry2 = {ry, ry}, rz2 = {rz, rz};
-        const kpd_f2 one = {1.0f, 1.0f}, ninv = {-P.inv_extent, -P.inv_extent}, tiny = {1e-10f, 1e-10f};
-        float dmin = 3.4e38f;
-#pragma unroll
-        for (int p = 0; p < KP_MAXP - 2; p += 2) {
-            const kpd_f2 kx2 = {kx[p], kx[p + 1]}, ky2 = {ky[p], ky[p + 1]}, kz2 = {kz[p], kz[p + 1]};
-            const kpd_f2 dx = rx2 - kx2, dy = ry2 - ky2, dz = rz2 - kz2;
-            const kpd_f2 d2 = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
-            dmin = fminf(dmin, fminf(d2.x, d2.y));
-            const kpd_f2 d2t = d2 + tiny;
-            const kpd_f2 sq = {__builtin_amdgcn_sqrtf(d2t.x), __builtin_amdgcn_sqrtf(d2t.y)};
-            const kpd_f2 v = __builtin_elementwise_fma(sq, ninv, one);
-            w[p] = fmaxf(v.x, 0.0f);
-            w[p + 1] = fmaxf(v.y, 0.0f);
-        }
-        {
-            constexpr int p = KP_MAXP - 2;
-            const float dx = rx - kx[p], dy = ry - ky[p], dz = rz - kz[p];
-            const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-            dmin = fminf(dmin, d2);
-            w[p] = fmaxf(fmaf(-__builtin_amdgcn_sqrtf(d2 + 1e-10f), P.inv_extent, 1.0f), 0.0f);
-        }
-        w[KP_MAXP - 1] = 0.f;
-        return dmin < P.e2;
-    } else {
-        return kpd_influences(P, kx, ky, kz, rx, ry, rz, w);
-    }
-}
-
-// support point of one (query, neighbour) pair, fetched a chunk ahead as kpconv.hip's KpPair (no row flag: there is no count)
-struct KpdPair {
-    int id;              // neighbour index, -1: shadow
-    float x, y, z;
-};
-__device__ __forceinline__ KpdPair kpd_pair_fetch(int id, int Ns, const float* __restrict__ s) {
-    KpdPair r;
-    const bool ok = id >= 0 && id < Ns;
-    const float* sp = s + 3u * (ok ? (unsigned)id : 0u);
-    r.x = sp[0]; r.y = sp[1]; r.z = sp[2];
-    r.id = ok ? id : -1;
-    return r;
-}
-
 template <int LQ, bool FAST>  // lanes per query = Cin / 4; FAST: linear / sum / 15 kernel points
 __global__ void __launch_bounds__(256)
 kpconv_deform_agg_vec4(const float* __restrict__ q, int Nq, const float* __restrict__ s, int Ns, const int* __restrict__ idx,
@@ -179,33 +102,28 @@ kpconv_deform_agg_vec4(const float* __restrict__ q, int Nq, const float* __restr
     __shared__ int lidx[TQ * KC];
     const int tid = threadIdx.x;
     const int ql = tid / LQ, cl = tid % LQ;  // query-in-block, channel group
-    const int qslot = tile * TQ + ql;
-    const int qg = (q_order && qslot < Nq) ? q_order[qslot] : qslot;
+    const KpQuery Q = kp_query(tile * TQ + ql, Nq, q_order, q, idx, ld_idx);
     const int Cin = LQ * 4;
     // ---- the workgroup's deformed kernel points: thread t < TQ stages query slot t ----
     for (int t = tid; t < TQ; t += NT) {
         const int ts = tile * TQ + t;
-        const int tg = (q_order && ts < Nq) ? q_order[ts] : ts;
-        kpd_stage_points(P, tg < Nq ? off + (size_t)tg * ld_off : nullptr, mod ? mod + (size_t)(tg < Nq ? tg : 0) * ld_mod : nullptr,
+        const int tg = kp_query_index(q_order, ts, Nq);
+        kpd_stage_points(P, ts < Nq ? off + (size_t)tg * ld_off : nullptr, mod ? mod + (size_t)(ts < Nq ? tg : 0) * ld_mod : nullptr,
                          &ldp[t * KPD_DS]);
     }
-    float acc[KP_MAXP - 1][4];
-#pragma unroll
-    for (int p = 0; p < KP_MAXP - 1; ++p) acc[p][0] = acc[p][1] = acc[p][2] = acc[p][3] = 0.f;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    if (qg < Nq) { qx = q[3 * (size_t)qg]; qy = q[3 * (size_t)qg + 1]; qz = q[3 * (size_t)qg + 2]; }
-    const int* idrow = idx + (qg < Nq ? __umul24((unsigned)qg, (unsigned)ld_idx) : 0u);   // (rows, leading dimensions < 2^24: kp_fits_u24)
-    KpdPair pr = kpd_pair_fetch(kp_pair_index(idrow, qg < Nq, cl, K, Ns), Ns, s);          // chunk 0's pair
+    KP_ZEROED_ACC(acc);
+    KpPair pr = kp_pair_fetch<false>(kp_pair_index(Q.idrow, Q.live, cl, K, Ns), Ns, s, nullptr);   // chunk 0's pair (no row flag: no count)
     __syncthreads();
     const float* dp = &ldp[ql * KPD_DS];
     for (int k0 = 0; k0 < K; k0 += KC) {
-        const int id_next = kp_pair_index(idrow, qg < Nq, k0 + KC + cl, K, Ns);             // in flight during phase A
+        const int id_next = kp_pair_index(Q.idrow, Q.live, k0 + KC + cl, K, Ns);            // in flight during phase A
         // ---- phase A: thread = (query ql, neighbour k0 + cl) ----
         {
             float kx[KP_MAXP], ky[KP_MAXP], kz[KP_MAXP], w[KP_MAXP];
             kpd_load16(dp, kx); kpd_load16(dp + KP_MAXP, ky); kpd_load16(dp + 2 * KP_MAXP, kz);
             const bool ok = pr.id >= 0;
-            const bool in = kpd_influences_t<FAST>(P, kx, ky, kz, ok ? pr.x - qx : 1e6f, ok ? pr.y - qy : 1e6f, ok ? pr.z - qz : 1e6f, w);
+            const bool in = kp_influences_t<FAST, true>(P, P.inv_extent, kx, ky, kz, ok ? pr.x - Q.x : 1e6f, ok ? pr.y - Q.y : 1e6f,
+                                                        ok ? pr.z - Q.z : 1e6f, w);
             const bool keep = ok && in;
             if (!FAST) {        // gaussian is not 0 out of range and 'closest' picks a point anyway: zero a dropped pair's weights
 #pragma unroll                  // (the FAST weights are finite and meet the zeros the gather returns for id = -1)
@@ -215,38 +133,15 @@ kpconv_deform_agg_vec4(const float* __restrict__ q, int Nq, const float* __restr
             kp_store_w(&lw[ql * WS + cl * 16], cl, w);
         }
         __syncthreads();
-        pr = kpd_pair_fetch(id_next, Ns, s);                                                // in flight during phase B
-        // ---- phase B: thread = (query ql, channels 4*cl .. 4*cl+3) ----
-        const int kend = min(KC, K - k0);
-        constexpr int PF = KC < 8 ? KC : 8;
-        for (int kg = 0; kg < kend; kg += PF) {
-            float4 fv[PF];
-            int ids[PF];
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                ids[u] = (kg + u < kend) ? lidx[ql * KC + kg + u] : -1;
-                fv[u] = kp_gather4(fbuf, ids[u], ldf, 4 * cl);
-            }
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                if (!__any(ids[u] >= 0)) continue;   // (wavefront-uniform) nothing to add for any query of the wavefront
-                float w[16];
-                kp_load_w(&lw[ql * WS + (kg + u) * 16], kg + u, w);
-#pragma unroll
-                for (int p = 0; p < KP_MAXP - 1; ++p) {
-                    acc[p][0] = fmaf(w[p], fv[u].x, acc[p][0]);
-                    acc[p][1] = fmaf(w[p], fv[u].y, acc[p][1]);
-                    acc[p][2] = fmaf(w[p], fv[u].z, acc[p][2]);
-                    acc[p][3] = fmaf(w[p], fv[u].w, acc[p][3]);
-                }
-            }
-        }
+        pr = kp_pair_fetch<false>(id_next, Ns, s, nullptr);                                 // in flight during phase B
+        // ---- phase B: thread = (query ql, channels 4*cl .. 4*cl+3), up to eight feature rows in flight ----
+        kp_phase_b<(KC < 8 ? KC : 8), 0>(fbuf, ldf, &lidx[ql * KC], &lw[ql * WS], min(KC, K - k0), cl, acc);
         __syncthreads();
     }
-    if (qg < Nq) {
+    if (Q.live) {
         float m[KP_MAXP];
         kpd_load16(dp + 3 * KP_MAXP, m);
-        float* o = wf + (size_t)qg * P.num_kp * Cin + 4 * cl;
+        float* o = wf + (size_t)Q.g * P.num_kp * Cin + 4 * cl;
 #pragma unroll
         for (int p = 0; p < KP_MAXP - 1; ++p)
             if (p < P.num_kp) {
@@ -280,7 +175,7 @@ kpconv_deform_agg_scalar(const float* __restrict__ q, int Nq, const float* __res
         const int id = idx[(size_t)qg * ld_idx + k];
         if (id < 0 || id >= Ns) continue;
         float w[KP_MAXP];
-        if (!kpd_influences(P, kx, ky, kz, s[3 * (size_t)id] - qx, s[3 * (size_t)id + 1] - qy, s[3 * (size_t)id + 2] - qz, w)) continue;
+        if (!kp_influences<true>(P, P.inv_extent, kx, ky, kz, s[3 * (size_t)id] - qx, s[3 * (size_t)id + 1] - qy, s[3 * (size_t)id + 2] - qz, w)) continue;
         const float fv = f[(size_t)id * ldf + c];
 #pragma unroll
         for (int p = 0; p < KP_MAXP; ++p) acc[p] = fmaf(w[p], fv, acc[p]);
@@ -314,28 +209,14 @@ extern "C" int d3f_kpconv_deform_aggregate(const float* q, int Nq, const float* 
     // (the vector kernels address rows with 24-bit multiplies; larger problems take the one-thread-per-output kernel)
     const bool vec = (Cin % 4 == 0) && (ldf % 4 == 0) && (((uintptr_t)f & 15) == 0) && (((uintptr_t)wf & 15) == 0) &&
                      kp_fits_u24(Nq, Ns, ld_idx, ldf);
-    const bool fast = kpd_fast_config(num_kp, influence, aggregation);
-#define D3F_DAGG(LQ_)                                                                                                              \
-    do {                                                                                                                           \
-        constexpr int TQ_ = (256 / LQ_) < 64 ? (256 / LQ_) : 64;                                                                   \
-        if (fast) kpconv_deform_agg_vec4<LQ_, true><<<d3f_cdiv(Nq, TQ_), TQ_ * LQ_, 0, stream>>>(q, Nq, s, Ns, idx, ld_idx, K, f, ldf, \
-                                                                                                 offsets, ld_off, modulations, ld_mod, P, wf, Nq_dev, Ns_dev, q_order); \
-        else kpconv_deform_agg_vec4<LQ_, false><<<d3f_cdiv(Nq, TQ_), TQ_ * LQ_, 0, stream>>>(q, Nq, s, Ns, idx, ld_idx, K, f, ldf,    \
-                                                                                              offsets, ld_off, modulations, ld_mod, P, wf, Nq_dev, Ns_dev, q_order); \
-    } while (0)
-    if (vec && Cin == 4) D3F_DAGG(1);
-    else if (vec && Cin == 8) D3F_DAGG(2);
-    else if (vec && Cin == 16) D3F_DAGG(4);
-    else if (vec && Cin == 32) D3F_DAGG(8);
-    else if (vec && Cin == 64) D3F_DAGG(16);
-    else if (vec && Cin == 128) D3F_DAGG(32);
-    else if (vec && Cin == 256) D3F_DAGG(64);
-    else if (vec && Cin == 512) D3F_DAGG(128);
-    else if (vec && Cin == 1024) D3F_DAGG(256);
-    else
+    const bool fast = kp_fast_config(num_kp, influence, aggregation);
+    bool on_ladder = vec;
+    if (vec)       // TQ = min(256 / LQ, 64) queries per workgroup of TQ * LQ threads
+        KP_LADDER(on_ladder, kpconv_deform_agg_vec4, 64, Cin, fast, Nq, stream, q, Nq, s, Ns, idx, ld_idx, K, f, ldf, offsets, ld_off,
+                  modulations, ld_mod, P, wf, Nq_dev, Ns_dev, q_order);
+    if (!on_ladder)
         kpconv_deform_agg_scalar<<<d3f_cdiv((long long)Nq * Cin, 256), 256, 0, stream>>>(q, Nq, s, Ns, idx, ld_idx, K, f, ldf, Cin,
                                                                                           offsets, ld_off, modulations, ld_mod, P, wf, Nq_dev, Ns_dev);
-#undef D3F_DAGG
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }

@@ -54,7 +54,7 @@ pytestmark = pytest.mark.gpu
 
 S = -124.0                        # sentinel of pre-filled outputs
 OK, ERR_ARG = 0, -3               # D3F_OK, D3F_ERR_ARG (include/d3feat_amd.h)
-FAST = ("linear", "sum", 15)      # kpd_fast_config: num_kp == 15 && influence == linear && aggregation == sum
+FAST = ("linear", "sum", 15)      # kp_fast_config: num_kp == 15 && influence == linear && aggregation == sum
 NONFAST = (("gaussian", "sum", 13), ("linear", "closest", 15), ("constant", "sum", 4), ("gaussian", "closest", 15),
            ("constant", "closest", 13), ("linear", "sum", 4))
 _INF = {"constant": 0, "linear": 1, "gaussian": 2}
