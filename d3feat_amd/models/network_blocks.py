@@ -61,8 +61,7 @@ def _bn(channels, use_batch_norm=True):
     vs = _vs()
     if use_batch_norm:
         return vs.folded_bn(vs.batch_norm_variables(channels))
-    name = vs.get('offset', (channels,), lambda: np.zeros(channels))
-    return None, vs.tensor(name)
+    return None, vs.tensor(vs.offset_variable(channels))
 
 
 def batch_norm(x, use_batch_norm=True, momentum=0.99, training=False):
@@ -98,12 +97,15 @@ def _kernel_points(config, extent):
 
 
 def KPConv(query_points, support_points, neighbors_indices, features, K_values, radius, config, epilogue=None):
-    """:86-103: extent = KP_extent * radius / density_parameter, then kernels.convolution_ops.KPConv."""
+    """:86-103: extent = KP_extent * radius / density_parameter, then kernels.convolution_ops.KPConv.  epilogue: the dict, or a
+    callable that makes it -- called after `kernel_points` exists, the reference's creation order (weights, kernel_points, then what
+    batch_norm creates)."""
     extent = config.KP_extent * radius / config.density_parameter
+    K_points = _kernel_points(config, extent)
     return conv_ops.KPConv(query_points, support_points, neighbors_indices, features, K_values,
                            fixed=config.fixed_kernel_points, KP_extent=extent, KP_influence=config.KP_influence,
-                           aggregation_mode=config.convolution_mode, K_points=_kernel_points(config, extent),
-                           epilogue=epilogue)
+                           aggregation_mode=config.convolution_mode, K_points=K_points,
+                           epilogue=epilogue() if callable(epilogue) else epilogue)
 
 
 def KPConv_deformable(query_points, support_points, neighbors_indices, features, K_values, radius, config, epilogue=None):
@@ -116,6 +118,7 @@ def KPConv_deformable(query_points, support_points, neighbors_indices, features,
     offset_dim = (4 if config.modulated else 3) * k
     w0 = vs.tensor(vs.get('offset_conv_weights', (k, cin, offset_dim), lambda: np.zeros((k, cin, offset_dim))))
     b0 = vs.tensor(vs.get('offset_conv_bias', (offset_dim,), lambda: np.zeros(offset_dim)))
+    epilogue = epilogue() if callable(epilogue) else epilogue
     return conv_ops.KPConv_deformable(query_points, support_points, neighbors_indices, features, K_values,
                                       fixed=config.fixed_kernel_points, KP_extent=extent, KP_influence=config.KP_influence,
                                       aggregation_mode=config.convolution_mode, modulated=config.modulated, K_points=K_points,
@@ -161,7 +164,7 @@ def simple_block(layer_ind, inputs, features, radius, fdim, config, training):
     _check_inference(training)
     w = weight_variable([config.num_kernel_points, int(features.shape[1]), fdim])
     return KPConv(inputs['points'][layer_ind], inputs['points'][layer_ind], inputs['neighbors'][layer_ind], features, w,
-                  radius, config, epilogue=_epilogue(fdim, config, True))
+                  radius, config, epilogue=lambda: _epilogue(fdim, config, True))
 
 
 def _resnetb(layer_ind, inputs, features, radius, fdim, config, strided, deformable=False):
@@ -175,13 +178,18 @@ def _resnetb(layer_ind, inputs, features, radius, fdim, config, strided, deforma
             q, s, nb = inputs['points'][layer_ind + 1], inputs['points'][layer_ind], inputs['pools'][layer_ind]
         else:
             q, s, nb = inputs['points'][layer_ind], inputs['points'][layer_ind], inputs['neighbors'][layer_ind]
-        x = (KPConv_deformable if deformable else KPConv)(q, s, nb, x, w, radius, config, epilogue=_epilogue(fdim // 2, config, True))
+        x = (KPConv_deformable if deformable else KPConv)(q, s, nb, x, w, radius, config,
+                                                          epilogue=lambda: _epilogue(fdim // 2, config, True))
     # variables are created in the reference's order (conv3 before shortcut, :342-356 / :585-600) so that lazily created
     # random weights equal build_variables(seed)'s; the compute order below is free
     with variable_scope('conv3'):
         vs = _vs()
         w3 = vs.weight_variable([fdim // 2, 2 * fdim])
-        bn3 = vs.batch_norm_variables(2 * fdim) if config.use_batch_norm else None
+        bn3 = None
+        if config.use_batch_norm:
+            bn3 = vs.batch_norm_variables(2 * fdim)
+        else:
+            vs.offset_variable(2 * fdim)      # conv3's `offset` (:162-165) before the shortcut's variables, as in the reference
     with variable_scope('shortcut'):
         shortcut = ind_max_pool(features, inputs['pools'][layer_ind]) if strided else features
         need_sc = int(shortcut.shape[1]) != 2 * fdim

@@ -72,6 +72,10 @@ class VariableStore:
                      self.get('moving_variance', (channels,), lambda: np.ones(channels))]
         return names
 
+    def offset_variable(self, channels):
+        """models/network_blocks.py:162-165: the `offset` vector a block adds in place of batch norm (use_batch_norm = False), zeros."""
+        return self.get('offset', (channels,), lambda: np.zeros(channels))
+
     # ---- device copies ------------------------------------------------------------------------------------
     def tensor(self, full):
         t = self._dev.get(full)
@@ -169,11 +173,17 @@ class VariableStore:
         self._recipes = {}
 
 
-def build_variables(config, seed=42, in_features_dim=None, randomize_bn=False, device=None, randomize_offsets=False):
+def build_variables(config, seed=42, in_features_dim=None, randomize_bn=False, device=None, randomize_offsets=False,
+                    kernel_points=None):
     """Create every variable of the network on the host without running it: a shape-only walk of
     models/network_blocks.py:1052-1118 (encoder) and models/D3Feat.py:19-63 (decoder).  The result has exactly the
     variable names / shapes of the reference's checkpoints (tests/test_host_logic.py checks
-    it against the table decoded from results/Log_contraloss/snapshots/snap-54.index).
+    it against the table decoded from results/Log_contraloss/snapshots/snap-54.index).  Without batch norm (config.use_batch_norm
+    False) every block has the `offset` vector of models/network_blocks.py:162-165 where it would have its batch_normalization/*
+    variables.
+
+    kernel_points: callable (radius, num_kernel_points, rng) -> [num_kernel_points, 3] that replaces create_kernel_points, which
+    optimises a disposition for every new count and caches it in a file of the package directory.
 
     randomize_bn: draw non-trivial batch-norm statistics (for parity tests; identity statistics hide bugs).
     randomize_offsets: draw non-zero `offset_conv_weights` / `offset_conv_bias` for the deformable blocks (for parity tests: the
@@ -187,6 +197,9 @@ def build_variables(config, seed=42, in_features_dim=None, randomize_bn=False, d
     cin = config.in_features_dim if in_features_dim is None else in_features_dim
 
     def bn(ch):
+        if not config.use_batch_norm:
+            vs.offset_variable(ch)
+            return
         names = vs.batch_norm_variables(ch)
         if randomize_bn:
             vs.values[names[0]] = (1.0 + 0.2 * vs.rng.standard_normal(ch)).astype(np.float32)
@@ -197,6 +210,9 @@ def build_variables(config, seed=42, in_features_dim=None, randomize_bn=False, d
     def kpconv(ci, co, layer):
         vs.weight_variable([K, ci, co])
         extent = config.KP_extent * (config.first_subsampling_dl * config.density_parameter * 2 ** layer) / config.density_parameter
+        if kernel_points is not None:
+            vs.get('kernel_points', (K, 3), lambda: np.asarray(kernel_points(1.5 * extent, K, vs.rng)).reshape(K, 3))
+            return
         vs.get('kernel_points', (K, 3), lambda: create_kernel_points(1.5 * extent, K, 1, 3, config.fixed_kernel_points,
                                                                      rng=vs.rng).reshape(K, 3))
 

@@ -153,9 +153,12 @@ def closest_pool(x, inds):
     return x[torch.as_tensor(inds).long()[:, 0]]
 
 
-def batch_norm(x, W, scope, eps=1e-6):
+def batch_norm(x, W, scope, eps=1e-6, use_batch_norm=True):
     """models/network_blocks.py:149-160 in inference mode (training = dropout_prob < 0.99 is False at
-    test time, :1071): tf.layers.batch_normalization with moving statistics, epsilon 1e-6."""
+    test time, :1071): tf.layers.batch_normalization with moving statistics, epsilon 1e-6.  Without batch norm
+    (:162-165) the block's `offset` vector is added instead."""
+    if not use_batch_norm:
+        return x + torch.as_tensor(W[scope + "/offset"], dtype=torch.float32)
     g = torch.as_tensor(W[scope + "/batch_normalization/gamma"])
     b = torch.as_tensor(W[scope + "/batch_normalization/beta"])
     m = torch.as_tensor(W[scope + "/batch_normalization/moving_mean"])
@@ -188,7 +191,7 @@ def _w(W, name):
 def unary_block(layer_ind, inputs, features, radius, fdim, config, W, scope):
     """:207-219."""
     x = unary_convolution(features, _w(W, scope + "/weights"))
-    return leaky_relu(batch_norm(x, W, scope))
+    return leaky_relu(batch_norm(x, W, scope, use_batch_norm=config.use_batch_norm))
 
 
 def last_unary_block(layer_ind, inputs, features, radius, fdim, config, W, scope):
@@ -200,21 +203,21 @@ def simple_block(layer_ind, inputs, features, radius, fdim, config, W, scope):
     """:222-244."""
     x = KPConv(inputs["points"][layer_ind], inputs["points"][layer_ind], inputs["neighbors"][layer_ind], features,
                _w(W, scope + "/weights"), _w(W, scope + "/kernel_points"), radius, config)
-    return leaky_relu(batch_norm(x, W, scope))
+    return leaky_relu(batch_norm(x, W, scope, use_batch_norm=config.use_batch_norm))
 
 
 def resnetb_block(layer_ind, inputs, features, radius, fdim, config, W, scope):
     """:321-368."""
     x = unary_convolution(features, _w(W, scope + "/conv1/weights"))
-    x = leaky_relu(batch_norm(x, W, scope + "/conv1"))
+    x = leaky_relu(batch_norm(x, W, scope + "/conv1", use_batch_norm=config.use_batch_norm))
     x = KPConv(inputs["points"][layer_ind], inputs["points"][layer_ind], inputs["neighbors"][layer_ind], x,
                _w(W, scope + "/conv2/weights"), _w(W, scope + "/conv2/kernel_points"), radius, config)
-    x = leaky_relu(batch_norm(x, W, scope + "/conv2"))
+    x = leaky_relu(batch_norm(x, W, scope + "/conv2", use_batch_norm=config.use_batch_norm))
     x = unary_convolution(x, _w(W, scope + "/conv3/weights"))
-    x = batch_norm(x, W, scope + "/conv3")
+    x = batch_norm(x, W, scope + "/conv3", use_batch_norm=config.use_batch_norm)
     if features.shape[1] != 2 * fdim:
         shortcut = unary_convolution(features, _w(W, scope + "/shortcut/weights"))
-        shortcut = batch_norm(shortcut, W, scope + "/shortcut")
+        shortcut = batch_norm(shortcut, W, scope + "/shortcut", use_batch_norm=config.use_batch_norm)
     else:
         shortcut = features
     return leaky_relu(x + shortcut)
@@ -223,16 +226,16 @@ def resnetb_block(layer_ind, inputs, features, radius, fdim, config, W, scope):
 def resnetb_strided_block(layer_ind, inputs, features, radius, fdim, config, W, scope):
     """:561-612."""
     x = unary_convolution(features, _w(W, scope + "/conv1/weights"))
-    x = leaky_relu(batch_norm(x, W, scope + "/conv1"))
+    x = leaky_relu(batch_norm(x, W, scope + "/conv1", use_batch_norm=config.use_batch_norm))
     x = KPConv(inputs["points"][layer_ind + 1], inputs["points"][layer_ind], inputs["pools"][layer_ind], x,
                _w(W, scope + "/conv2/weights"), _w(W, scope + "/conv2/kernel_points"), radius, config)
-    x = leaky_relu(batch_norm(x, W, scope + "/conv2"))
+    x = leaky_relu(batch_norm(x, W, scope + "/conv2", use_batch_norm=config.use_batch_norm))
     x = unary_convolution(x, _w(W, scope + "/conv3/weights"))
-    x = batch_norm(x, W, scope + "/conv3")
+    x = batch_norm(x, W, scope + "/conv3", use_batch_norm=config.use_batch_norm)
     shortcut = ind_max_pool(features, inputs["pools"][layer_ind])
     if shortcut.shape[1] != 2 * fdim:
         shortcut = unary_convolution(shortcut, _w(W, scope + "/shortcut/weights"))
-        shortcut = batch_norm(shortcut, W, scope + "/shortcut")
+        shortcut = batch_norm(shortcut, W, scope + "/shortcut", use_batch_norm=config.use_batch_norm)
     return leaky_relu(x + shortcut)
 
 
