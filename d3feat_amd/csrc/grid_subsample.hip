@@ -23,6 +23,11 @@
 //     (insert / tile scan + tile sums in its last workgroup / place);
 //   * 9 + 3*rounds launches per call (csrc/prims.h: fused reset, boxes + geometry, one-launch scans); in capacity mode
 //     (d3f_batch_grid_subsample_async) all sizes stay on the device and an overflowing call reports an empty result.
+//
+// Three forms of the algorithm -- hash (gs_run_hash), sort (gs_run_sort), one workgroup per cloud (gs_small.h) -- on ONE copy of
+// every shared piece: the bit-exact voxel arithmetic (gs_axis, gs_cell, gs_inv_count, below), the bucket words and the order
+// round in LDS (gs_order.h), the scans (d3f_wave_incl_scan in common.h, d3f_block_excl_scan in prims.h), the digit bases of the
+// radix sort (rs_wave_bases in radix_sort.h).  Host side: GsWork::carve (the workspace), gs_run (picks the form), gs_order_launch.
 #include <cstdlib>
 #include "prims.h"
 #include "radix_sort.h"
@@ -44,11 +49,31 @@ struct GsElem {
     long long bbase;  // base of this element's bucket scratch
 };
 
-static unsigned long long gs_chain_ge(long long n) {
-    for (int j = 0; j < D3F_NCHAIN; ++j)
-        if ((long long)D3F_CHAIN_HOST[j] >= n) return D3F_CHAIN_HOST[j];
-    return D3F_CHAIN_HOST[D3F_NCHAIN - 1];
+#include "gs_order.h"
+
+// ---- the voxel arithmetic that has to match the reference bit for bit: ONE copy for the three forms --------------------------
+// Origin of one axis and the index of its last cell (an integral float >= 0; the axis has that + 1 cells) from the ordered-uint
+// min / max of the coordinate; inv = __fdiv_rn(1, dl), the reference's `1/sampleDl` (grid_subsampling.cpp:24-30).
+__device__ __forceinline__ float gs_axis(unsigned mn, unsigned mx, float dl, float inv, float& org) {
+    org = __fmul_rn(floorf(__fmul_rn(d3f_ord2f(mn), inv)), dl);
+    return fmaxf(floorf(__fdiv_rn(__fsub_rn(d3f_ord2f(mx), org), dl)), 0.f);
 }
+// Cell of point p per axis, clamped at 0 (integral floats, true IEEE divide: grid_subsampling.cpp:49-59); returns
+// D3F_ST_NEG_CELL when an index was negative, else 0.  Every site assembles its own key from the indices.
+__device__ __forceinline__ int gs_cell(const float* __restrict__ p, float ox, float oy, float oz, float dl, float& cx, float& cy,
+                                       float& cz) {
+    const float fx = floorf(__fdiv_rn(__fsub_rn(p[0], ox), dl));
+    const float fy = floorf(__fdiv_rn(__fsub_rn(p[1], oy), dl));
+    const float fz = floorf(__fdiv_rn(__fsub_rn(p[2], oz), dl));
+    cx = fmaxf(fx, 0.f);
+    cy = fmaxf(fy, 0.f);
+    cz = fmaxf(fz, 0.f);
+    return (fx < 0.f || fy < 0.f || fz < 0.f) ? D3F_ST_NEG_CELL : 0;
+}
+
+// Scale of a voxel's fp32 coordinate sum: the reference's `1.0 / v.second.count` is a double, narrowed by
+// operator*(PointXYZ, float) (grid_subsampling.cpp:81-92).
+__device__ __forceinline__ float gs_inv_count(int c) { return (float)(1.0 / (double)c); }
 
 __device__ __forceinline__ unsigned long long gs_mix(unsigned long long x) {
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
@@ -81,16 +106,14 @@ __device__ __forceinline__ void gs_prep(const unsigned* __restrict__ bbox, const
             e.NX = e.NY = e.NZ = 1;
         } else {
             const float inv = __fdiv_rn(1.0f, dl);  // `1/sampleDl`
-            float mx[3];
+            unsigned long long dims[3];
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
-                float mn = d3f_ord2f(__hip_atomic_load(&bbox[b * 6 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                mx[d] = d3f_ord2f(__hip_atomic_load(&bbox[b * 6 + 3 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                e.org[d] = __fmul_rn(floorf(__fmul_rn(mn, inv)), dl);
+                const unsigned mn = __hip_atomic_load(&bbox[b * 6 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned mx = __hip_atomic_load(&bbox[b * 6 + 3 + d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                dims[d] = (unsigned long long)gs_axis(mn, mx, dl, inv, e.org[d]) + 1ull;
             }
-            e.NX = (unsigned long long)fmaxf(floorf(__fdiv_rn(__fsub_rn(mx[0], e.org[0]), dl)), 0.f) + 1ull;
-            e.NY = (unsigned long long)fmaxf(floorf(__fdiv_rn(__fsub_rn(mx[1], e.org[1]), dl)), 0.f) + 1ull;
-            e.NZ = (unsigned long long)fmaxf(floorf(__fdiv_rn(__fsub_rn(mx[2], e.org[2]), dl)), 0.f) + 1ull;
+            e.NX = dims[0]; e.NY = dims[1]; e.NZ = dims[2];
         }
         // bucket scratch base: prefix over elements of chain_ge(len)
         long long base = 0;
@@ -167,13 +190,9 @@ __global__ void __launch_bounds__(256) gs_insert_kernel(const float* __restrict_
     if (i >= min(N, offs[B])) return;   // N is the capacity, offs[B] the real point count
     const int b = d3f_find_elem(offs, B, i);
     const GsElem e = el[b];
-    const float fx = floorf(__fdiv_rn(__fsub_rn(pts[3 * (size_t)i + 0], e.org[0]), dl));
-    const float fy = floorf(__fdiv_rn(__fsub_rn(pts[3 * (size_t)i + 1], e.org[1]), dl));
-    const float fz = floorf(__fdiv_rn(__fsub_rn(pts[3 * (size_t)i + 2], e.org[2]), dl));
-    int st = 0;
-    if (fx < 0.f || fy < 0.f || fz < 0.f) st |= D3F_ST_NEG_CELL;
-    const unsigned long long ix = (unsigned long long)fmaxf(fx, 0.f), iy = (unsigned long long)fmaxf(fy, 0.f),
-                             iz = (unsigned long long)fmaxf(fz, 0.f);
+    float cx, cy, cz;
+    int st = gs_cell(pts + 3 * (size_t)i, e.org[0], e.org[1], e.org[2], dl, cx, cy, cz);
+    const unsigned long long ix = (unsigned long long)cx, iy = (unsigned long long)cy, iz = (unsigned long long)cz;
     const unsigned long long key = ix + e.NX * iy + e.NX * e.NY * iz;
     if (key > GS_KEYMASK) st |= D3F_ST_KEY_RANGE;
     if (st) atomicOr(&status[1], st);
@@ -275,22 +294,6 @@ __global__ void __launch_bounds__(256) gs_rank_kernel(int N, const int* __restri
 }
 
 // ---- libstdc++ unordered_map iteration order (closed form, see file header) --------------------------
-__device__ __forceinline__ int gs_ld(const int* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// key % nb for key < 2^56, nb < 2^31 without the 64-bit software division: double-precision quotient estimate
-// (off by at most 1 or 2) and a branch-free correction.
-__device__ __forceinline__ int gs_mod(unsigned long long key, unsigned nb, double inv_nb) {
-    const unsigned long long q = (unsigned long long)((double)key * inv_nb);
-    long long r = (long long)(key - q * (unsigned long long)nb);
-    r += (r < 0) ? (long long)nb : 0;
-    r += (r < 0) ? (long long)nb : 0;
-    r -= (r >= (long long)nb) ? (long long)nb : 0;
-    r -= (r >= (long long)nb) ? (long long)nb : 0;
-    return (int)r;
-}
-
 // Round j reads the insertion sequence from list buffer P[j&1] and writes the new list order to P[(j+1)&1]; its
 // bucket arrays are the parity-(j&1) set.  Rounds 0..GS_SMALL_LAST (bucket counts 13..1109) are tiny and run inside
 // ONE single-workgroup launch (gs_order_small_kernel); a single CU however sustains only ~1 divergent L2 access per
@@ -324,93 +327,39 @@ struct GsOrderArgs {
 // 256 threads, not 1024: a workgroup of 16 wavefronts + 44 KB of LDS has to wait for a CU that the other replays in flight have
 // left completely free (rocprof showed 190 us for 15 us of work); four wavefronts are placed at once
 #define GS_SMALL_T 256
-__global__ void __launch_bounds__(GS_SMALL_T) gs_order_small_kernel(GsOrderArgs A, int small_last) {
+__global__ void __launch_bounds__(GS_SMALL_T) gs_order_small_kernel(GsOrderArgs A) {
     __shared__ int wsum[GS_SMALL_T / 64];
     __shared__ int sBF[GS_SMALL_NB], sBC[GS_SMALL_NB], sBH[GS_SMALL_NB], sNX[GS_SMALL_NB], sCD[GS_SMALL_NB], sBK[GS_SMALL_NB];
     __shared__ int sL[2][GS_SMALL_NB];
     __shared__ unsigned long long sKey[GS_SMALL_NB];
     const int b = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const int M = A.moffs[b + 1] - A.moffs[b];
     if (M <= 0) return;
     const unsigned long long* key = A.vkey + A.moffs[b];
     int* VP = A.vpos + A.moffs[b];
     const long long bbase = A.el[b].bbase;
-    if (small_last > GS_SMALL_LAST) small_last = GS_SMALL_LAST;     // the LDS arrays are sized for 1109 buckets
     for (int t = tid; t < min(M, GS_SMALL_NB); t += GS_SMALL_T) sKey[t] = key[t];
-    int lo = 0, cur = 0;
-    bool done = false;
     __syncthreads();
-    for (int j = 0; j <= small_last && j < D3F_NCHAIN; ++j) {
-        const int nb = (int)D3F_CHAIN_DEV[j];
-        const double inv_nb = 1.0 / (double)nb;
-        const bool last = M <= nb;
-        const int hi = last ? M : nb;
-        const int* La = sL[cur];
-        int* Lb = sL[cur ^ 1];
-        for (int t = tid; t < nb; t += GS_SMALL_T) { sBF[t] = 0x7fffffff; sBC[t] = 0; sBH[t] = -1; }
-        __syncthreads();
-        for (int t = tid; t < hi; t += GS_SMALL_T) {
-            const int id = (t < lo) ? La[t] : t;
-            const int bk = gs_mod(sKey[id], (unsigned)nb, inv_nb);
-            atomicMin(&sBF[bk], t);
-            atomicAdd(&sBC[bk], 1);
-            sNX[t] = atomicExch(&sBH[bk], t);
-            sBK[t] = bk;
-        }
-        __syncthreads();
-        int carry = 0;
-        for (int c0 = 0; c0 < hi; c0 += GS_SMALL_T) {
-            const int u = c0 + tid, t = hi - 1 - u;
-            int c = 0;
-            if (u < hi) {
-                const int bk = sBK[t];
-                c = (sBF[bk] == t) ? sBC[bk] : 0;
-            }
-            int x = c;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                int y = __shfl_up(x, d, 64);
-                if (lane >= d) x += y;
-            }
-            if (lane == 63) wsum[w] = x;
-            __syncthreads();
-            int wbase = 0, tot = 0;
-#pragma unroll
-            for (int q = 0; q < GS_SMALL_T / 64; ++q) {
-                int v = wsum[q];
-                if (q < w) wbase += v;
-                tot += v;
-            }
-            __syncthreads();
-            if (u < hi) sCD[t] = carry + wbase + x - c;
-            carry += tot;
-        }
-        __syncthreads();
-        for (int t = tid; t < hi; t += GS_SMALL_T) {
-            const int id = (t < lo) ? La[t] : t;
-            const int bk = sBK[t];
-            int r = 0;
-            for (int q = sBH[bk]; q >= 0; q = sNX[q]) r += (q > t) ? 1 : 0;
-            const int dest = sCD[sBF[bk]] + r;
+    GsOrderLds<unsigned long long> S;       // (field by field: an aggregate of LDS addresses would be a static initialiser)
+    S.key = sKey; S.bf = sBF; S.bc = sBC; S.bh = sBH; S.nx = sNX; S.cd = sCD; S.bk = sBK; S.L0 = sL[0]; S.L1 = sL[1];
+    S.wsum = wsum;
+    int lo;
+    const int* list;
+    const bool done = gs_order_rounds_lds<GS_SMALL_T, unsigned long long, true>(
+        S, M, GS_SMALL_LAST,
+        [VP](int* Lb, int id, int dest) {
             Lb[dest] = id;
-            if (last) VP[id] = dest;
-        }
-        __syncthreads();
-        cur ^= 1;
-        if (last) { done = true; break; }
-        lo = hi;
-    }
-    if (!done && small_last + 1 < D3F_NCHAIN) {
+            VP[id] = dest;
+        },
+        lo, list);
+    if (!done && GS_SMALL_LAST + 1 < D3F_NCHAIN) {
         // hand over to the first grid-wide round j: it reads the current list from P[j & 1] and expects clean bucket arrays
-        const int j = small_last + 1;
+        const int j = GS_SMALL_LAST + 1;
         int* P = A.P[j & 1] + A.offs[b];
-        for (int t = tid; t < lo; t += GS_SMALL_T) P[t] = sL[cur][t];
+        for (int t = tid; t < lo; t += GS_SMALL_T) P[t] = list[t];
         const int nb = (int)D3F_CHAIN_DEV[j];
-        int* BF = A.bf[j & 1] + bbase;
-        int* BC = A.bc[j & 1] + bbase;
-        int* BH = A.bh[j & 1] + bbase;
-        for (int t = tid; t < nb; t += GS_SMALL_T) { BF[t] = 0x7fffffff; BC[t] = 0; BH[t] = -1; }
+        for (int t = tid; t < nb; t += GS_SMALL_T) gs_bucket_reset(A.bf[j & 1] + bbase, A.bc[j & 1] + bbase, A.bh[j & 1] + bbase, t);
     }
 }
 
@@ -436,9 +385,7 @@ __global__ void __launch_bounds__(256) gs_order_insert_kernel(GsOrderArgs A, int
     const long long bbase = A.el[b].bbase;
     const int id = (t < lo) ? A.P[j & 1][o + t] : t;
     const int bk = gs_mod(A.vkey[A.moffs[b] + id], (unsigned)nb, 1.0 / (double)nb);
-    atomicMin(&A.bf[j & 1][bbase + bk], t);
-    atomicAdd(&A.bc[j & 1][bbase + bk], 1);
-    A.nx[j & 1][o + t] = atomicExch(&A.bh[j & 1][bbase + bk], t);
+    A.nx[j & 1][o + t] = gs_bucket_insert(A.bf[j & 1] + bbase, A.bc[j & 1] + bbase, A.bh[j & 1] + bbase, bk, t);
     A.bkt[j & 1][o + t] = bk;
 }
 
@@ -449,28 +396,13 @@ __device__ __forceinline__ void gs_order_scan_sums(const GsOrderArgs& A, int j, 
     if (!gs_round(A, b, j, M, lo, hi, nb, last)) return;
     int* ts = A.tsum + A.offs[b] / GS_TILE + b;
     const int ntiles = (hi + GS_TILE - 1) / GS_TILE;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     int carry = 0;
     for (int c0 = 0; c0 < ntiles; c0 += 256) {
-        const int i = c0 + tid;
+        const int i = c0 + (int)threadIdx.x;
         const int v = (i < ntiles) ? __hip_atomic_load(&ts[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-        int x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        int wbase = 0, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int s = wsum[q];
-            if (q < w) wbase += s;
-            tot += s;
-        }
-        __syncthreads();
-        if (i < ntiles) ts[i] = carry + wbase + x - v;
+        int tot;
+        const int e = d3f_block_excl_scan<256>(v, wsum, &tot);
+        if (i < ntiles) ts[i] = carry + e;
         carry += tot;
     }
 }
@@ -490,17 +422,14 @@ __global__ void __launch_bounds__(256) gs_order_scan_tiles_kernel(GsOrderArgs A,
     {
         const int o = A.offs[b];
         const long long bbase = A.el[b].bbase;
-        const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+        const int tid = threadIdx.x;
         if (!last && j + 1 < D3F_NCHAIN) {
             // clear the other parity's bucket arrays: round j + 1 is inserted by this round's place kernel (nb_next < 2.24 hi;
             // they were last read by round j - 1's place kernel, which has finished)
             const int nbn = (int)D3F_CHAIN_DEV[j + 1];
             const int stride = ((hi + GS_TILE - 1) / GS_TILE) * 256;
-            for (int i = tile * 256 + tid; i < nbn; i += stride) {
-                A.bf[(j + 1) & 1][bbase + i] = 0x7fffffff;
-                A.bc[(j + 1) & 1][bbase + i] = 0;
-                A.bh[(j + 1) & 1][bbase + i] = -1;
-            }
+            for (int i = tile * 256 + tid; i < nbn; i += stride)
+                gs_bucket_reset(A.bf[(j + 1) & 1] + bbase, A.bc[(j + 1) & 1] + bbase, A.bh[(j + 1) & 1] + bbase, i);
         }
         int c[4], s = 0;
 #pragma unroll
@@ -513,22 +442,8 @@ __global__ void __launch_bounds__(256) gs_order_scan_tiles_kernel(GsOrderArgs A,
             }
             s += c[k];
         }
-        int x = s;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        int wbase = 0, tot = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int v = wsum[q];
-            if (q < w) wbase += v;
-            tot += v;
-        }
-        int run = wbase + x - s;
+        int tot;
+        int run = d3f_block_excl_scan<256>(s, wsum, &tot);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int u = tile * GS_TILE + tid * 4 + k;
@@ -570,9 +485,8 @@ __global__ void __launch_bounds__(256) gs_order_place_kernel(GsOrderArgs A, int 
     }
     if (next && id >= 0) {
         const int bk = gs_mod(A.vkey[A.moffs[b] + id], (unsigned)nbn, 1.0 / (double)nbn);
-        atomicMin(&A.bf[(j + 1) & 1][bbase + bk], pos);
-        atomicAdd(&A.bc[(j + 1) & 1][bbase + bk], 1);
-        A.nx[(j + 1) & 1][o + pos] = atomicExch(&A.bh[(j + 1) & 1][bbase + bk], pos);
+        A.nx[(j + 1) & 1][o + pos] =
+            gs_bucket_insert(A.bf[(j + 1) & 1] + bbase, A.bc[(j + 1) & 1] + bbase, A.bh[(j + 1) & 1] + bbase, bk, pos);
         A.bkt[(j + 1) & 1][o + pos] = bk;
     }
 }
@@ -632,11 +546,9 @@ __global__ void __launch_bounds__(RS_THREADS) gs_sortkey_kernel(const float* __r
             // the bounding box keeps every index below its dimension
             const unsigned NX = (unsigned)sEl[b].NX, NY = (unsigned)sEl[b].NY;
             const float* __restrict__ P = sBase[b];
-            const float fx = floorf(__fdiv_rn(__fsub_rn(P[3 * (size_t)i + 0], ox), dl));
-            const float fy = floorf(__fdiv_rn(__fsub_rn(P[3 * (size_t)i + 1], oy), dl));
-            const float fz = floorf(__fdiv_rn(__fsub_rn(P[3 * (size_t)i + 2], oz), dl));
-            if (fx < 0.f || fy < 0.f || fz < 0.f) st |= D3F_ST_NEG_CELL;
-            const unsigned ix = (unsigned)fmaxf(fx, 0.f), iy = (unsigned)fmaxf(fy, 0.f), iz = (unsigned)fmaxf(fz, 0.f);
+            float cx, cy, cz;
+            st |= gs_cell(P + 3 * (size_t)i, ox, oy, oz, dl, cx, cy, cz);
+            const unsigned ix = (unsigned)cx, iy = (unsigned)cy, iz = (unsigned)cz;
             const unsigned k = ix + NX * (iy + NY * iz);                 // < NX NY NZ <= 2^kb
             key[r] = (kb < 32 ? ((unsigned)b << kb) : 0u) | (kb < 32 ? (k & ((1u << kb) - 1u)) : k);
             skey[i] = key[r];
@@ -721,7 +633,7 @@ __global__ void __launch_bounds__(256) gs_runs_kernel(int N, const RsMeta* __res
             ++c;
         }
     }
-    const float sc = (float)(1.0 / (double)c);  // `1.0 / v.second.count` is a double, narrowed by operator*(PointXYZ, float)
+    const float sc = gs_inv_count(c);
     vkey[v] = (unsigned long long)(smeta->kb < 32 ? (k & ((1u << smeta->kb) - 1u)) : k);
     bary[3 * (size_t)v + 0] = __fmul_rn(ax, sc);
     bary[3 * (size_t)v + 1] = __fmul_rn(ay, sc);
@@ -782,7 +694,7 @@ __global__ void __launch_bounds__(256) gs_accum_kernel(const float* __restrict__
         sy = __fadd_rn(sy, pts[3 * i + 1]);
         sz = __fadd_rn(sz, pts[3 * i + 2]);
     }
-    const float sc = (float)(1.0 / (double)n);  // `1.0 / v.second.count` is a double, narrowed by operator*(PointXYZ, float)
+    const float sc = gs_inv_count(n);
     out_p[3 * dest + 0] = __fmul_rn(sx, sc);
     out_p[3 * dest + 1] = __fmul_rn(sy, sc);
     out_p[3 * dest + 2] = __fmul_rn(sz, sc);
@@ -798,10 +710,6 @@ __global__ void __launch_bounds__(256) gs_accum_kernel(const float* __restrict__
 
 // classes: the reference's max_element over unordered_map<int,int> compares (label, count) pairs, label
 // first, i.e. returns the LARGEST label id present in the voxel (grid_subsampling.cpp:94).
-__global__ void __launch_bounds__(256) gs_fill_kernel(int* __restrict__ p, size_t n, int v) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
 __global__ void __launch_bounds__(256) gs_labels_kernel(int N, int ldim, const int* __restrict__ cls,
                                                         const int* __restrict__ pvid, const int* __restrict__ moffs, int B,
                                                         const int* __restrict__ vpos, int* __restrict__ out_c) {
@@ -894,157 +802,100 @@ static int gs_run_small(const float* points, int N, const int* lens_dev, int B, 
     return gs_small_launch<1024, 16>(A, sub_points, sub_lens_dev, status_dev, stream);
 }
 
-// Shared implementation.  sync mode (status_host != NULL): ONE host synchronisation after the voxel count is known,
-// everything after it sized by M.  async mode (status_dev != NULL): no host round trip at all -- N and M_cap are
-// capacities, the real sizes live in HBM (lens_dev -> offs[B]; M -> status_dev[0]) and every kernel bounds itself by them,
-// so the call can be captured in a HIP graph and replayed for clouds of any size up to the capacity.
-static int gs_run(const float* points, int N, const int* lens_dev, int B, float dl, const float* features, int fdim,
-                  const int* classes, int ldim, float* sub_points, int M_cap, int elem_cap, int elem_points, float* sub_features,
-                  int* sub_classes, int* sub_lens_dev, int* status_host, int* status_dev, void* workspace,
-                  size_t workspace_bytes, hipStream_t stream, const float* const* ptrs = nullptr, const unsigned* bbox_in = nullptr,
-                  unsigned* bbox_out = nullptr) {
-    const bool async = status_dev != nullptr;
-    if (async && !features && ldim == 0 && !ptrs) {
-        // one workgroup per cloud when the caller's capacities fit it: every cloud <= 16384 points and <= 5087 voxels (a cloud
-        // beyond its stated capacity is reported by either form, so the choice adds no failure mode)
-        const int pc = (elem_points > 0 && elem_points < N) ? elem_points : N;
-        int ec = (elem_cap > 0 && elem_cap < M_cap) ? elem_cap : M_cap;
-        if (ec > pc) ec = pc;
-        if (pc <= 16384 && ec <= GSS_NB_MAX) return gs_run_small(points, N, lens_dev, B, dl, sub_points, M_cap, elem_cap, pc, sub_lens_dev, status_dev,
-                                             workspace, workspace_bytes, stream, bbox_out);
-    }
-    GsLayout L = gs_layout(N, B, async ? M_cap : -1);
-    D3fArena ar(workspace, workspace_bytes);
-    const size_t n = (size_t)N;
-    int* offs = ar.take<int>(B + 1);
-    int* moffs = ar.take<int>(B + 1);
-    unsigned* bbox = ar.take<unsigned>(B * 6);
-    GsElem* el = ar.take<GsElem>(B);
+// The arguments of one call (hash and sort form), as the entry points receive them.
+struct GsCall {
+    const float* points; int N; const int* lens_dev; int B; float dl;
+    const float* features; int fdim; const int* classes; int ldim;
+    float* sub_points; int M_cap; float* sub_features; int* sub_classes; int* sub_lens_dev;
+    int* status_host;               // sync mode: [M, flags, per-element counts]
+    int* status_dev;                // async (capacity) mode
+    hipStream_t stream;
+    const float* const* ptrs;       // clouds read in place (sort form)
+    const unsigned* bbox_in;        // finished boxes of the input clouds (sort form)
+    unsigned* bbox_out;             // boxes of the clouds this call writes
+};
+
+// The workspace of the hash and the sort form: ONE pass over the arena, in layout order (d3f_grid_subsample_workspace_bytes
+// counts the same arrays).
+struct GsWork {
+    GsLayout L;
+    int *offs, *moffs;
+    unsigned* bbox;
+    GsElem* el;
     // ticket counters: [0] boxes, [1] voxel-id scan, [2] start scan, [4 + j * B + b] iteration-order round j of element b
-    const int ncounters = 4 + D3F_NCHAIN * B;
-    unsigned* counters = ar.take<unsigned>(ncounters);
-    // [tkey | tfirst | vhead] are reset to 0xFFFFFFFF and [meta | vcnt] to 0 by ONE launch: keep each group contiguous
-    unsigned long long* tkey = ar.take<unsigned long long>(L.cap);
-    unsigned* tfirst = ar.take<unsigned>(L.cap);
-    int* vhead = ar.take<int>(n);
-    int* meta = ar.take<int>(B + 2);   // [M, flags, sub_lens...]
-    int* vcnt = ar.take<int>(n);
-    unsigned long long* vkey = ar.take<unsigned long long>(n);
-    int* slot = ar.take<int>(n);
-    int* vscan = ar.take<int>(n);
-    int* pvid = ar.take<int>(n);
-    int* pnext = ar.take<int>(n);
-    int* vstart = ar.take<int>(n);
-    int* sorted = ar.take<int>(n);
+    int ncounters;
+    unsigned* counters;
+    // [tkey | tfirst | vhead] are reset to 0xFFFFFFFF and [meta | vcnt] to 0 by ONE launch: each group is contiguous
+    unsigned long long* tkey;
+    unsigned* tfirst;
+    int* vhead;
+    int* meta;   // [M, flags, sub_lens...]
+    int* vcnt;
+    unsigned long long* vkey;
+    int *slot, *vscan, *pvid, *pnext, *vstart, *sorted;
     GsOrderArgs A;
-    A.vpos = ar.take<int>(n);
-    A.P[0] = ar.take<int>(n);
-    A.P[1] = ar.take<int>(n);
-    A.nx[0] = ar.take<int>(n);
-    A.nx[1] = ar.take<int>(n);
-    A.cd = ar.take<int>(n);
-    A.bkt[0] = ar.take<int>(n);
-    A.bkt[1] = ar.take<int>(n);
-    for (int k = 0; k < 2; ++k) {
-        A.bf[k] = ar.take<int>((size_t)L.bucket_total);
-        A.bc[k] = ar.take<int>((size_t)L.bucket_total);
-        A.bh[k] = ar.take<int>((size_t)L.bucket_total);
-    }
-    A.tsum = ar.take<int>(n / GS_TILE + B + 8);
-    int* vbase = ar.take<int>(d3f_scan_base_ints(N));   // tile offsets of the voxel-id scan
-    int* sbase = ar.take<int>(d3f_scan_base_ints(N));   // ... of the voxel-start scan
-    // sort form of the point -> voxel pass: capacity mode, points only, large calls (see gs_sortkey_kernel)
-    const bool use_sort = async && !features && ldim == 0;     // capacity mode: always the sort form (or gs_run_small above)
-    unsigned* rs_hist = ar.take<unsigned>(rs_hist_words(N));
-    unsigned* fbits = ar.take<unsigned>(n / 32 + 2);
-    float* bary = ar.take<float>(3 * n);
-    RsMeta* smeta = ar.take<RsMeta>(1);
-    if (!ar.ok) return D3F_ERR_WORKSPACE;
-    A.vkey = vkey; A.moffs = moffs; A.offs = offs; A.el = el;
-    if (elem_cap <= 0 || elem_cap > M_cap) elem_cap = M_cap;
-    if (elem_cap > N) elem_cap = N;
-    A.max_m = async ? elem_cap : 0x7fffffff;
+    int* vbase;   // tile offsets of the voxel-id scan
+    int* sbase;   // ... of the voxel-start scan
+    // sort form: digit histograms, first-occurrence bits, per-voxel barycentres, the sort's description
+    unsigned* rs_hist;
+    unsigned* fbits;
+    float* bary;
+    RsMeta* smeta;
 
-    // 9 + 3 * rounds launches (was 27 + 4 * rounds): reset -> boxes (+ grid geometry) -> keys / hash insert ->
-    // voxel-id scan (first-occurrence flags fused in, per-element offsets / lengths / status in its last workgroup) ->
-    // chains -> start scan -> in-chain rank -> iteration order (small rounds in one workgroup, large rounds grid-wide) ->
-    // in-order accumulation.
-    int rc;
-    const D3fFill none{nullptr, 0ull, 0u};
-    const unsigned long long ones_words = (unsigned long long)((char*)(vhead + n) - (char*)tkey) / 4ull;
-    const unsigned long long zero_words = (unsigned long long)((char*)(vcnt + n) - (char*)meta) / 4ull;
-    // (sort form: only the first-occurrence bits and the status words need clearing)
-    if (bbox_in && use_sort) {
-        // finished boxes: no pass over the points, the grid geometry is derived by the reset launch itself
-        const unsigned long long words = (unsigned long long)(n / 32 + 2);
-        long long blocks = (long long)(words / 4 / 256) + 1;
-        if (blocks > 1024) blocks = 1024;
-        gs_begin_boxed_kernel<<<(int)blocks, 256, 0, stream>>>(lens_dev, B, offs, bbox_in, counters, ncounters, D3fFill{fbits, words, 0u},
-                                                               D3fFill{(unsigned*)meta, (unsigned long long)(B + 2), 0u}, dl, el, meta,
-                                                               smeta, N);
-        D3F_LAUNCH_CHECK();
-    } else {
-    if ((rc = use_sort ? d3f_begin_launch(lens_dev, B, offs, bbox, counters, ncounters, D3fFill{fbits, (unsigned long long)(n / 32 + 2), 0u},
-                                          D3fFill{(unsigned*)meta, (unsigned long long)(B + 2), 0u}, none, none, stream)
-                       : d3f_begin_launch(lens_dev, B, offs, bbox, counters, ncounters, D3fFill{(unsigned*)tkey, ones_words, 0xFFFFFFFFu},
-                                          D3fFill{(unsigned*)meta, zero_words, 0u}, none, none, stream)) != D3F_OK) return rc;
-    GsPrepEpi prep{bbox, offs, B, dl, el, meta, use_sort ? smeta : nullptr, N};
-    if ((rc = d3f_bbox_launch_t(points, offs, B, N, bbox, counters, prep, stream, ptrs)) != D3F_OK) return rc;
+    bool carve(void* workspace, size_t workspace_bytes, int N, int B, int keys) {
+        L = gs_layout(N, B, keys);
+        D3fArena ar(workspace, workspace_bytes);
+        const size_t n = (size_t)N;
+        offs = ar.take<int>(B + 1);
+        moffs = ar.take<int>(B + 1);
+        bbox = ar.take<unsigned>(B * 6);
+        el = ar.take<GsElem>(B);
+        ncounters = 4 + D3F_NCHAIN * B;
+        counters = ar.take<unsigned>(ncounters);
+        tkey = ar.take<unsigned long long>(L.cap);
+        tfirst = ar.take<unsigned>(L.cap);
+        vhead = ar.take<int>(n);
+        meta = ar.take<int>(B + 2);
+        vcnt = ar.take<int>(n);
+        vkey = ar.take<unsigned long long>(n);
+        slot = ar.take<int>(n);
+        vscan = ar.take<int>(n);
+        pvid = ar.take<int>(n);
+        pnext = ar.take<int>(n);
+        vstart = ar.take<int>(n);
+        sorted = ar.take<int>(n);
+        A.vpos = ar.take<int>(n);
+        A.P[0] = ar.take<int>(n);
+        A.P[1] = ar.take<int>(n);
+        A.nx[0] = ar.take<int>(n);
+        A.nx[1] = ar.take<int>(n);
+        A.cd = ar.take<int>(n);
+        A.bkt[0] = ar.take<int>(n);
+        A.bkt[1] = ar.take<int>(n);
+        for (int k = 0; k < 2; ++k) {
+            A.bf[k] = ar.take<int>((size_t)L.bucket_total);
+            A.bc[k] = ar.take<int>((size_t)L.bucket_total);
+            A.bh[k] = ar.take<int>((size_t)L.bucket_total);
+        }
+        A.tsum = ar.take<int>(n / GS_TILE + B + 8);
+        vbase = ar.take<int>(d3f_scan_base_ints(N));
+        sbase = ar.take<int>(d3f_scan_base_ints(N));
+        rs_hist = ar.take<unsigned>(rs_hist_words(N));
+        fbits = ar.take<unsigned>(n / 32 + 2);
+        bary = ar.take<float>(3 * n);
+        smeta = ar.take<RsMeta>(1);
+        A.vkey = vkey; A.moffs = moffs; A.offs = offs; A.el = el;
+        return ar.ok;
     }
-    const int nblk = d3f_cdiv(N, 256);
-    const int elem_lim = async ? elem_cap : 0x7fffffff;
-    int M, maxM;       // sizes of the voxel-indexed launches
-    if (use_sort) {
-        // storage reuse: sort keys in slot / pnext, point indices in pvid / sorted, word scan in vscan / vbase
-        unsigned *key0 = (unsigned*)slot, *key1 = (unsigned*)pnext, *val0 = (unsigned*)pvid, *val1 = (unsigned*)sorted;
-        gs_sortkey_kernel<<<rs_tiles(N), RS_THREADS, 0, stream>>>(points, ptrs, offs, B, dl, el, smeta, key0, rs_hist, meta);
-        D3F_LAUNCH_CHECK();
-        if ((rc = rs_sort_launch(smeta, N, key0, key1, val0, val1, rs_hist, stream)) != D3F_OK) return rc;
-        gs_heads_kernel<<<nblk, 256, 0, stream>>>(N, smeta, key0, key1, val0, val1, fbits);
-        D3F_LAUNCH_CHECK();
-        const GsRankBits rank{fbits, vscan, vbase};
-        GsMoffsEpi<GsRankBits> mepi{offs, B, rank, meta, moffs, sub_lens_dev, status_dev, M_cap, elem_lim};
-        if ((rc = d3f_scan_fold_launch(GsBitsIn{fbits}, N / 32 + 1, nullptr, vscan, vbase, counters + 1, mepi, stream)) != D3F_OK)
-            return rc;
-        gs_runs_kernel<<<nblk, 256, 0, stream>>>(N, smeta, key0, key1, val0, val1, rank, points, ptrs, offs, vkey, bary);
-        D3F_LAUNCH_CHECK();
-        M = N < M_cap ? N : M_cap;
-        maxM = elem_cap;
-    } else {
-    GsMoffsEpi<GsRankScan> mepi{offs, B, GsRankScan{vscan, vbase}, meta, moffs, sub_lens_dev, status_dev, M_cap, elem_lim};
-    gs_insert_kernel<<<nblk, 256, 0, stream>>>(points, N, offs, B, dl, el, tkey, tfirst, (unsigned long long)L.cap - 1ull,
-                                               slot, meta);
-    D3F_LAUNCH_CHECK();
-    if ((rc = d3f_scan_fold_launch(GsMarkIn{offs + B, slot, tfirst}, N, offs + B, vscan, vbase, counters + 1, mepi, stream)) != D3F_OK)
-        return rc;
-    if (!async) {
-        // The output size is data dependent (as for the reference op, whose output tensor is allocated after the
-        // computation): ONE host synchronisation here brings back M, the flags and the per-element counts; everything
-        // after it is sized by M instead of N.
-        D3F_HIP_TRY(hipMemcpyAsync(status_host, meta, (B + 2) * sizeof(int), hipMemcpyDeviceToHost, stream));
-        D3F_HIP_TRY(hipStreamSynchronize(stream));
-        M = status_host[0];
-        if (status_host[1] != 0 || M <= 0) return D3F_OK;  // flags are reported to the caller; nothing more to compute
-        maxM = 0;
-        for (int b = 0; b < B; ++b) maxM = status_host[2 + b] > maxM ? status_host[2 + b] : maxM;
-    } else {
-        M = N < M_cap ? N : M_cap;   // upper bound: voxels <= points, and the caller promises <= M_cap (checked on device)
-        maxM = elem_cap;             // ... and <= elem_cap in any one element: the order rounds are launched for that
-    }
+};
 
-    gs_chain_kernel<<<nblk, 256, 0, stream>>>(N, slot, tfirst, tkey, vscan, vbase, pvid, vkey, vhead, vcnt, pnext, offs + B);
-    D3F_LAUNCH_CHECK();
-    if ((rc = d3f_scan_fold_launch(D3fScanIn{vcnt}, async ? N : M, meta, vstart, sbase, counters + 2, D3fNoEpi{}, stream)) != D3F_OK)
-        return rc;
-    gs_rank_kernel<<<nblk, 256, 0, stream>>>(N, offs + B, pvid, vhead, pnext, vstart, sbase, sorted);
-    }
-    // ---- libstdc++ iteration order ----
-    // Rounds > GS_SMALL_LAST are spread grid-wide.  (Keeping ALL rounds in the single workgroup per element saves ~50 launches
-    // per fragment but was measured slower end to end, 580 vs 640 fragments/s: the serial rounds of the 30 k-voxel stage sit
-    // on every fragment's critical path and four fragments in flight do not hide them.)
-    const int small_last = GS_SMALL_LAST;
-    gs_order_small_kernel<<<B, GS_SMALL_T, 0, stream>>>(A, small_last);
-    for (int j = small_last + 1; j < D3F_NCHAIN && (long long)D3F_CHAIN_HOST[j - 1] < (long long)maxM; ++j) {
+// ---- libstdc++ iteration order of every element's voxel keys (W.A.vkey -> W.A.vpos), for elements of up to maxM voxels ----
+// Rounds 0 .. GS_SMALL_LAST in one workgroup per element, the rounds after them spread grid-wide.  (Keeping ALL rounds in the
+// single workgroup per element saves ~50 launches per fragment but was measured slower end to end, 580 vs 640 fragments/s: the
+// serial rounds of the 30 k-voxel stage sit on every fragment's critical path and four fragments in flight do not hide them.)
+static int gs_order_launch(const GsWork& W, int B, int maxM, hipStream_t stream) {
+    gs_order_small_kernel<<<B, GS_SMALL_T, 0, stream>>>(W.A);
+    for (int j = GS_SMALL_LAST + 1; j < D3F_NCHAIN && (long long)D3F_CHAIN_HOST[j - 1] < (long long)maxM; ++j) {
         const long long nbj = (long long)D3F_CHAIN_HOST[j];
         const int hi = (int)((long long)maxM < nbj ? (long long)maxM : nbj);
         // the place kernel of a round also inserts the next round (when there is one): its grid covers that round's positions
@@ -1052,23 +903,155 @@ static int gs_run(const float* points, int N, const int* lens_dev, int B, float 
         const long long nbn = more ? (long long)D3F_CHAIN_HOST[j + 1] : 0;
         const int hin = more ? (int)((long long)maxM < nbn ? (long long)maxM : nbn) : hi;
         dim3 g(d3f_cdiv(hi, 256), B), gt(d3f_cdiv(hi, GS_TILE), B), gp(d3f_cdiv(hin > hi ? hin : hi, 256), B);
-        if (j == small_last + 1) gs_order_insert_kernel<<<g, 256, 0, stream>>>(A, j);
-        gs_order_scan_tiles_kernel<<<gt, 256, 0, stream>>>(A, j, B, counters + 4 + j * B);
-        gs_order_place_kernel<<<gp, 256, 0, stream>>>(A, j);
-    }
-    if (use_sort)
-        if (bbox_out) gs_emit_kernel<true><<<d3f_cdiv(M, 1024), 1024, 0, stream>>>(meta, moffs, B, A.vpos, bary, sub_points, M_cap, bbox_out);
-        else gs_emit_kernel<false><<<d3f_cdiv(M, 256), 256, 0, stream>>>(meta, moffs, B, A.vpos, bary, sub_points, M_cap, nullptr);
-    else
-        gs_accum_kernel<<<d3f_cdiv(async ? N : M, 256), 256, 0, stream>>>(points, features, fdim, meta, moffs, B, vstart, sbase,
-                                                                         vcnt, sorted, A.vpos, sub_points, sub_features, M_cap);
-    if (ldim > 0) {
-        const size_t tot = (size_t)M * (size_t)ldim;
-        gs_fill_kernel<<<d3f_cdiv((long long)tot, 256), 256, 0, stream>>>(sub_classes, tot, (int)0x80000000);
-        gs_labels_kernel<<<nblk, 256, 0, stream>>>(N, ldim, classes, pvid, moffs, B, A.vpos, sub_classes);
+        if (j == GS_SMALL_LAST + 1) gs_order_insert_kernel<<<g, 256, 0, stream>>>(W.A, j);
+        gs_order_scan_tiles_kernel<<<gt, 256, 0, stream>>>(W.A, j, B, W.counters + 4 + j * B);
+        gs_order_place_kernel<<<gp, 256, 0, stream>>>(W.A, j);
     }
     D3F_LAUNCH_CHECK();
     return D3F_OK;
+}
+
+// ---- sort form (capacity mode, points only): see gs_sortkey_kernel ----------------------------------------------------------
+// reset (+ grid geometry from finished boxes) | reset -> boxes + geometry -> keys -> radix sort -> run heads -> voxel-id scan
+// (offsets / lengths / status in its last workgroup) -> runs -> iteration order -> emit.  No host round trip: N and M_cap are
+// capacities, the real sizes live in HBM and every kernel bounds itself by them.
+static int gs_run_sort(const GsCall& C, const GsWork& W, int elem_cap) {
+    const int N = C.N, B = C.B;
+    const size_t n = (size_t)N;
+    hipStream_t stream = C.stream;
+    int rc;
+    // (only the first-occurrence bits and the status words need clearing)
+    const D3fFill none{nullptr, 0ull, 0u};
+    const D3fFill fill_bits{W.fbits, (unsigned long long)(n / 32 + 2), 0u};
+    const D3fFill fill_meta{(unsigned*)W.meta, (unsigned long long)(B + 2), 0u};
+    if (C.bbox_in) {
+        // finished boxes: no pass over the points, the grid geometry is derived by the reset launch itself
+        long long blocks = (long long)(fill_bits.n / 4 / 256) + 1;
+        if (blocks > 1024) blocks = 1024;
+        gs_begin_boxed_kernel<<<(int)blocks, 256, 0, stream>>>(C.lens_dev, B, W.offs, C.bbox_in, W.counters, W.ncounters, fill_bits,
+                                                               fill_meta, C.dl, W.el, W.meta, W.smeta, N);
+        D3F_LAUNCH_CHECK();
+    } else {
+        if ((rc = d3f_begin_launch(C.lens_dev, B, W.offs, W.bbox, W.counters, W.ncounters, fill_bits, fill_meta, none, none,
+                                   stream)) != D3F_OK)
+            return rc;
+        GsPrepEpi prep{W.bbox, W.offs, B, C.dl, W.el, W.meta, W.smeta, N};
+        if ((rc = d3f_bbox_launch_t(C.points, W.offs, B, N, W.bbox, W.counters, prep, stream, C.ptrs)) != D3F_OK) return rc;
+    }
+    const int nblk = d3f_cdiv(N, 256);
+    // storage reuse: sort keys in slot / pnext, point indices in pvid / sorted, word scan in vscan / vbase
+    unsigned *key0 = (unsigned*)W.slot, *key1 = (unsigned*)W.pnext, *val0 = (unsigned*)W.pvid, *val1 = (unsigned*)W.sorted;
+    gs_sortkey_kernel<<<rs_tiles(N), RS_THREADS, 0, stream>>>(C.points, C.ptrs, W.offs, B, C.dl, W.el, W.smeta, key0, W.rs_hist,
+                                                              W.meta);
+    D3F_LAUNCH_CHECK();
+    if ((rc = rs_sort_launch(W.smeta, N, key0, key1, val0, val1, W.rs_hist, stream)) != D3F_OK) return rc;
+    gs_heads_kernel<<<nblk, 256, 0, stream>>>(N, W.smeta, key0, key1, val0, val1, W.fbits);
+    D3F_LAUNCH_CHECK();
+    const GsRankBits rank{W.fbits, W.vscan, W.vbase};
+    GsMoffsEpi<GsRankBits> mepi{W.offs, B, rank, W.meta, W.moffs, C.sub_lens_dev, C.status_dev, C.M_cap, elem_cap};
+    if ((rc = d3f_scan_fold_launch(GsBitsIn{W.fbits}, N / 32 + 1, nullptr, W.vscan, W.vbase, W.counters + 1, mepi, stream)) != D3F_OK)
+        return rc;
+    gs_runs_kernel<<<nblk, 256, 0, stream>>>(N, W.smeta, key0, key1, val0, val1, rank, C.points, C.ptrs, W.offs, W.vkey, W.bary);
+    D3F_LAUNCH_CHECK();
+    // upper bounds: voxels <= points, and the caller promises <= M_cap (checked on the device) and <= elem_cap in any one element
+    const int M = N < C.M_cap ? N : C.M_cap;
+    if ((rc = gs_order_launch(W, B, elem_cap, stream)) != D3F_OK) return rc;
+    if (C.bbox_out)
+        gs_emit_kernel<true><<<d3f_cdiv(M, 1024), 1024, 0, stream>>>(W.meta, W.moffs, B, W.A.vpos, W.bary, C.sub_points, C.M_cap,
+                                                                     C.bbox_out);
+    else
+        gs_emit_kernel<false><<<d3f_cdiv(M, 256), 256, 0, stream>>>(W.meta, W.moffs, B, W.A.vpos, W.bary, C.sub_points, C.M_cap,
+                                                                    nullptr);
+    D3F_LAUNCH_CHECK();
+    return D3F_OK;
+}
+
+// ---- hash form (features / classes, and every synchronous call) -------------------------------------------------------------
+// 9 + 3 * rounds launches: reset -> boxes (+ grid geometry) -> keys / hash insert -> voxel-id scan (first-occurrence flags
+// fused in, per-element offsets / lengths / status in its last workgroup) -> chains -> start scan -> in-chain rank -> iteration
+// order -> in-order accumulation (-> labels).
+// sync mode (status_host != NULL): ONE host synchronisation after the voxel count is known, everything after it sized by M.
+// async mode (status_dev != NULL): no host round trip, as the sort form.
+static int gs_run_hash(const GsCall& C, const GsWork& W, int elem_cap) {
+    const int N = C.N, B = C.B;
+    const size_t n = (size_t)N;
+    const bool async = C.status_dev != nullptr;
+    hipStream_t stream = C.stream;
+    int rc;
+    const D3fFill none{nullptr, 0ull, 0u};
+    const unsigned long long ones_words = (unsigned long long)((char*)(W.vhead + n) - (char*)W.tkey) / 4ull;
+    const unsigned long long zero_words = (unsigned long long)((char*)(W.vcnt + n) - (char*)W.meta) / 4ull;
+    if ((rc = d3f_begin_launch(C.lens_dev, B, W.offs, W.bbox, W.counters, W.ncounters, D3fFill{(unsigned*)W.tkey, ones_words, 0xFFFFFFFFu},
+                               D3fFill{(unsigned*)W.meta, zero_words, 0u}, none, none, stream)) != D3F_OK)
+        return rc;
+    GsPrepEpi prep{W.bbox, W.offs, B, C.dl, W.el, W.meta, nullptr, N};
+    if ((rc = d3f_bbox_launch_t(C.points, W.offs, B, N, W.bbox, W.counters, prep, stream, C.ptrs)) != D3F_OK) return rc;
+    const int nblk = d3f_cdiv(N, 256);
+    GsMoffsEpi<GsRankScan> mepi{W.offs, B, GsRankScan{W.vscan, W.vbase}, W.meta, W.moffs, C.sub_lens_dev, C.status_dev, C.M_cap,
+                                async ? elem_cap : 0x7fffffff};
+    gs_insert_kernel<<<nblk, 256, 0, stream>>>(C.points, N, W.offs, B, C.dl, W.el, W.tkey, W.tfirst, (unsigned long long)W.L.cap - 1ull,
+                                               W.slot, W.meta);
+    D3F_LAUNCH_CHECK();
+    if ((rc = d3f_scan_fold_launch(GsMarkIn{W.offs + B, W.slot, W.tfirst}, N, W.offs + B, W.vscan, W.vbase, W.counters + 1, mepi,
+                                   stream)) != D3F_OK)
+        return rc;
+    int M, maxM;       // sizes of the voxel-indexed launches
+    if (!async) {
+        // The output size is data dependent (as for the reference op, whose output tensor is allocated after the
+        // computation): ONE host synchronisation here brings back M, the flags and the per-element counts; everything
+        // after it is sized by M instead of N.
+        D3F_HIP_TRY(hipMemcpyAsync(C.status_host, W.meta, (B + 2) * sizeof(int), hipMemcpyDeviceToHost, stream));
+        D3F_HIP_TRY(hipStreamSynchronize(stream));
+        M = C.status_host[0];
+        if (C.status_host[1] != 0 || M <= 0) return D3F_OK;  // flags are reported to the caller; nothing more to compute
+        maxM = 0;
+        for (int b = 0; b < B; ++b) maxM = C.status_host[2 + b] > maxM ? C.status_host[2 + b] : maxM;
+    } else {
+        M = N < C.M_cap ? N : C.M_cap;   // upper bound: voxels <= points, and the caller promises <= M_cap (checked on device)
+        maxM = elem_cap;                 // ... and <= elem_cap in any one element: the order rounds are launched for that
+    }
+    gs_chain_kernel<<<nblk, 256, 0, stream>>>(N, W.slot, W.tfirst, W.tkey, W.vscan, W.vbase, W.pvid, W.vkey, W.vhead, W.vcnt, W.pnext,
+                                              W.offs + B);
+    D3F_LAUNCH_CHECK();
+    if ((rc = d3f_scan_fold_launch(D3fScanIn{W.vcnt}, async ? N : M, W.meta, W.vstart, W.sbase, W.counters + 2, D3fNoEpi{},
+                                   stream)) != D3F_OK)
+        return rc;
+    gs_rank_kernel<<<nblk, 256, 0, stream>>>(N, W.offs + B, W.pvid, W.vhead, W.pnext, W.vstart, W.sbase, W.sorted);
+    if ((rc = gs_order_launch(W, B, maxM, stream)) != D3F_OK) return rc;
+    gs_accum_kernel<<<d3f_cdiv(async ? N : M, 256), 256, 0, stream>>>(C.points, C.features, C.fdim, W.meta, W.moffs, B, W.vstart,
+                                                                     W.sbase, W.vcnt, W.sorted, W.A.vpos, C.sub_points,
+                                                                     C.sub_features, C.M_cap);
+    D3F_LAUNCH_CHECK();
+    if (C.ldim > 0) {
+        // classes start at INT_MIN, the labels kernel takes the maximum
+        if ((rc = d3f_fill_u32(C.sub_classes, (size_t)M * (size_t)C.ldim, 0x80000000u, stream)) != D3F_OK) return rc;
+        gs_labels_kernel<<<nblk, 256, 0, stream>>>(N, C.ldim, C.classes, W.pvid, W.moffs, B, W.A.vpos, C.sub_classes);
+        D3F_LAUNCH_CHECK();
+    }
+    return D3F_OK;
+}
+
+// Shared implementation: picks the form.  Capacity mode with points only takes the one-workgroup form when the caller's
+// capacities fit it, the sort form otherwise; everything else (features, classes, every synchronous call) the hash form.
+static int gs_run(const GsCall& C, int elem_cap, int elem_points, void* workspace, size_t workspace_bytes) {
+    const bool async = C.status_dev != nullptr;
+    const bool use_sort = async && !C.features && C.ldim == 0;
+    if (use_sort && !C.ptrs) {
+        // one workgroup per cloud: every cloud <= 16384 points and <= 5087 voxels (a cloud beyond its stated capacity is
+        // reported by either form, so the choice adds no failure mode)
+        const int pc = (elem_points > 0 && elem_points < C.N) ? elem_points : C.N;
+        int ec = (elem_cap > 0 && elem_cap < C.M_cap) ? elem_cap : C.M_cap;
+        if (ec > pc) ec = pc;
+        if (pc <= 16384 && ec <= GSS_NB_MAX)
+            return gs_run_small(C.points, C.N, C.lens_dev, C.B, C.dl, C.sub_points, C.M_cap, elem_cap, pc, C.sub_lens_dev, C.status_dev,
+                                workspace, workspace_bytes, C.stream, C.bbox_out);
+    }
+    GsWork W;
+    if (!W.carve(workspace, workspace_bytes, C.N, C.B, async ? C.M_cap : -1)) return D3F_ERR_WORKSPACE;
+    if (elem_cap <= 0 || elem_cap > C.M_cap) elem_cap = C.M_cap;
+    if (elem_cap > C.N) elem_cap = C.N;
+    W.A.max_m = async ? elem_cap : 0x7fffffff;   // capacity mode: the order rounds are launched for elements up to elem_cap
+    return use_sort ? gs_run_sort(C, W, elem_cap) : gs_run_hash(C, W, elem_cap);
 }
 
 extern "C" int d3f_batch_grid_subsample(const float* points, int N, const int* lens_dev, int B, float dl,
@@ -1081,49 +1064,42 @@ extern "C" int d3f_batch_grid_subsample(const float* points, int N, const int* l
     if ((fdim > 0 && (!features || !sub_features)) || (ldim > 0 && (!classes || !sub_classes))) return D3F_ERR_ARG;
     for (int i = 0; i < B + 2; ++i) status_host[i] = 0;
     if (N == 0) return d3f_fill_u32(sub_lens_dev, B, 0u, stream);
-    return gs_run(points, N, lens_dev, B, dl, features, fdim, classes, ldim, sub_points, N, N, 0, sub_features, sub_classes,
-                  sub_lens_dev, status_host, nullptr, workspace, workspace_bytes, stream);
+    const GsCall C{points, N, lens_dev, B, dl, features, fdim, classes, ldim, sub_points, N, sub_features, sub_classes, sub_lens_dev,
+                   status_host, nullptr, stream, nullptr, nullptr, nullptr};
+    return gs_run(C, N, 0, workspace, workspace_bytes);
 }
 
-extern "C" int d3f_batch_grid_subsample_async(const float* points, int N_cap, const int* lens_dev, int B, float dl,
-                                              float* sub_points, int M_cap, int elem_cap, int elem_points_cap, int* sub_lens_dev,
-                                              int* status_dev, void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (N_cap < 1 || N_cap > (1 << 30) || M_cap < 1 || elem_cap < 0 || elem_points_cap < 0 || B < 1 || B > D3F_MAX_BATCH || !(dl > 0.f))
-        return D3F_ERR_ARG;
-    if (!points || !lens_dev || !sub_points || !sub_lens_dev || !status_dev) return D3F_ERR_ARG;
-    return gs_run(points, N_cap, lens_dev, B, dl, nullptr, 0, nullptr, 0, sub_points, M_cap, elem_cap, elem_points_cap, nullptr,
-                  nullptr, sub_lens_dev, nullptr, status_dev, workspace, workspace_bytes, stream);
-}
-
-// The same call with the clouds read IN PLACE: cloud b is its own array clouds_dev[b] (f32[lens[b], 3], any address), nothing is
-// stacked.  N_cap bounds the SUM of the lengths (workspace and launch sizes).  What a replayed launch sequence needs to take its
-// inputs where the producer left them: the pointer table and the lengths are the only per-replay uploads.
-extern "C" int d3f_batch_grid_subsample_async_inplace(const float* const* clouds_dev, int N_cap, const int* lens_dev, int B, float dl,
-                                                      float* sub_points, int M_cap, int elem_cap, int* sub_lens_dev, int* status_dev,
-                                                      void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (N_cap < 1 || N_cap > (1 << 30) || M_cap < 1 || elem_cap < 0 || B < 1 || B > D3F_MAX_BATCH || !(dl > 0.f)) return D3F_ERR_ARG;
-    if (!clouds_dev || !lens_dev || !sub_points || !sub_lens_dev || !status_dev) return D3F_ERR_ARG;
-    return gs_run(nullptr, N_cap, lens_dev, B, dl, nullptr, 0, nullptr, 0, sub_points, M_cap, elem_cap, 0, nullptr, nullptr, sub_lens_dev,
-                  nullptr, status_dev, workspace, workspace_bytes, stream, clouds_dev);
-}
-
-// d3f_batch_grid_subsample_async / _inplace (clouds_dev != NULL: in place, `points` unused) with bounding boxes handed along the
-// pyramid: bbox_in_dev (optional) = the finished boxes of the input clouds, gathered by the kernel that wrote them -- the sort form
-// then makes no pass over the points to box them (the one-workgroup form boxes its cloud out of the loads it needs anyway);
-// bbox_out_dev (optional) = the boxes of the clouds this call writes, accumulated into pre-initialised words (d3f_geometry_reset).
+// Capacity mode.  `points` = the stacked clouds, or clouds_dev = the clouds read IN PLACE (exactly one of the two): cloud b is its
+// own array clouds_dev[b] (f32[lens[b], 3], any address), nothing is stacked, N_cap bounds the SUM of the lengths (workspace and
+// launch sizes) -- what a replayed launch sequence needs to take its inputs where the producer left them: the pointer table and
+// the lengths are the only per-replay uploads.  Bounding boxes handed along the pyramid: bbox_in_dev (optional) = the finished
+// boxes of the input clouds, gathered by the kernel that wrote them -- the sort form then makes no pass over the points to box
+// them (the one-workgroup form boxes its cloud out of the loads it needs anyway); bbox_out_dev (optional) = the boxes of the
+// clouds this call writes, accumulated into pre-initialised words (d3f_geometry_reset).
 extern "C" int d3f_batch_grid_subsample_async_boxed(const float* points, const float* const* clouds_dev, int N_cap, const int* lens_dev,
                                                     int B, float dl, float* sub_points, int M_cap, int elem_cap, int elem_points_cap,
                                                     int* sub_lens_dev, int* status_dev, const unsigned* bbox_in_dev,
                                                     unsigned* bbox_out_dev, void* workspace, size_t workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     if (N_cap < 1 || N_cap > (1 << 30) || M_cap < 1 || elem_cap < 0 || elem_points_cap < 0 || B < 1 || B > D3F_MAX_BATCH || !(dl > 0.f))
         return D3F_ERR_ARG;
     if ((!points && !clouds_dev) || (points && clouds_dev) || !lens_dev || !sub_points || !sub_lens_dev || !status_dev) return D3F_ERR_ARG;
-    return gs_run(points, N_cap, lens_dev, B, dl, nullptr, 0, nullptr, 0, sub_points, M_cap, elem_cap, clouds_dev ? 0 : elem_points_cap,
-                  nullptr, nullptr, sub_lens_dev, nullptr, status_dev, workspace, workspace_bytes, stream, clouds_dev, bbox_in_dev,
-                  bbox_out_dev);
+    const GsCall C{points, N_cap, lens_dev, B, dl, nullptr, 0, nullptr, 0, sub_points, M_cap, nullptr, nullptr, sub_lens_dev,
+                   nullptr, status_dev, (hipStream_t)stream_, clouds_dev, bbox_in_dev, bbox_out_dev};
+    return gs_run(C, elem_cap, clouds_dev ? 0 : elem_points_cap, workspace, workspace_bytes);
+}
+// the stacked clouds, no boxes
+extern "C" int d3f_batch_grid_subsample_async(const float* points, int N_cap, const int* lens_dev, int B, float dl,
+                                              float* sub_points, int M_cap, int elem_cap, int elem_points_cap, int* sub_lens_dev,
+                                              int* status_dev, void* workspace, size_t workspace_bytes, void* stream_) {
+    return d3f_batch_grid_subsample_async_boxed(points, nullptr, N_cap, lens_dev, B, dl, sub_points, M_cap, elem_cap, elem_points_cap,
+                                                sub_lens_dev, status_dev, nullptr, nullptr, workspace, workspace_bytes, stream_);
+}
+// the clouds in place, no boxes
+extern "C" int d3f_batch_grid_subsample_async_inplace(const float* const* clouds_dev, int N_cap, const int* lens_dev, int B, float dl,
+                                                      float* sub_points, int M_cap, int elem_cap, int* sub_lens_dev, int* status_dev,
+                                                      void* workspace, size_t workspace_bytes, void* stream_) {
+    return d3f_batch_grid_subsample_async_boxed(nullptr, clouds_dev, N_cap, lens_dev, B, dl, sub_points, M_cap, elem_cap, 0, sub_lens_dev,
+                                                status_dev, nullptr, nullptr, workspace, workspace_bytes, stream_);
 }
 
 // np.concatenate([pts, pts]) of the reference's test generators (datasets/ThreeDMatch.py:190-192, demo_registration.py:

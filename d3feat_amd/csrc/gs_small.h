@@ -7,7 +7,8 @@
 //   bounding box -> origin / grid (grid_subsampling.cpp:24-30) -> voxel keys (:49-59) -> stable LSD radix sort of (key, point)
 //   in LDS (wave-ballot ranking as in radix_sort.h; the tile is the whole cloud) -> run heads -> first-occurrence bits +
 //   popcount scan = voxel ids in insertion order -> the head of a run sums its points in input order (:63-70, :81-92) ->
-//   libstdc++ iteration-order rounds (closed form of grid_subsample.hip's header) on the voxel keys, all in LDS ->
+//   libstdc++ iteration-order rounds (closed form of grid_subsample.hip's header; gs_order_rounds_lds of gs_order.h, the body
+//   that gs_order_small_kernel runs too) on the voxel keys, all in LDS ->
 //   barycentres to the cloud's block of a staging buffer [B][elem_cap][3];
 //
 // a second, trivial launch packs the B blocks into the contiguous [M, 3] output and writes lengths / status (the offsets need
@@ -33,29 +34,6 @@ struct GsSmallArgs {
     int* cflags;           // [B] D3F_ST_* bits of each cloud (written, not accumulated: nothing to reset between calls)
     unsigned* bbox_out;    // optional [B][6]: the box of every cloud's barycentres (ordered-uint min xyz, max xyz; pre-initialised)
 };
-
-template <int T>
-__device__ __forceinline__ int gss_block_excl_scan(int v, int* __restrict__ wsum, int* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < T / 64; ++q) {
-        const int s = wsum[q];
-        if (q < w) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
 
 // LDS layout (dynamic), in 32-bit words:
 //   [0, 128)                   scratch: wave sums, box reduction; word 127 = the cloud's status bits
@@ -124,8 +102,7 @@ __global__ void __launch_bounds__(T) gs_small_kernel(GsSmallArgs A) {
         for (int d = 0; d < 3; ++d) {
             unsigned a = 0xFFFFFFFFu, c = 0u;
             for (int q = 0; q < W; ++q) { a = min(a, (unsigned)sScr[q * 6 + d]); c = max(c, (unsigned)sScr[q * 6 + 3 + d]); }
-            org[d] = __fmul_rn(floorf(__fmul_rn(d3f_ord2f(a), inv)), dl);
-            const float ext = fmaxf(floorf(__fdiv_rn(__fsub_rn(d3f_ord2f(c), org[d]), dl)), 0.f) + 1.0f;
+            const float ext = gs_axis(a, c, dl, inv, org[d]) + 1.0f;
             dims[d] = ext < 4294967040.f ? (unsigned)ext : 0xFFFFFFFFu;
         }
     }
@@ -153,11 +130,9 @@ __global__ void __launch_bounds__(T) gs_small_kernel(GsSmallArgs A) {
         key[r] = 0u;
         val[r] = (unsigned)i;
         if (i < len) {
-            const float fx = floorf(__fdiv_rn(__fsub_rn(P[3 * (size_t)i + 0], org[0]), dl));
-            const float fy = floorf(__fdiv_rn(__fsub_rn(P[3 * (size_t)i + 1], org[1]), dl));
-            const float fz = floorf(__fdiv_rn(__fsub_rn(P[3 * (size_t)i + 2], org[2]), dl));
-            if (fx < 0.f || fy < 0.f || fz < 0.f) st |= D3F_ST_NEG_CELL;
-            const unsigned ix = (unsigned)fmaxf(fx, 0.f), iy = (unsigned)fmaxf(fy, 0.f), iz = (unsigned)fmaxf(fz, 0.f);
+            float cx, cy, cz;
+            st |= gs_cell(P + 3 * (size_t)i, org[0], org[1], org[2], dl, cx, cy, cz);
+            const unsigned ix = (unsigned)cx, iy = (unsigned)cy, iz = (unsigned)cz;
             key[r] = ix + dims[0] * (iy + dims[1] * iz);       // < cells <= 2^32
         }
     }
@@ -183,30 +158,16 @@ __global__ void __launch_bounds__(T) gs_small_kernel(GsSmallArgs A) {
             }
             rank[r] = 0u;
             if (valid) {
-                const unsigned prev = myCnt[dg];
+                const unsigned prev = myCnt[dg];                                  // every peer reads the counter ...
                 const unsigned below = (unsigned)__popcll(peers & d3f_lanemask_lt());
                 rank[r] = prev + below;
                 __builtin_amdgcn_wave_barrier();
-                if (below == 0u) myCnt[dg] = prev + (unsigned)__popcll(peers);
+                if (below == 0u) myCnt[dg] = prev + (unsigned)__popcll(peers);    // ... then the lowest peer advances it
             }
             __builtin_amdgcn_wave_barrier();
         }
         __syncthreads();
-        {   // digit totals -> first position of each digit, then each wave's base inside the digit's run
-            int cnt = 0;
-            if (tid < 256)
-                for (int q = 0; q < W; ++q) cnt += (int)sCnt[q][tid];
-            int tot;
-            const int loc = gss_block_excl_scan<T>(tid < 256 ? cnt : 0, sScr, &tot);
-            if (tid < 256) {
-                unsigned run = (unsigned)loc;
-                for (int q = 0; q < W; ++q) {
-                    const unsigned c = sCnt[q][tid];
-                    sCnt[q][tid] = run;
-                    run += c;
-                }
-            }
-        }
+        rs_wave_bases<W>(sCnt, (unsigned*)sScr);   // digit totals -> first position of each digit -> each wave's base in its run
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -245,7 +206,7 @@ __global__ void __launch_bounds__(T) gs_small_kernel(GsSmallArgs A) {
             const int t = c0 + tid;
             const int c = (t < NI / 32) ? __popc(sBits[t]) : 0;
             int tot;
-            const int e = gss_block_excl_scan<T>(c, sScr, &tot);
+            const int e = d3f_block_excl_scan<T>(c, sScr, &tot);
             if (t < NI / 32) sWS[t] = carry + e;
             carry += tot;
         }
@@ -275,7 +236,7 @@ __global__ void __launch_bounds__(T) gs_small_kernel(GsSmallArgs A) {
                 sz = __fadd_rn(sz, P[3 * (size_t)pi + 2]);
                 ++c;
             }
-            const float sc = (float)(1.0 / (double)c);
+            const float sc = gs_inv_count(c);
             rec[vid] = make_float4(__fmul_rn(sx, sc), __fmul_rn(sy, sc), __fmul_rn(sz, sc), __uint_as_float(k));
         }
     }
@@ -293,55 +254,11 @@ __global__ void __launch_bounds__(T) gs_small_kernel(GsSmallArgs A) {
     int* sL1 = sL0 + NB;
     for (int v = tid; v < M; v += T) sKey[v] = __float_as_uint(rec[v].w);
     __syncthreads();
-    int* La = sL0;
-    int* Lb = sL1;
-    int lo_r = 0;
-    for (int j = 0; j < D3F_NCHAIN; ++j) {
-        const int nb = (int)D3F_CHAIN_DEV[j];
-        const double inv_nb = 1.0 / (double)nb;
-        const bool last = M <= nb;
-        const int hi = last ? M : nb;
-        for (int t = tid; t < nb; t += T) { sBF[t] = 0x7fffffff; sBC[t] = 0; sBH[t] = -1; }
-        __syncthreads();
-        for (int t = tid; t < hi; t += T) {
-            const int id = (t < lo_r) ? La[t] : t;
-            const int bk = gs_mod((unsigned long long)sKey[id], (unsigned)nb, inv_nb);
-            atomicMin(&sBF[bk], t);
-            atomicAdd(&sBC[bk], 1);
-            sNX[t] = atomicExch(&sBH[bk], t);
-        }
-        __syncthreads();
-        // reverse exclusive scan over positions of c[t] = (t first of its bucket) ? bucket size : 0; the value replaces the
-        // bucket's size (only its first position reads it)
-        int carry = 0;
-        for (int c0 = 0; c0 < hi; c0 += T) {
-            const int u = c0 + tid, t = hi - 1 - u;
-            int c = 0, bk = 0;
-            if (u < hi) {
-                const int id = (t < lo_r) ? La[t] : t;
-                bk = gs_mod((unsigned long long)sKey[id], (unsigned)nb, inv_nb);
-                c = (sBF[bk] == t) ? sBC[bk] : 0;
-            }
-            int tot;
-            const int e = gss_block_excl_scan<T>(c, sScr, &tot);
-            if (u < hi && sBF[bk] == t) sBC[bk] = carry + e;
-            carry += tot;
-        }
-        __syncthreads();
-        for (int t = tid; t < hi; t += T) {
-            const int id = (t < lo_r) ? La[t] : t;
-            const int bk = gs_mod((unsigned long long)sKey[id], (unsigned)nb, inv_nb);
-            int rk = 0;
-            for (int q = sBH[bk]; q >= 0; q = sNX[q]) rk += (q > t) ? 1 : 0;
-            const int dest = sBC[bk] + rk;
-            if (last) Lb[id] = dest;      // final round: the list buffer becomes the position table
-            else Lb[dest] = id;
-        }
-        __syncthreads();
-        int* tmp = La; La = Lb; Lb = tmp;
-        if (last) break;
-        lo_r = hi;
-    }
+    const GsOrderLds<unsigned> S{sKey, sBF, sBC, sBH, sNX, nullptr, nullptr, sL0, sL1, sScr};
+    int lo_r;
+    const int* La;
+    // (M <= nbmax: the last round is reached; it turns its list buffer into the position table)
+    gs_order_rounds_lds<T, unsigned, false>(S, M, D3F_NCHAIN - 1, [](int* Lb, int id, int dest) { Lb[id] = dest; }, lo_r, La);
     // La[v] = iteration-order position of voxel v
     float* __restrict__ out = A.stage + 3 * (size_t)b * (size_t)A.elem_cap;
     unsigned bmn[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, bmx[3] = {0u, 0u, 0u};

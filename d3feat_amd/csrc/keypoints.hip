@@ -80,13 +80,7 @@ __device__ __forceinline__ void topk_pick(const unsigned* hist, unsigned remaini
         unsigned h[4], s = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { h[j] = hist[255 - 4 * l - j]; s += h[j]; }
-        unsigned incl = s;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned v = __shfl_up(incl, off);
-            if (l >= off) incl += v;
-        }
-        unsigned above = incl - s;
+        unsigned above = d3f_wave_incl_scan(s) - s;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (above < remaining && remaining <= above + h[j]) { sel[0] = 255 - 4 * l - j; sel[1] = above; sel[2] = h[j]; }

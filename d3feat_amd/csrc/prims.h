@@ -9,6 +9,8 @@
 //   * scan_fold_kernel<In, Epi>  exclusive scan in ONE launch: every workgroup scans its 1024-item tile (`local`), the last
 //                       workgroup to finish scans the tile sums into `base` and runs an epilogue with the grand total.
 //                       Consumers read  local[i] + base[i / D3F_SCAN_TILE]  (d3f_scan_at) instead of a third "add" pass.
+//   * d3f_block_excl_scan<T>  the exclusive scan over the T threads of a workgroup that every scanning kernel calls (on top of
+//                       d3f_wave_incl_scan, common.h).
 // Inter-workgroup hand-off ("last workgroup") follows cdna_hip_programming.md G16: every workgroup's stores, then
 // __syncthreads, then one lane: agent-scope release fence + s_waitcnt + device-scope atomic ticket; the last arriver
 // issues an agent-scope acquire fence before its (first-touch) reads of the other workgroups' results.
@@ -260,21 +262,20 @@ __device__ __forceinline__ T d3f_block_sum(T v, T* red) {
 }
 
 // ---- one-launch exclusive scan --------------------------------------------------------------------------------------
-__device__ __forceinline__ int d3f_block_excl_scan_256(int v, int* lds4, int* total) {
+// Exclusive scan of v over the T threads of the workgroup (all of them call this), the grand total in every thread: wave scan
+// (d3f_wave_incl_scan), wave sums in wsum[T / 64] (LDS), every thread adds up the waves before its own.  The second barrier
+// frees wsum, so calls may follow one another.
+template <int T>
+__device__ __forceinline__ int d3f_block_excl_scan(int v, int* wsum, int* total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds4[w] = x;
+    const int x = d3f_wave_incl_scan(v);
+    if (lane == 63) wsum[w] = x;
     __syncthreads();
     int base = 0, tot = 0;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int s = lds4[i];
-        if (i < w) base += s;
+    for (int q = 0; q < T / 64; ++q) {
+        const int s = wsum[q];
+        if (q < w) base += s;
         tot += s;
     }
     __syncthreads();
@@ -305,7 +306,7 @@ __global__ void __launch_bounds__(256) scan_fold_kernel(In in, int n, const int*
         s += v[k];
     }
     int tot;
-    int ex = d3f_block_excl_scan_256(s, lds, &tot);
+    int ex = d3f_block_excl_scan<256>(s, lds, &tot);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (i0 + k < n) local[i0 + k] = ex;
@@ -319,7 +320,7 @@ __global__ void __launch_bounds__(256) scan_fold_kernel(In in, int n, const int*
         const int i = c + threadIdx.x;
         const int x = (i < nblocks) ? __hip_atomic_load(&base[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
         int t;
-        const int e = d3f_block_excl_scan_256(x, lds, &t);
+        const int e = d3f_block_excl_scan<256>(x, lds, &t);
         if (i < nblocks) base[i] = carry + e;
         carry += t;
     }

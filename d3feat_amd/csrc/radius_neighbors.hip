@@ -261,13 +261,8 @@ __global__ void __launch_bounds__(NBX_SMALL_T) nbx_small_kernel(const float* __r
     const int j0 = min(tid * per_t, nc), j1 = min(j0 + per_t, nc);
     int sum = 0;
     for (int j = j0; j < j1; ++j) sum += sCnt[j];
-    int x = sum;
+    const int x = d3f_wave_incl_scan(sum);
     const int lane = tid & 63, w = tid >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
     if (lane == 63) sW[w] = x;
     __syncthreads();
     int run = lo + x - sum;

@@ -12,7 +12,8 @@
 //   * rs_scatter_kernel: every workgroup sums the columns of the (tiles x 256) matrix itself -- everything before its own
 //     tile and the column totals; wave w takes rows w, w + 8, ..., one 16-byte load per lane = one 1 KB row per instruction,
 //     8 rows in flight (a thread-per-column loop was 73 dependent L2 round trips: 168 us for 1.2 M items) -- which replaces a
-//     separate scan launch and any cross-workgroup hand-off; digit bases by one 256-wide scan.  Ranking is wave-local and stable: a wave owns 1024
+//     separate scan launch and any cross-workgroup hand-off; digit bases by one 256-wide scan (rs_wave_bases, shared with the
+//     one-workgroup subsampler gs_small.h; the wave scan is d3f_wave_incl_scan of common.h).  Ranking is wave-local and stable: a wave owns 1024
 //     consecutive items and walks them in 16 rounds of 64; the lanes of a round that hold the same digit find each other
 //     with 8 wavefront ballots (one per digit bit), rank = popcount of the peers below, and the per-wave digit counter in
 //     LDS advances by the peer count (the wave's LDS accesses are in program order: all peers read the counter, then the
@@ -52,6 +53,37 @@ __device__ __forceinline__ void rs_tile_histogram(const unsigned (&key)[RS_ROUND
         if (valid_mask & (1u << r)) atomicAdd(&sHist[(key[r] >> shift) & 255u], 1u);
     __syncthreads();
     if (threadIdx.x < 256) hist_row[threadIdx.x] = sHist[threadIdx.x];
+}
+
+// Digit totals of the W waves' counters -> first position of each digit inside the tile -> sCnt[q][d] = position of wave q's
+// first item of digit d.  Called by the whole workgroup (>= 256 threads) after a barrier behind the wave-local ranking, and followed by
+// one before sCnt is read; sScan: one word of LDS per wave.  Returns the first tile position of digit threadIdx.x (< 256).
+template <int W>
+__device__ __forceinline__ unsigned rs_wave_bases(unsigned (*sCnt)[256], unsigned* sScan) {
+    const int tid = threadIdx.x, w = tid >> 6;
+    unsigned cnt = 0u;
+    if (tid < 256) {
+#pragma unroll
+        for (int q = 0; q < W; ++q) cnt += sCnt[q][tid];
+    }
+    const unsigned x = d3f_wave_incl_scan(cnt);
+    if ((tid & 63) == 63) sScan[w] = x;
+    __syncthreads();
+    unsigned loc = 0u;
+    if (tid < 256) {
+        unsigned wb = 0u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) wb += (q < w) ? sScan[q] : 0u;
+        loc = wb + x - cnt;
+        unsigned run = loc;
+#pragma unroll
+        for (int q = 0; q < W; ++q) {
+            const unsigned c = sCnt[q][tid];
+            sCnt[q][tid] = run;
+            run += c;
+        }
+    }
+    return loc;
 }
 
 __global__ void __launch_bounds__(RS_THREADS) rs_hist_kernel(const RsMeta* __restrict__ meta, int pass,
@@ -144,12 +176,7 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter_kernel(const RsMeta* __
 #pragma unroll
             for (int q = 0; q < RS_WAVES; ++q) { total += sCnt[q][tid]; before += sPart[q][tid]; }
         }
-        unsigned x = total;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned y = (unsigned)__shfl_up((int)x, d, 64);
-            if (lane >= d) x += y;
-        }
+        const unsigned x = d3f_wave_incl_scan(total);
         if (lane == 63) sScan[w] = x;
         __syncthreads();
 #pragma unroll
@@ -193,33 +220,8 @@ __global__ void __launch_bounds__(RS_THREADS) rs_scatter_kernel(const RsMeta* __
     // contiguous run in memory (32 items on average for an 8192-item tile = one 128-byte line).
     //   position inside the tile  p = locbase[digit] + (waves before)[digit] + rank;   memory position = p + delta[digit]
     {
-        unsigned cnt = 0u;
-        if (tid < 256) {
-#pragma unroll
-            for (int q = 0; q < RS_WAVES; ++q) cnt += sCnt[q][tid];
-        }
-        unsigned x = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned y = (unsigned)__shfl_up((int)x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) sScan[w] = x;
-        __syncthreads();
-        if (tid < 256) {
-            unsigned wb = 0u;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) wb += (q < w) ? sScan[q] : 0u;
-            const unsigned loc = wb + x - cnt;            // first tile position of digit tid
-            unsigned run = loc;
-#pragma unroll
-            for (int q = 0; q < RS_WAVES; ++q) {
-                const unsigned c = sCnt[q][tid];
-                sCnt[q][tid] = run;
-                run += c;
-            }
-            sBase[tid] -= loc;                            // delta (mod 2^32)
-        }
+        const unsigned loc = rs_wave_bases<RS_WAVES>(sCnt, sScan);
+        if (tid < 256) sBase[tid] -= loc;                 // delta (mod 2^32)
     }
     __syncthreads();
 #pragma unroll

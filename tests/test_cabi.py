@@ -117,6 +117,42 @@ def test_registration_entry_points_refuse_bad_arguments_without_a_gpu(lib):
     assert lib.d3f_mutual_matches(p, 10, p, 10, p, None, p, 4096, None) == -3                  # count_dev == NULL
 
 
+def test_capacity_mode_subsample_entry_points_refuse_bad_arguments_without_a_gpu(lib):
+    """d3f_batch_grid_subsample_async, _async_inplace and _async_boxed share one argument check: each of them answers D3F_ERR_ARG
+    for every argument it rejects, before anything touches the device.  Every case is a valid call with ONE argument spoilt (a
+    valid call is never made: it would launch)."""
+    buf = ctypes.create_string_buffer(4096)
+    p = ctypes.addressof(buf)
+    good = dict(points=p, clouds=None, N_cap=1000, lens=p, B=2, dl=0.05, sub=p, M_cap=500, elem_cap=300, elem_points_cap=600,
+                sub_lens=p, status=p, bbox_in=None, bbox_out=None)
+
+    def stacked(a):
+        return lib.d3f_batch_grid_subsample_async(a["points"], a["N_cap"], a["lens"], a["B"], a["dl"], a["sub"], a["M_cap"],
+                                                  a["elem_cap"], a["elem_points_cap"], a["sub_lens"], a["status"], p, 4096, None)
+
+    def inplace(a):
+        return lib.d3f_batch_grid_subsample_async_inplace(a["points"], a["N_cap"], a["lens"], a["B"], a["dl"], a["sub"], a["M_cap"],
+                                                          a["elem_cap"], a["sub_lens"], a["status"], p, 4096, None)
+
+    def boxed(a):
+        return lib.d3f_batch_grid_subsample_async_boxed(a["points"], a["clouds"], a["N_cap"], a["lens"], a["B"], a["dl"], a["sub"],
+                                                        a["M_cap"], a["elem_cap"], a["elem_points_cap"], a["sub_lens"], a["status"],
+                                                        a["bbox_in"], a["bbox_out"], p, 4096, None)
+
+    common = [("N_cap", 0), ("N_cap", -5), ("N_cap", (1 << 30) + 1), ("M_cap", 0), ("M_cap", -1), ("elem_cap", -1), ("B", 0),
+              ("B", 256), ("dl", 0.0), ("dl", -0.05), ("dl", float("nan")), ("points", None), ("lens", None), ("sub", None),
+              ("sub_lens", None), ("status", None)]
+    for entry, extra in ((stacked, [("elem_points_cap", -1)]), (inplace, []), (boxed, [("elem_points_cap", -1)])):
+        for name, bad in common + extra:      # (`points` is the first argument: the pointer table of the in-place entry)
+            assert entry(dict(good, **{name: bad})) == -3, (entry.__name__, name, bad)
+    # the boxed entry takes the stacked clouds or the pointer table: exactly one of the two
+    assert boxed(dict(good, clouds=p)) == -3
+    assert boxed(dict(good, points=None, clouds=None)) == -3
+    for name, bad in common:
+        if name != "points":
+            assert boxed(dict(good, points=None, clouds=p, **{name: bad})) == -3, ("boxed, in place", name, bad)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from d3feat_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
