@@ -110,6 +110,10 @@ SIGNATURES = {
     "d3f_neighbor_transpose": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "d3f_detect_head_backward_workspace_bytes": (_sz, [_i, _i, _i]),
     "d3f_detect_head_backward": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _sz, _vp]),
+    "d3f_neighbor_transpose_qs": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3f_kpconv_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "d3f_kpconv_backward": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _f, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp,
+                                 _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "d3f_pose_errors": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_sanitize_descriptors": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "d3f_matching_summary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -1204,3 +1204,6 @@ extern "C" int d3f_kpconv_aggregate(const float* q, int Nq, const float* s, int 
     D3F_LAUNCH_CHECK();
     return D3F_OK;
 }
+
+// ---- the backward of the operator above (d3f_kpconv_backward) --------------------------------------------------------------------
+#include "kp_backward.h"

@@ -18,17 +18,11 @@ namespace {
 // histogram + the sort's description), RS_MAX_PASSES scatter and RS_MAX_PASSES - 1 histogram launches (passes above the
 // significant bits of n return at once), and one finishing kernel -- nine, whatever N, K and B are.
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RS_THREADS) nt_keys_kernel(const int* __restrict__ idx, int N, int ld_idx, int K,
-                                                             const int* __restrict__ lens, int B, RsMeta* __restrict__ meta,
-                                                             unsigned* __restrict__ key0, unsigned* __restrict__ hist) {
-    __shared__ unsigned sHist[256];
-    __shared__ int sN;
-    if (threadIdx.x == 0) sN = 0;
-    __syncthreads();
-    if ((int)threadIdx.x < B) atomicAdd(&sN, max(lens[threadIdx.x], 0));       // (integers: any order gives the same sum)
-    __syncthreads();
-    const int n = min(max(sN, 0), N);
-    const int items = n * K;                                                    // N * K <= 2^31 - RS_TILE: checked by the launcher
+// the keys of one tile, written once for both tables: nq rows name, rows 0 .. ns - 1 are named (the square table: nq == ns == n)
+__device__ __forceinline__ void nt_keys_tile(const int* __restrict__ idx, int nq, int ns, int ld_idx, int K, RsMeta* __restrict__ meta,
+                                             unsigned* __restrict__ key0, unsigned* __restrict__ hist, unsigned* sHist) {
+    const int n = ns;
+    const int items = nq * K;                                                   // N * K <= 2^31 - RS_TILE: checked by the launcher
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         RsMeta m;
         m.n = items;
@@ -55,6 +49,28 @@ __global__ void __launch_bounds__(RS_THREADS) nt_keys_kernel(const int* __restri
         }
     }
     rs_tile_histogram(key, vm, 0, sHist, hist + (size_t)tile * 256);
+}
+
+__global__ void __launch_bounds__(RS_THREADS) nt_keys_kernel(const int* __restrict__ idx, int N, int ld_idx, int K,
+                                                             const int* __restrict__ lens, int B, RsMeta* __restrict__ meta,
+                                                             unsigned* __restrict__ key0, unsigned* __restrict__ hist) {
+    __shared__ unsigned sHist[256];
+    __shared__ int sN;
+    if (threadIdx.x == 0) sN = 0;
+    __syncthreads();
+    if ((int)threadIdx.x < B) atomicAdd(&sN, max(lens[threadIdx.x], 0));       // (integers: any order gives the same sum)
+    __syncthreads();
+    const int n = min(max(sN, 0), N);
+    nt_keys_tile(idx, n, n, ld_idx, K, meta, key0, hist, sHist);
+}
+
+// the rectangular table (d3f_neighbor_transpose_qs): nq query rows name ns support rows, both read on the device
+__global__ void __launch_bounds__(RS_THREADS) nt_keys_qs_kernel(const int* __restrict__ idx, int Nq, int ld_idx, int K,
+                                                                const int* __restrict__ Nq_dev, int Ns, const int* __restrict__ Ns_dev,
+                                                                RsMeta* __restrict__ meta, unsigned* __restrict__ key0,
+                                                                unsigned* __restrict__ hist) {
+    __shared__ unsigned sHist[256];
+    nt_keys_tile(idx, max(d3f_dyn(Nq, Nq_dev), 0), max(d3f_dyn(Ns, Ns_dev), 0), ld_idx, K, meta, key0, hist, sHist);
 }
 
 // thread t < items: sorted position t -> edges[t] (valid edges only; they come first).  thread j <= N: start[j] = the first sorted
@@ -90,6 +106,30 @@ extern "C" size_t d3f_neighbor_transpose_workspace_bytes(int N, int K) {
     return 4 * d3f_align(items * 4) + d3f_align(rs_hist_words((int)items) * 4) + d3f_align(sizeof(RsMeta));
 }
 
+// the sort and the finishing kernel behind a key kernel: shared by both tables.  rows: the capacity of the named side (start has
+// rows + 1 entries); items: the slots of the index matrix
+struct NtBuffers {
+    unsigned *key0, *key1, *val0, *val1, *hist;
+    RsMeta* meta;
+};
+static inline bool nt_take(D3fArena& ar, int items, NtBuffers& b) {
+    b.key0 = ar.take<unsigned>(items);
+    b.key1 = ar.take<unsigned>(items);
+    b.val0 = ar.take<unsigned>(items);
+    b.val1 = ar.take<unsigned>(items);
+    b.hist = ar.take<unsigned>(rs_hist_words(items));
+    b.meta = ar.take<RsMeta>(1);
+    return ar.ok;
+}
+static inline int nt_sort_finish(const NtBuffers& b, int items, int rows, int* start, int* edges, hipStream_t stream) {
+    const int rc = rs_sort_launch(b.meta, items, b.key0, b.key1, b.val0, b.val1, b.hist, stream);
+    if (rc != D3F_OK) return rc;
+    const long long threads = items > rows + 1 ? (long long)items : (long long)rows + 1;
+    nt_finish_kernel<<<d3f_cdiv(threads, 256), 256, 0, stream>>>(b.meta, rows, b.key0, b.key1, b.val0, b.val1, start, edges);
+    D3F_LAUNCH_CHECK();
+    return D3F_OK;
+}
+
 extern "C" int d3f_neighbor_transpose(const int* idx, int N, int ld_idx, int K, const int* lens_dev, int B, int* start, int* edges,
                                       void* workspace, size_t workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
@@ -98,21 +138,26 @@ extern "C" int d3f_neighbor_transpose(const int* idx, int N, int ld_idx, int K, 
     if (!start || !lens_dev || (items > 0 && (!edges || !idx))) return D3F_ERR_ARG;
     if (!workspace || workspace_bytes < d3f_neighbor_transpose_workspace_bytes(N, K)) return D3F_ERR_WORKSPACE;
     D3fArena ar(workspace, workspace_bytes);
-    unsigned* key0 = ar.take<unsigned>(items);
-    unsigned* key1 = ar.take<unsigned>(items);
-    unsigned* val0 = ar.take<unsigned>(items);
-    unsigned* val1 = ar.take<unsigned>(items);
-    unsigned* hist = ar.take<unsigned>(rs_hist_words(items));
-    RsMeta* meta = ar.take<RsMeta>(1);
-    if (!ar.ok) return D3F_ERR_WORKSPACE;
-    nt_keys_kernel<<<rs_tiles(items), RS_THREADS, 0, stream>>>(idx, N, ld_idx, K, lens_dev, B, meta, key0, hist);
+    NtBuffers b;
+    if (!nt_take(ar, items, b)) return D3F_ERR_WORKSPACE;
+    nt_keys_kernel<<<rs_tiles(items), RS_THREADS, 0, stream>>>(idx, N, ld_idx, K, lens_dev, B, b.meta, b.key0, b.hist);
     D3F_LAUNCH_CHECK();
-    const int rc = rs_sort_launch(meta, items, key0, key1, val0, val1, hist, stream);
-    if (rc != D3F_OK) return rc;
-    const long long threads = items > N + 1 ? (long long)items : (long long)N + 1;
-    nt_finish_kernel<<<d3f_cdiv(threads, 256), 256, 0, stream>>>(meta, N, key0, key1, val0, val1, start, edges);
+    return nt_sort_finish(b, items, N, start, edges, stream);
+}
+
+extern "C" int d3f_neighbor_transpose_qs(const int* idx, int Nq, int ld_idx, int K, const int* Nq_dev, int Ns, const int* Ns_dev,
+                                         int* start, int* edges, void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!nt_sizes_ok(Nq, K) || Ns < 0 || ld_idx < K) return D3F_ERR_ARG;
+    const int items = Nq * K;
+    if (!start || (items > 0 && (!edges || !idx))) return D3F_ERR_ARG;
+    if (!workspace || workspace_bytes < d3f_neighbor_transpose_workspace_bytes(Nq, K)) return D3F_ERR_WORKSPACE;
+    D3fArena ar(workspace, workspace_bytes);
+    NtBuffers b;
+    if (!nt_take(ar, items, b)) return D3F_ERR_WORKSPACE;
+    nt_keys_qs_kernel<<<rs_tiles(items), RS_THREADS, 0, stream>>>(idx, Nq, ld_idx, K, Nq_dev, Ns, Ns_dev, b.meta, b.key0, b.hist);
     D3F_LAUNCH_CHECK();
-    return D3F_OK;
+    return nt_sort_finish(b, items, Ns, start, edges, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

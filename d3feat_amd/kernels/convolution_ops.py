@@ -83,6 +83,15 @@ def KPConv_ops(query_points, support_points, neighbors_indices, features, K_poin
     return ops.gemm(wf, K_values.reshape(num_kp * cin, cout), row_scale=inv_cnt, **(epilogue or {}))
 
 
+def KPConv_ops_backward(query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent, KP_influence,
+                        aggregation_mode, grad_output, **kwargs):
+    """Backward of KPConv_ops (without epilogue): grad_output f32[n, Cout] -> (gradient with respect to `features` [n0, Cin], gradient
+    with respect to K_values [num_kp, Cin, Cout]).  Keywords (transpose, need_features, need_weights, out_features, out_weights) as
+    ops.kpconv_backward; the definition is in include/d3feat_amd.h (d3f_kpconv_backward)."""
+    return ops.kpconv_backward(query_points, support_points, neighbors_indices, features, K_points, K_values, grad_output, KP_extent,
+                               KP_influence, aggregation_mode, **kwargs)
+
+
 def KPConv_deformable(query_points, support_points, neighbors_indices, features, K_values, fixed='center', KP_extent=1.0,
                       KP_influence='linear', aggregation_mode='sum', modulated=False, K_points=None, offset_weights=None,
                       offset_bias=None, epilogue=None):

@@ -1285,6 +1285,129 @@ def detect_head_backward(x, neighbors, stack_lengths_dev, include_zero_dev, grad
     return _tag(out, x)
 
 
+def _count(t, name):
+    """An optional device-resident row count: int32, one element."""
+    if t is not None:
+        _typed(t, torch.int32, name)
+        if t.numel() != 1:
+            raise ValueError("%s must hold one int32 (got shape %s)" % (name, tuple(t.shape)))
+    return t
+
+
+def neighbor_transpose_supports(neighbors, num_supports, nq_dev=None, ns_dev=None):
+    """The transposed table of a neighbour matrix whose rows (queries) differ from the rows it names (num_supports supports):
+    d3f_neighbor_transpose_qs -> (start i32[num_supports + 1], edges i32[Nq * K]).  nq_dev / ns_dev: device-resident real counts
+    (int32[1]) when the shapes are capacities; nq_dev defaults to the tag of `neighbors`.  Nine launches, no read-back, capturable."""
+    lib = _lib.load()
+    nb, ldi = _rows(_typed(neighbors, torch.int32, "neighbors"), "neighbors")
+    Ns = int(num_supports)
+    if Ns < 0:
+        raise ValueError("neighbor_transpose_supports: num_supports = %d" % Ns)
+    Nq, K = nb.shape
+    if Nq * K > (1 << 31) - 8192:
+        raise ValueError("neighbor_transpose_supports: %d x %d neighbour slots (at most 2^31 - 8192)" % (Nq, K))
+    if nq_dev is None:
+        nq_dev = getattr(neighbors, "n_dev", None)
+    nq_dev, ns_dev = _count(nq_dev, "nq_dev"), _count(ns_dev, "ns_dev")
+    _on_device("neighbor_transpose_supports", neighbors=nb, nq_dev=nq_dev, ns_dev=ns_dev)
+    dev = nb.device
+    start = torch.empty((Ns + 1,), dtype=torch.int32, device=dev)
+    edges = torch.empty((max(Nq * K, 1),), dtype=torch.int32, device=dev)
+    nbytes = lib.d3f_neighbor_transpose_workspace_bytes(Nq, K)
+    ws = workspace(nbytes, dev)
+    with _timed("neighbor_transpose_supports", dict(Nq=Nq, Ns=Ns, K=K), dev):
+        rc = lib.d3f_neighbor_transpose_qs(nb.data_ptr(), Nq, ldi, K, _ptr(nq_dev), Ns, _ptr(ns_dev), start.data_ptr(), edges.data_ptr(),
+                                           ws.data_ptr(), nbytes, _stream(dev))
+    _lib.check(rc, "neighbor_transpose_supports")
+    return start, edges[:Nq * K]
+
+
+def kpconv_backward(query_points, support_points, neighbors_indices, features, K_points, K_values, grad_out, KP_extent,
+                    KP_influence="linear", aggregation_mode="sum", transpose=None, need_features=True, need_weights=True,
+                    out_features=None, out_weights=None):
+    """Backward of KPConv_ops (kernels/convolution_ops.py:161-255) -> (gf f32[Ns, Cin] or None, gW f32[num_kp, Cin, Cout] or None): the
+    gradients with respect to the support feature rows and to K_values, from grad_out f32[Nq, Cout] (rows may be strided).  The
+    definition and the summation orders: include/d3feat_amd.h (d3f_kpconv_backward).  transpose: (start, edges) of
+    neighbor_transpose_supports for the same `neighbors_indices`; built here when None and gf is wanted.  Device-resident counts ride
+    on the tensors' tags as in the forward; rows of out_features at or beyond the support count are left alone.  No read-back,
+    capturable."""
+    lib = _lib.load()
+    q = _typed(query_points, torch.float32, "query_points", 2)
+    s = _typed(support_points, torch.float32, "support_points", 2)
+    idx, ld_idx = _rows(_typed(neighbors_indices, torch.int32, "neighbors_indices"), "neighbors_indices")
+    f, ldf = _rows(_typed(features, torch.float32, "features"), "features")
+    W = _typed(K_values, torch.float32, "K_values", 3)
+    g, ldg = _rows(_typed(grad_out, torch.float32, "grad_out"), "grad_out")
+    if KP_influence not in _INFLUENCE:
+        raise ValueError("Unknown influence function type (config.KP_influence)")
+    if aggregation_mode not in _AGGREGATION:
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    if q.shape[1] != 3 or s.shape[1] != 3:
+        raise ValueError("kpconv_backward: points must be [n, 3] (got %s, %s)" % (tuple(q.shape), tuple(s.shape)))
+    Nq, Ns, K = q.shape[0], s.shape[0], idx.shape[1]
+    num_kp, Cin, Cout = W.shape
+    kp = _kp_host(K_points)
+    if kp.ndim != 2 or kp.shape != (num_kp, 3) or not 1 <= num_kp <= 15:
+        raise ValueError("kpconv_backward: K_points is %s, K_values %s (1 .. 15 kernel points)" % (tuple(kp.shape), tuple(W.shape)))
+    if Cin < 1 or Cout < 1:
+        raise ValueError("kpconv_backward: K_values is %s" % (tuple(W.shape),))
+    if idx.shape[0] != Nq or f.shape[0] != Ns:
+        raise ValueError("kpconv_backward: %d queries / %d index rows, %d supports / %d feature rows" % (Nq, idx.shape[0], Ns, f.shape[0]))
+    if f.shape[1] != Cin:
+        raise ValueError("kpconv_backward: features have %d channels, K_values expects %d" % (f.shape[1], Cin))
+    if tuple(g.shape) != (Nq, Cout):
+        raise ValueError("kpconv_backward: grad_out is %s, wanted %s" % (tuple(g.shape), (Nq, Cout)))
+    if not (need_features or need_weights):
+        raise ValueError("kpconv_backward: neither gradient is wanted")
+    if Nq * K > (1 << 31) - 8192:
+        raise ValueError("kpconv_backward: %d x %d neighbour slots (at most 2^31 - 8192)" % (Nq, K))
+    if Ns == 0 and Nq > 0:
+        raise ValueError("kpconv_backward: %d queries and no support" % Nq)
+    if not float(KP_extent) > 0:
+        raise ValueError("kpconv_backward: KP_extent = %r" % (KP_extent,))
+    gf = ldgf = gW = None
+    if need_features and out_features is not None:
+        gf, ldgf = _rows(_typed(out_features, torch.float32, "out_features"), "out_features")
+        if tuple(gf.shape) != (Ns, Cin):
+            raise ValueError("kpconv_backward: out_features is %s, wanted %s" % (tuple(gf.shape), (Ns, Cin)))
+    if need_weights and out_weights is not None:
+        gW = _typed(out_weights, torch.float32, "out_weights", 3)
+        if tuple(gW.shape) != (num_kp, Cin, Cout) or not gW.is_contiguous():
+            raise ValueError("kpconv_backward: out_weights must be contiguous %s" % ((num_kp, Cin, Cout),))
+    start = edges = None
+    if need_features and transpose is not None:
+        start = _typed(transpose[0], torch.int32, "transpose[0]", 1)
+        edges = _typed(transpose[1], torch.int32, "transpose[1]", 1)
+        if start.numel() != Ns + 1 or edges.numel() < Nq * K or not (start.is_contiguous() and edges.is_contiguous()):
+            raise ValueError("kpconv_backward: transpose must be (start i32[Ns + 1], edges i32[Nq * K]) of the same neighbours")
+    nq_t = getattr(query_points, "n_dev", None)
+    ns_t = getattr(support_points, "n_dev", None)
+    if ns_t is None:
+        ns_t = getattr(features, "n_dev", None)
+    _on_device("kpconv_backward", query_points=q, support_points=s, neighbors_indices=idx, features=f, K_values=W, grad_out=g,
+               out_features=gf, out_weights=gW, start=start, edges=edges, nq_dev=nq_t, ns_dev=ns_t)
+    dev = f.device
+    q, s, W = q.contiguous(), s.contiguous(), W.contiguous()
+    if need_features and start is None:
+        start, edges = neighbor_transpose_supports(idx, Ns, nq_t, ns_t)
+    if need_features and gf is None:
+        gf, ldgf = torch.empty((Ns, Cin), dtype=torch.float32, device=dev), Cin
+    if need_weights and gW is None:
+        gW = torch.empty((num_kp, Cin, Cout), dtype=torch.float32, device=dev)
+    nbytes = lib.d3f_kpconv_backward_workspace_bytes(Nq, Ns, K, Cin, Cout, num_kp)
+    ws = workspace(nbytes, dev)
+    with _timed("kpconv_backward", dict(Nq=Nq, Ns=Ns, K=K, Cin=Cin, Cout=Cout), dev):
+        rc = lib.d3f_kpconv_backward(q.data_ptr(), Nq, s.data_ptr(), Ns, idx.data_ptr(), ld_idx, K, f.data_ptr(), ldf, Cin, kp.ctypes.data,
+                                     num_kp, float(KP_extent), _INFLUENCE[KP_influence], _AGGREGATION[aggregation_mode], W.data_ptr(),
+                                     g.data_ptr(), ldg, Cout, _ptr(start), _ptr(edges), _ptr(gf), ldgf or 0, _ptr(gW), _ptr(nq_t), _ptr(ns_t),
+                                     _order(query_points), 0, ws.data_ptr(), nbytes, _stream(dev))
+    _lib.check(rc, "kpconv_backward")
+    if gf is not None and ns_t is not None:
+        gf.n_dev = ns_t
+        gf.n_hint = getattr(support_points, "n_hint", 0) or getattr(features, "n_hint", 0)
+    return gf, gW
+
+
 class RawRecords:
     """A cloud still in its file encoding (utils.ply.read_ply_records / utils.results.read_kitti_records): raw bytes + record
     layout.  FragmentEngine.submit takes it wherever it takes a float32 [n,3] cloud and decodes it on the GPU, straight into

@@ -856,6 +856,66 @@ int d3f_detect_head_backward(const float* x, int N, int ldx, int C, const int* i
                              const float* gdesc, int ldg, const float* gscore, int ldgs, float* gx, int ldgx, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* The rectangular transposed table: Nq query rows name Ns support rows (a strided KPConv; d3f_neighbor_transpose is the square case
+ * whose row count comes from stack lengths).  Nq_dev / Ns_dev (device i32, may be NULL): nq = min(Nq, *Nq_dev), ns = min(Ns, *Ns_dev),
+ * as in the KPConv entry points; Nq and Ns are capacities.
+ *   idx i32[Nq, ld_idx] (K columns).  Edge e = i * K + k (i < nq) is VALID when 0 <= idx[i, k] < ns.  Keys are 0 .. ns.
+ *   start i32[Ns + 1]: row j's segment; every start[j] with j >= ns is the number of valid edges.
+ *   edges i32[Nq * K]: as d3f_neighbor_transpose; words at or beyond the number of valid edges are left alone.
+ * The same stable sort, the same nine launches and the same finishing kernel as d3f_neighbor_transpose.  D3F_ERR_ARG before anything
+ * touches the device: Nq < 0, Ns < 0, K < 0, Nq * K > 2^31 - 8192, ld_idx < K, a NULL start, a NULL edges or idx with Nq * K > 0.
+ * workspace >= d3f_neighbor_transpose_workspace_bytes(Nq, K), else D3F_ERR_WORKSPACE. */
+int d3f_neighbor_transpose_qs(const int* idx, int Nq, int ld_idx, int K, const int* Nq_dev, int Ns, const int* Ns_dev, int* start,
+                              int* edges, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of the rigid KPConv (kernels/convolution_ops.py:161-255): from gout f32[nq, Cout] (leading dimension ldg), the gradient
+ * with respect to the output of KPConv_ops, to gf f32[ns, Cin] (ldgf), the gradient with respect to the support feature rows, and
+ * gW f32[num_kp * Cin, Cout], the gradient with respect to K_values.  Either output may be NULL when it is not wanted.  The gather
+ * group (q .. Cin) and the kernel-point group (kp_host .. aggregation) are d3f_kpconv_aggregate's; W f32[num_kp * Cin, Cout] is
+ * K_values; start / edges: the table d3f_neighbor_transpose_qs made of the same idx; Nq_dev / Ns_dev / q_order as in the forward.
+ * Every influence, aggregation mode, channel count and num_kp the forward takes; queries may differ from supports (strided layers).
+ * fp32 feature rows only: feat_bf16 != 0 is D3F_ERR_ARG.
+ * Forward, as d3f_kpconv_aggregate documents it: h[n,k,p] is the influence of kernel point p on the pair (n, k) -- zero for shadow
+ * slots (idx[n,k] outside [0, ns)), masked to the arg-min kernel point under 'closest' --
+ *   wf[n,p,c] = sum_k h[n,k,p] f[idx[n,k], c]      cnt_n = max(#{k valid : row_pos[idx[n,k]]}, 1)
+ *   out[n,o]  = (sum_{p,c} wf[n,p,c] W[p,c,o]) / cnt_n
+ * Backward:
+ *   g[n,o]     = gout[n,o] / cnt_n (the rounded product gout * inv_cnt, inv_cnt = 1 / cnt_n as the forward computes it).  The count
+ *                has no gradient (tf.greater and the cast have none); the kernel points are trainable=False and the points are inputs,
+ *                so h is a constant of the backward; one_hot and argmin have no gradient either.
+ *   gW[p,c,o]  = sum_{n < nq} wf[n,p,c] g[n,o]
+ *   gwf[n,p,c] = sum_o g[n,o] W[p,c,o]
+ *   msg[e,c]   = sum_p h[n,k,p] gwf[n,p,c]   for the edge e = n K + k
+ *   gf[j,c]    = sum of msg[e,c] over row j's segment of the transposed table, in ascending e
+ * Summation orders: msg is ONE chain of fp32 fused multiply-adds over ascending p, started at zero.  The segment sum is ONE fp32 chain
+ * per channel in ascending e, started at zero (the rule of d3f_detect_head_backward step 4).  gW is summed over slices of consecutive
+ * query rows; the slice length depends on the CAPACITY Nq only -- 256 rows, doubled until at most 128 slices cover Nq -- never on
+ * the device or its occupancy; inside a slice the matrix instruction (v_mfma_f32_32x32x2_f32) adds pairs of rows to one accumulator
+ * in ascending row order; the slice partials are added in ascending slice order, started at zero.  gwf is d3f_gemm_f32 on g (a
+ * contiguous copy, so ldg does not matter) and a transposed copy of W: fixed for given shapes.  No float atomic, no workgroup waits for another: two
+ * calls give equal bits in both outputs, and a row of gf depends on its own segment only.
+ * Every word of the first ns rows of gf (Cin columns) and of all of gW is written; rows that nobody names get exact zeros; gf rows at
+ * or beyond ns are left alone.  gout, q and idx rows at or beyond nq are never read, s and f rows at or beyond ns neither, and no
+ * index outside [0, ns) forms an address.  The table is range-checked, never trusted.
+ * Launches: d3f_row_positive and d3f_kpconv_aggregate as they are (wf, inv_cnt); g; for gW the slice contraction and the kernel that
+ * adds the partials; for gf the transposed copy of W, d3f_gemm_f32 (gwf overwrites wf), the message kernel (the forward's neighbour
+ * loop turned round: Cin = 4 .. 1024 powers of two on the forward's lanes-per-query ladder, any other Cin one thread per (query,
+ * channel)) and the segment gather.  All sizes are read on the device; no read-back, no memset, no atomic on global memory;
+ * capturable.  Nq == 0 or K == 0 is D3F_OK with gf and gW written as zeros.
+ * D3F_ERR_ARG before anything touches the device: a negative size, Cin or Cout < 1 or > 2^20, ld_idx < K, ldf < Cin, ldg < Cout,
+ * ldgf < Cin (gf given), num_kp outside 1 .. 15, an unknown influence or aggregation, KP_extent <= 0, Nq * K > 2^31 - 8192, both
+ * outputs NULL, Ns == 0 with Nq > 0, a NULL kp_host or W, a NULL start with gf given, a NULL q, s, f or gout with Nq > 0, a NULL idx
+ * (or edges, gf given) with Nq * K > 0.
+ * workspace >= d3f_kpconv_backward_workspace_bytes(Nq, Ns, K, Cin, Cout, num_kp): wf / gwf (Nq num_kp Cin floats), msg (Nq K Cin),
+ * the gW partials (ceil(Nq / slice) num_kp Cin Cout), g (Nq Cout), inv_cnt (Nq), the row flags (Ns bytes), the transposed W and the contraction's
+ * own workspace; else D3F_ERR_WORKSPACE.  The function returns 0 for sizes the call refuses. */
+size_t d3f_kpconv_backward_workspace_bytes(int Nq, int Ns, int K, int Cin, int Cout, int num_kp);
+int d3f_kpconv_backward(const float* q, int Nq, const float* s, int Ns, const int* idx, int ld_idx, int K, const void* f, int ldf,
+                        int Cin, const float* kp_host, int num_kp, float KP_extent, int influence, int aggregation, const float* W,
+                        const float* gout, int ldg, int Cout, const int* start, const int* edges, float* gf, int ldgf, float* gW,
+                        const int* Nq_dev, const int* Ns_dev, const int* q_order, int feat_bf16, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* The KITTI test metric of P * per_pair estimated transforms in two launches (utils/tester.py:326-344 of the reference: relative
  * translation error, relative rotation error, success under both thresholds, and the sums of its three AverageMeters).
  *   T_est f32[P * per_pair, 12], row-major [R | t]; gt f32[P, 12] in the SAME direction as T_est: source -> target, the direction of
