@@ -114,6 +114,12 @@ SIGNATURES = {
     "d3f_kpconv_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "d3f_kpconv_backward": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp, _i, _f, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp,
                                  _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "d3f_gemm_tn_workspace_bytes": (_sz, [_i, _i, _i]),
+    "d3f_gemm_tn_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "d3f_batch_norm_workspace_bytes": (_sz, [_i, _i]),
+    "d3f_batch_norm_train": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "d3f_batch_norm_backward": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz,
+                                     _vp]),
     "d3f_pose_errors": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_sanitize_descriptors": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "d3f_matching_summary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -17,14 +17,8 @@
 #pragma once
 
 // ---- gW: the contraction over the query rows, in slices ---------------------------------------------------------------------------
-// The slice length depends on the CAPACITY Nq only: 256 rows, doubled until at most 128 slices cover the capacity.
-#define KPB_SLICE_MIN 256
-#define KPB_SLICES_MAX 128
-static inline int kpb_slice_rows(int Nq) {
-    int S = KPB_SLICE_MIN;
-    while (d3f_cdiv(Nq, S) > KPB_SLICES_MAX) S *= 2;
-    return S;
-}
+// The slice length depends on the CAPACITY Nq only: 256 rows, doubled until at most 128 slices cover the capacity (common.h).
+static inline int kpb_slice_rows(int Nq) { return d3f_slice_rows(Nq); }
 
 // g[n, o] = gout[n, o] * inv_cnt[n] for the nq real rows
 __global__ void __launch_bounds__(256) kpb_scale_kernel(const float* __restrict__ gout, int ldg, const float* __restrict__ inv_cnt, int Nq,
@@ -37,8 +31,9 @@ __global__ void __launch_bounds__(256) kpb_scale_kernel(const float* __restrict_
 
 // one wavefront per (32 rows of gW's M = num_kp * Cin, 32 output channels, slice): D[32 x 32] += A[32 x 2] B[2 x 32] per pair of query
 // rows, A[i][k] = wf[n + k, m0 + i] (the 32 lanes of a half read 128 consecutive bytes of one wf row), B[k][j] = g[n + k, o0 + j].
-// One accumulator chain over the slice's rows in ascending order, eight rows requested before any is multiplied.
-__global__ void __launch_bounds__(64) kpb_gw_kernel(const float* __restrict__ wf, const float* __restrict__ g, int Nq,
+// One accumulator chain over the slice's rows in ascending order, eight rows requested before any is multiplied.  ldw / ldg: the
+// leading dimensions of wf and g (d3f_kpconv_backward passes M and Cout, d3f_gemm_tn_f32 its callers' own).
+__global__ void __launch_bounds__(64) kpb_gw_kernel(const float* __restrict__ wf, int ldw, const float* __restrict__ g, int ldg, int Nq,
                                                     const int* __restrict__ Nq_dev, int M, int Cout, int S, float* __restrict__ part) {
     const int nq = d3f_dyn(Nq, Nq_dev);
     const int slice = blockIdx.z;
@@ -57,8 +52,8 @@ __global__ void __launch_bounds__(64) kpb_gw_kernel(const float* __restrict__ wf
         for (int u = 0; u < 4; ++u) {
             const int r = n + 2 * u + kh;
             const bool ok = r < n1;
-            a[u] = (ok && mok) ? wf[(size_t)r * M + m] : 0.f;
-            b[u] = (ok && ook) ? g[(size_t)r * Cout + o] : 0.f;
+            a[u] = (ok && mok) ? wf[(size_t)r * ldw + m] : 0.f;
+            b[u] = (ok && ook) ? g[(size_t)r * ldg + o] : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -297,7 +292,7 @@ extern "C" int d3f_kpconv_backward(const float* q, int Nq, const float* s, int N
         const int S = kpb_slice_rows(Nq);
         if (work) {
             const dim3 grid(d3f_cdiv(M, 32), d3f_cdiv(Cout, 32), d3f_cdiv(Nq, S));
-            kpb_gw_kernel<<<grid, 64, 0, stream>>>(wf, g, Nq, Nq_dev, M, Cout, S, part);
+            kpb_gw_kernel<<<grid, 64, 0, stream>>>(wf, M, g, Cout, Nq, Nq_dev, M, Cout, S, part);
         }
         kpb_gw_reduce_kernel<<<d3f_cdiv((long long)words, 256), 256, 0, stream>>>(part, work ? Nq : 0, Nq_dev, words, S, gW);
         D3F_LAUNCH_CHECK();
@@ -332,5 +327,32 @@ extern "C" int d3f_kpconv_backward(const float* q, int Nq, const float* s, int N
             D3F_LAUNCH_CHECK();
         }
     }
+    return D3F_OK;
+}
+
+// ---- out = A^T B ------------------------------------------------------------------------------------------------------------------
+// d3f_gemm_tn_f32: the gW contraction above on the caller's own operands (the backward of a unary convolution: gW = x^T gy).  The same
+// two kernels, the same slices, the same order: on contiguous operands the bits of d3f_kpconv_backward's gW for the same rows.
+static inline bool kpb_tn_sizes_ok(int M, int Ca, int Cb) { return M >= 0 && Ca >= 1 && Cb >= 1 && Ca <= (1 << 20) && Cb <= (1 << 20); }
+
+extern "C" size_t d3f_gemm_tn_workspace_bytes(int M, int Ca, int Cb) {
+    if (!kpb_tn_sizes_ok(M, Ca, Cb)) return 0;
+    return d3f_align((size_t)d3f_cdiv(M, kpb_slice_rows(M)) * Ca * Cb * 4 + 4);
+}
+
+extern "C" int d3f_gemm_tn_f32(const float* A, int lda, const float* B, int ldb, int M, int Ca, int Cb, float* out, const int* M_dev,
+                               void* workspace, size_t workspace_bytes, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!kpb_tn_sizes_ok(M, Ca, Cb) || lda < Ca || ldb < Cb || !out || (M > 0 && (!A || !B))) return D3F_ERR_ARG;
+    if (!workspace || workspace_bytes < d3f_gemm_tn_workspace_bytes(M, Ca, Cb)) return D3F_ERR_WORKSPACE;
+    float* part = (float*)workspace;
+    const int S = kpb_slice_rows(M);
+    const size_t words = (size_t)Ca * Cb;
+    if (M > 0) {
+        const dim3 grid(d3f_cdiv(Ca, 32), d3f_cdiv(Cb, 32), d3f_cdiv(M, S));
+        kpb_gw_kernel<<<grid, 64, 0, stream>>>(A, lda, B, ldb, M, M_dev, Ca, Cb, S, part);
+    }
+    kpb_gw_reduce_kernel<<<d3f_cdiv((long long)words, 256), 256, 0, stream>>>(part, M, M_dev, words, S, out);
+    D3F_LAUNCH_CHECK();
     return D3F_OK;
 }

@@ -2,16 +2,21 @@
 block types of the shipped architectures.  Every block keeps the reference signature
     block(layer_ind, inputs, features, radius, fdim, config, training)
 and runs eagerly on the MI355X; variables live in the VariableStore set by `use_variables(...)` (the role of
-the TF variable scopes).  Inference only: `training` must be False (the reference derives it from
-dropout_prob < 0.99, :1071), batch norm uses the moving statistics and is fused, together with LeakyReLU(0.2)
-and the residual add, into the epilogue of the producing contraction.
+the TF variable scopes).  With training=False (the reference derives it from dropout_prob < 0.99, :1071) batch norm uses the
+moving statistics and is fused, together with LeakyReLU(0.2) and the residual add, into the epilogue of the producing contraction.
+With training=True the `unary`, `simple` and `resnetb` blocks run as the unfused composition of the trainable operators
+(kernels/autograd.py): batch statistics, the moving statistics updated in place, gradients to every variable of the block
+(VariableStore.parameter).  The strided and the deformable blocks, a pending nearest-upsample input and bf16 feature storage raise
+NotImplementedError with training=True.
 """
 import contextlib
 
 import numpy as np
+import torch
 
 from .. import ops
 from ..kernels import convolution_ops as conv_ops
+from ..kernels.autograd import batch_norm_trainable, kpconv_trainable, unary_trainable
 from ..kernels.kernel_points import create_kernel_points
 
 _STORE = None
@@ -64,10 +69,23 @@ def _bn(channels, use_batch_norm=True):
     return None, vs.tensor(vs.offset_variable(channels))
 
 
+def _bn_train(x, use_batch_norm, momentum, leaky=False, residual=None):
+    """:149-165 with training=True on the variables of the current scope, then the residual add and LeakyReLU(0.2) of the block in
+    the same pass: batch statistics, the scope's moving statistics updated in place."""
+    vs = _vs()
+    channels = int(x.shape[1])
+    if not use_batch_norm:
+        return batch_norm_trainable(x, None, vs.parameter(vs.offset_variable(channels)), residual, leaky, 0.2)
+    gamma, beta, mean, var = vs.batch_norm_variables(channels)
+    return batch_norm_trainable(x, vs.parameter(gamma), vs.parameter(beta), residual, leaky, 0.2, vs.tensor(mean), vs.tensor(var),
+                                momentum, 1e-6)
+
+
 def batch_norm(x, use_batch_norm=True, momentum=0.99, training=False):
-    """:149-165, inference mode, as a stand-alone op."""
+    """:149-165, as a stand-alone op."""
     if training:
-        raise NotImplementedError('d3feat_amd implements the inference path only (training=False)')
+        _check_trainable(x, 'batch_norm')
+        return _bn_train(x, use_batch_norm, momentum)
     scale, shift = _bn(int(x.shape[1]), use_batch_norm)
     return ops.affine_act(x, scale, shift)
 
@@ -125,9 +143,18 @@ def KPConv_deformable(query_points, support_points, neighbors_indices, features,
                                       offset_weights=w0, offset_bias=b0, epilogue=epilogue)
 
 
-def _check_inference(training):
+def _check_inference(training, what):
     if training:
-        raise NotImplementedError('d3feat_amd implements the inference path only (training=False)')
+        raise NotImplementedError('training=True: %s' % what)
+
+
+def _check_trainable(features, block):
+    """The inputs the training path does not take yet."""
+    if isinstance(features, ops.UpsampleCat):
+        raise NotImplementedError('training=True: %s on a pending nearest-upsample concatenation needs the backward of the nearest '
+                                  'upsampling, which is not built' % block)
+    if ops.BF16_FEATURES or features.dtype != torch.float32:
+        raise NotImplementedError('training=True: %s under bf16 feature storage: the trainable operators take float32 rows only' % block)
 
 
 # ---- blocks --------------------------------------------------------------------------------------------------------
@@ -141,7 +168,11 @@ def last_unary_block(layer_ind, inputs, features, radius, fdim, config, training
 
 def unary_block(layer_ind, inputs, features, radius, fdim, config, training):
     """:207-219."""
-    _check_inference(training)
+    if training:
+        _check_trainable(features, 'unary_block')
+        vs = _vs()
+        w = vs.parameter(vs.weight_variable([int(features.shape[1]), fdim]))
+        return _bn_train(unary_trainable(features, w), config.use_batch_norm, config.batch_norm_momentum, leaky=True)
     if isinstance(features, ops.UpsampleCat):
         # decoder: nearest upsampling + skip concatenation (models/D3Feat.py:55-63) fused into this contraction
         vs = _vs()
@@ -161,10 +192,53 @@ def unary_block(layer_ind, inputs, features, radius, fdim, config, training):
 
 def simple_block(layer_ind, inputs, features, radius, fdim, config, training):
     """:222-244."""
-    _check_inference(training)
+    if training:
+        _check_trainable(features, 'simple_block')
+        vs = _vs()
+        w = vs.parameter(vs.weight_variable([config.num_kernel_points, int(features.shape[1]), fdim]))
+        pts = inputs['points'][layer_ind]
+        x = _kpconv_train(pts, pts, inputs['neighbors'][layer_ind], features, w, radius, config)
+        return _bn_train(x, config.use_batch_norm, config.batch_norm_momentum, leaky=True)
     w = weight_variable([config.num_kernel_points, int(features.shape[1]), fdim])
     return KPConv(inputs['points'][layer_ind], inputs['points'][layer_ind], inputs['neighbors'][layer_ind], features, w,
                   radius, config, epilogue=lambda: _epilogue(fdim, config, True))
+
+
+def _kpconv_train(query_points, support_points, neighbors_indices, features, K_values, radius, config):
+    """KPConv (:86-103) without epilogue, trainable: the `kernel_points` of the current scope are created after the weights."""
+    extent = config.KP_extent * radius / config.density_parameter
+    K_points = _kernel_points(config, extent)
+    return kpconv_trainable(query_points, support_points, neighbors_indices, features, K_points, K_values, extent, config.KP_influence,
+                            config.convolution_mode)
+
+
+def _resnetb_train(layer_ind, inputs, features, radius, fdim, config):
+    """:321-368 with training=True, unfused: conv1 unary -> BN -> leaky; conv2 KPConv -> BN -> leaky; shortcut unary -> BN iff the
+    width changes; conv3 unary -> BN + shortcut -> leaky.  Variables are created in the reference's order (conv3 before shortcut)."""
+    _check_trainable(features, 'resnetb_block')
+    vs = _vs()
+    bn, momentum = config.use_batch_norm, config.batch_norm_momentum
+    cin = int(features.shape[1])
+    with variable_scope('conv1'):
+        w = vs.parameter(vs.weight_variable([cin, fdim // 2]))
+        x = _bn_train(unary_trainable(features, w), bn, momentum, leaky=True)
+    with variable_scope('conv2'):
+        w = vs.parameter(vs.weight_variable([config.num_kernel_points, fdim // 2, fdim // 2]))
+        pts = inputs['points'][layer_ind]
+        x = _bn_train(_kpconv_train(pts, pts, inputs['neighbors'][layer_ind], x, w, radius, config), bn, momentum, leaky=True)
+    with variable_scope('conv3'):
+        w3 = vs.parameter(vs.weight_variable([fdim // 2, 2 * fdim]))
+        if bn:
+            vs.batch_norm_variables(2 * fdim)
+        else:
+            vs.offset_variable(2 * fdim)
+    shortcut = features
+    if cin != 2 * fdim:
+        with variable_scope('shortcut'):
+            w = vs.parameter(vs.weight_variable([cin, 2 * fdim]))
+            shortcut = _bn_train(unary_trainable(features, w), bn, momentum)
+    with variable_scope('conv3'):
+        return _bn_train(unary_trainable(x, w3), bn, momentum, leaky=True, residual=shortcut)
 
 
 def _resnetb(layer_ind, inputs, features, radius, fdim, config, strided, deformable=False):
@@ -215,26 +289,28 @@ def _resnetb(layer_ind, inputs, features, radius, fdim, config, strided, deforma
 
 def resnetb_block(layer_ind, inputs, features, radius, fdim, config, training):
     """:321-368: unary -> KPConv -> unary, shortcut (unary + BN iff the width changes), LeakyReLU(sum)."""
-    _check_inference(training)
+    if training:
+        return _resnetb_train(layer_ind, inputs, features, radius, fdim, config)
     return _resnetb(layer_ind, inputs, features, radius, fdim, config, False)
 
 
 def resnetb_strided_block(layer_ind, inputs, features, radius, fdim, config, training):
     """:561-612: as resnetb but the KPConv queries the next layer's points through `pools`, and the shortcut is
     the max pooling of the input features (+ unary + BN iff the width changes)."""
-    _check_inference(training)
+    _check_inference(training, 'resnetb_strided_block needs the backward of the max pooling of its shortcut, which is not built')
     return _resnetb(layer_ind, inputs, features, radius, fdim, config, True)
 
 
 def resnetb_deformable_block(layer_ind, inputs, features, radius, fdim, config, training):
     """:424-471: resnetb with a deformable KPConv as conv2."""
-    _check_inference(training)
+    _check_inference(training, 'resnetb_deformable_block needs the backward of the deformable KPConv, which is not built')
     return _resnetb(layer_ind, inputs, features, radius, fdim, config, False, deformable=True)
 
 
 def resnetb_deformable_strided_block(layer_ind, inputs, features, radius, fdim, config, training):
     """:672-723: resnetb_strided with a deformable KPConv as conv2."""
-    _check_inference(training)
+    _check_inference(training, 'resnetb_deformable_strided_block needs the backward of the deformable KPConv and of the max pooling, '
+                     'which are not built')
     return _resnetb(layer_ind, inputs, features, radius, fdim, config, True, deformable=True)
 
 

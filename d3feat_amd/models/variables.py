@@ -31,6 +31,7 @@ class VariableStore:
         self._scope = []
         self._dev = {}
         self._recipes = {}      # derived device tensors -> how to recompute them on the host (update_in_place)
+        self._params = {}       # trainable leaves over the device copies (parameter)
 
     # ---- scopes -------------------------------------------------------------------------------------
     @contextlib.contextmanager
@@ -80,9 +81,30 @@ class VariableStore:
     def tensor(self, full):
         t = self._dev.get(full)
         if t is None:
-            t = torch.from_numpy(np.ascontiguousarray(self.values[full], dtype=np.float32)).to(self.device)
+            # (a copy of the host master also on the CPU device, where .to() would share its memory: an in-place step on the device
+            # copy reaches the master through commit() only)
+            t = torch.from_numpy(np.array(self.values[full], dtype=np.float32, order='C')).to(self.device)
             self._dev[full] = t
         return t
+
+    # ---- training ---------------------------------------------------------------------------------------
+    def parameter(self, full):
+        """The variable as a trainable leaf: requires_grad, the storage (and the version counter) of tensor(full), so an in-place
+        step on either is seen by both and by the packed copies that ride on them.  The same object at every call."""
+        p = self._params.get(full)
+        if p is None:
+            p = self._params[full] = self.tensor(full).detach().requires_grad_(True)
+        return p
+
+    def parameters(self):
+        """name -> leaf, of the parameters created so far (in creation order)."""
+        return dict(self._params)
+
+    def commit(self):
+        """After training steps on the device: the device copies (parameters and moving statistics) become the host masters, and the
+        folded, stacked and split copies the inference path reads are derived again in place (update_in_place).  -> the device
+        tensors that were rewritten."""
+        return self.update_in_place({k: t.detach().cpu().numpy() for k, t in self._dev.items() if isinstance(k, str)})
 
     def _bn_host(self, names, eps):
         g, b, m, v = (self.values[n].astype(np.float32) for n in names)
@@ -159,7 +181,8 @@ class VariableStore:
         touched = []
         for key, t in self._dev.items():
             if isinstance(key, str):
-                t.copy_(torch.from_numpy(self.values[key]))
+                with torch.no_grad():
+                    t.copy_(torch.from_numpy(self.values[key]))
                 touched.append(t)
             else:
                 host = self._recipes[key]()
@@ -171,6 +194,7 @@ class VariableStore:
     def invalidate_device(self):
         self._dev = {}
         self._recipes = {}
+        self._params = {}
 
 
 def build_variables(config, seed=42, in_features_dim=None, randomize_bn=False, device=None, randomize_offsets=False,

@@ -1498,3 +1498,181 @@ def affine_act(x, col_scale=None, col_shift=None, residual=None, leaky=False, al
                             out.data_ptr(), N, _nd(x), _stream(x.device))
     _lib.check(rc, "affine_act")
     return _tag(out, x)
+
+
+# ---- training: batch norm with batch statistics, the unary convolution's backward -----------------------------------------
+def _col(v, n, name):
+    """An optional float32 vector of n columns, contiguous."""
+    if v is not None:
+        _typed(v, torch.float32, name)
+        if v.numel() != n or not v.is_contiguous():
+            raise ValueError("%s must be a contiguous vector of %d" % (name, n))
+    return v
+
+
+def _row_count(*tensors):
+    """The device-resident row count that rides on the first tagged tensor, or None."""
+    for t in tensors:
+        d = getattr(t, "n_dev", None) if t is not None else None
+        if d is not None:
+            return d
+    return None
+
+
+def batch_norm_train(x, gamma, beta, eps=1e-6, residual=None, leaky=False, alpha=0.2, moving_mean=None, moving_variance=None,
+                     momentum=0.99, out=None):
+    """tf.layers.batch_normalization(training=True) on rows (models/network_blocks.py:149-165) with the block's epilogue ->
+    (y, mean f32[2, C], rstd f32[C]): y = act((x - mean) rstd gamma + beta + residual) with the statistics of the real rows, and the
+    moving statistics updated in place when both are given.  mean[0] is the batch mean, mean[1] its rounding remainder (the float64
+    mean is mean[0] + mean[1]); batch_norm_backward takes the pair as it is.  gamma=None: the form without batch norm, y = act(x + beta + residual),
+    mean and rstd are None.  The definition and the summation order: include/d3feat_amd.h (d3f_batch_norm_train).  out may be the
+    residual.  Three launches, no read-back, capturable."""
+    lib = _lib.load()
+    x, ldx = _rows(_typed(x, torch.float32, "x"), "x")
+    M, C = x.shape
+    if C < 1:
+        raise ValueError("batch_norm_train: x is %s" % (tuple(x.shape),))
+    gamma, beta = _col(gamma, C, "gamma"), _col(beta, C, "beta")
+    if beta is None:
+        raise ValueError("batch_norm_train: beta (the offset) is required")
+    if (moving_mean is None) != (moving_variance is None):
+        raise ValueError("batch_norm_train: moving_mean and moving_variance come together")
+    moving_mean, moving_variance = _col(moving_mean, C, "moving_mean"), _col(moving_variance, C, "moving_variance")
+    ldr = 0
+    if residual is not None:
+        residual, ldr = _rows(_typed(residual, torch.float32, "residual"), "residual")
+        if tuple(residual.shape) != (M, C):
+            raise ValueError("batch_norm_train: residual is %s, wanted %s" % (tuple(residual.shape), (M, C)))
+    if out is not None:
+        out, ldy = _rows(_typed(out, torch.float32, "out"), "out")
+        if tuple(out.shape) != (M, C):
+            raise ValueError("batch_norm_train: out is %s, wanted %s" % (tuple(out.shape), (M, C)))
+    if gamma is not None and not float(eps) > 0:
+        raise ValueError("batch_norm_train: eps = %r" % (eps,))
+    n_dev = _row_count(x, residual)
+    _on_device("batch_norm_train", x=x, gamma=gamma, beta=beta, residual=residual, out=out, moving_mean=moving_mean,
+               moving_variance=moving_variance, n_dev=n_dev)
+    dev = x.device
+    if out is None:
+        out, ldy = torch.empty((M, C), dtype=torch.float32, device=dev), C
+    mean = rstd = None
+    if gamma is not None:
+        mean = torch.empty((2, C), dtype=torch.float32, device=dev)
+        rstd = torch.empty((C,), dtype=torch.float32, device=dev)
+    else:
+        moving_mean = moving_variance = None
+    nbytes = lib.d3f_batch_norm_workspace_bytes(M, C)
+    ws = workspace(nbytes, dev)
+    with _timed("batch_norm_train", dict(M=M, C=C), dev):
+        rc = lib.d3f_batch_norm_train(x.data_ptr(), ldx, M, C, _ptr(gamma), beta.data_ptr(), float(eps), float(momentum),
+                                      _ptr(moving_mean), _ptr(moving_variance), _ptr(residual), ldr, 1 if leaky else 0, float(alpha),
+                                      out.data_ptr(), ldy, _ptr(mean), _ptr(rstd), _ptr(n_dev), ws.data_ptr(), nbytes, _stream(dev))
+    _lib.check(rc, "batch_norm_train")
+    if n_dev is not None and getattr(out, "n_dev", None) is None:
+        _tag(out, x if getattr(x, "n_dev", None) is not None else residual)
+    return out, mean, rstd
+
+
+def batch_norm_backward(x, y, grad_y, gamma, mean, rstd, leaky=False, alpha=0.2, need_residual=False, out=None, out_residual=None):
+    """Backward of batch_norm_train -> (gx, ggamma, gbeta, gres): from grad_y and the stored y (the LeakyReLU mask is taken from it),
+    the gradients with respect to x, gamma, beta and -- need_residual -- the residual (None otherwise).  gamma=None: the form without
+    batch norm, ggamma is None and gx is the masked gradient.  out (for gx) may be grad_y; out_residual (for gres) may be grad_y when
+    out is not.  The definition: include/d3feat_amd.h
+    (d3f_batch_norm_backward).  Two launches, no read-back, capturable."""
+    lib = _lib.load()
+    g, ldg = _rows(_typed(grad_y, torch.float32, "grad_y"), "grad_y")
+    M, C = g.shape
+    if C < 1:
+        raise ValueError("batch_norm_backward: grad_y is %s" % (tuple(g.shape),))
+    ldx = ldy = 0
+    if gamma is not None:
+        x, ldx = _rows(_typed(x, torch.float32, "x"), "x")
+        gamma, mean, rstd = _col(gamma, C, "gamma"), _col(mean, 2 * C, "mean"), _col(rstd, C, "rstd")
+        if mean is None or rstd is None:
+            raise ValueError("batch_norm_backward: mean and rstd of the forward are required with gamma")
+    else:
+        x = mean = rstd = None
+    if leaky:
+        y, ldy = _rows(_typed(y, torch.float32, "y"), "y")
+    else:
+        y = None
+    for t, name in ((x, "x"), (y, "y")):
+        if t is not None and tuple(t.shape) != (M, C):
+            raise ValueError("batch_norm_backward: %s is %s, grad_y %s" % (name, tuple(t.shape), (M, C)))
+    if out is not None:
+        out, ldgx = _rows(_typed(out, torch.float32, "out"), "out")
+        if tuple(out.shape) != (M, C):
+            raise ValueError("batch_norm_backward: out is %s, wanted %s" % (tuple(out.shape), (M, C)))
+    gres, ldgr = None, C
+    if need_residual and out_residual is not None:
+        gres, ldgr = _rows(_typed(out_residual, torch.float32, "out_residual"), "out_residual")
+        if tuple(gres.shape) != (M, C):
+            raise ValueError("batch_norm_backward: out_residual is %s, wanted %s" % (tuple(gres.shape), (M, C)))
+    n_dev = _row_count(grad_y, x, y)
+    _on_device("batch_norm_backward", x=x, y=y, grad_y=g, gamma=gamma, mean=mean, rstd=rstd, out=out, out_residual=gres, n_dev=n_dev)
+    dev = g.device
+    if out is None:
+        out, ldgx = torch.empty((M, C), dtype=torch.float32, device=dev), C
+    gbeta = torch.empty((C,), dtype=torch.float32, device=dev)
+    ggamma = torch.empty((C,), dtype=torch.float32, device=dev) if gamma is not None else None
+    if need_residual and gres is None:
+        gres = torch.empty((M, C), dtype=torch.float32, device=dev)
+    nbytes = lib.d3f_batch_norm_workspace_bytes(M, C)
+    ws = workspace(nbytes, dev)
+    with _timed("batch_norm_backward", dict(M=M, C=C), dev):
+        rc = lib.d3f_batch_norm_backward(_ptr(x), ldx, _ptr(y), ldy, g.data_ptr(), ldg, M, C, _ptr(gamma), _ptr(mean), _ptr(rstd),
+                                         1 if leaky else 0, float(alpha), out.data_ptr(), ldgx, _ptr(ggamma), gbeta.data_ptr(), _ptr(gres),
+                                         ldgr, _ptr(n_dev), ws.data_ptr(), nbytes, _stream(dev))
+    _lib.check(rc, "batch_norm_backward")
+    if n_dev is not None:
+        for t in (out, gres):
+            if t is not None and getattr(t, "n_dev", None) is None:
+                t.n_dev = n_dev
+                t.n_hint = max(int(getattr(s, "n_hint", 0) or 0) for s in (grad_y, x, y) if s is not None)
+    return out, ggamma, gbeta, gres
+
+
+def gemm_tn(A, B, out=None):
+    """A^T B f32[Ca, Cb] over the real rows of A f32[n, Ca] and B f32[n, Cb] (rows may be strided): the contraction of
+    kpconv_backward's gW -- slices of rows in order, equal bits from call to call (include/d3feat_amd.h, d3f_gemm_tn_f32)."""
+    lib = _lib.load()
+    A, lda = _rows(_typed(A, torch.float32, "A"), "A")
+    B, ldb = _rows(_typed(B, torch.float32, "B"), "B")
+    if A.shape[0] != B.shape[0] or A.shape[1] < 1 or B.shape[1] < 1:
+        raise ValueError("gemm_tn: A is %s, B is %s" % (tuple(A.shape), tuple(B.shape)))
+    (M, Ca), Cb = A.shape, B.shape[1]
+    if out is not None:
+        _typed(out, torch.float32, "out", 2)
+        if tuple(out.shape) != (Ca, Cb) or not out.is_contiguous():
+            raise ValueError("gemm_tn: out must be contiguous %s" % ((Ca, Cb),))
+    n_dev = _row_count(A, B)
+    _on_device("gemm_tn", A=A, B=B, out=out, n_dev=n_dev)
+    dev = A.device
+    if out is None:
+        out = torch.empty((Ca, Cb), dtype=torch.float32, device=dev)
+    nbytes = lib.d3f_gemm_tn_workspace_bytes(M, Ca, Cb)
+    ws = workspace(nbytes, dev)
+    with _timed("gemm_tn", dict(M=M, Ca=Ca, Cb=Cb), dev):
+        rc = lib.d3f_gemm_tn_f32(A.data_ptr(), lda, B.data_ptr(), ldb, M, Ca, Cb, out.data_ptr(), _ptr(n_dev), ws.data_ptr(), nbytes,
+                                 _stream(dev))
+    _lib.check(rc, "gemm_tn")
+    return out
+
+
+def unary_backward(x, W, grad_y, need_input=True, need_weights=True):
+    """Backward of the unary convolution y = x W (W f32[Cin, Cout]) -> (gx = grad_y W^T or None, gW = x^T grad_y or None).  gx is
+    ops.gemm on a transposed copy of W (its packed copies are keyed on the tensor and its version, so a fresh transpose per call is
+    safe); gW is gemm_tn."""
+    _typed(W, torch.float32, "W", 2)
+    if tuple(grad_y.shape) != (x.shape[0], W.shape[1]) or x.shape[1] != W.shape[0]:
+        raise ValueError("unary_backward: x is %s, W %s, grad_y %s" % (tuple(x.shape), tuple(W.shape), tuple(grad_y.shape)))
+    if not (need_input or need_weights):
+        raise ValueError("unary_backward: neither gradient is wanted")
+    gx = gW = None
+    if need_input:
+        g = grad_y if getattr(grad_y, "n_dev", None) is not None else _tag(grad_y.detach(), x)
+        with f32_output():
+            gx = gemm(g, W.detach().t().contiguous())
+    if need_weights:
+        gW = gemm_tn(x, grad_y)
+    return gx, gW

@@ -916,6 +916,74 @@ int d3f_kpconv_backward(const float* q, int Nq, const float* s, int Ns, const in
                         const int* Nq_dev, const int* Ns_dev, const int* q_order, int feat_bf16, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* out f32[Ca, Cb] = A^T B over the first m = min(M, *M_dev) rows (M_dev may be NULL: m = M): A f32[m, Ca] (lda), B f32[m, Cb] (ldb).  The
+ * backward of a unary convolution y = x W with respect to W is gW = x^T gy.  A second entry onto the two kernels of d3f_kpconv_backward's
+ * gW, so the order is the same: slices of consecutive rows whose length depends on the CAPACITY M only (256 rows, doubled until at most
+ * 128 slices cover M); inside a slice the matrix instruction (v_mfma_f32_32x32x2_f32) adds pairs of rows to one accumulator in ascending
+ * row order; the slice partials are added in ascending slice order, started at zero.  On contiguous operands the bits are those of
+ * d3f_kpconv_backward's gW for the same rows.  Two launches, no atomic, no read-back, capturable; every word of out is written (m == 0:
+ * zeros); rows at or beyond m are never read.  D3F_ERR_ARG: a negative M, Ca or Cb < 1 or > 2^20, lda < Ca, ldb < Cb, a NULL out, a
+ * NULL A or B with M > 0.  workspace >= d3f_gemm_tn_workspace_bytes(M, Ca, Cb) (the slice partials), else D3F_ERR_WORKSPACE. */
+size_t d3f_gemm_tn_workspace_bytes(int M, int Ca, int Cb);
+int d3f_gemm_tn_f32(const float* A, int lda, const float* B, int ldb, int M, int Ca, int Cb, float* out, const int* M_dev,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* Batch normalisation in TRAINING mode with the epilogue of a block, and its backward: tf.layers.batch_normalization(training=True) of
+ * models/network_blocks.py:149-165 on a rank-2 input (the non-fused path of TF 1.x), then the residual add and leaky_relu (:185-186).
+ * x f32[n, C] (ldx), n = min(M, *M_dev) (M_dev may be NULL: n = M); M is the capacity.  The statistics are taken over the n real rows of
+ * the stacked batch, all clouds together.
+ * Forward:
+ *   mean_c = (1/n) sum_i x[i,c]
+ *   var_c  = (1/n) sum_i (x[i,c] - mean_c)^2      two passes as tf.nn.moments, biased (no Bessel correction); the deviation is taken
+ *                                                 from the float64 mean, so a constant column has var == 0 exactly
+ *   rstd_c = 1 / sqrt(var_c + eps)                in float64, then rounded; rstd f32[C] is an output
+ *   mean f32[2, C] is an output in two parts: mean[0, c] the float64 mean rounded to fp32 (the batch mean of the moving update),
+ *             mean[1, c] the rounded remainder (float64 mean - mean[0, c]).  Both passes take x - mean as (x - mean[0]) - mean[1]: a
+ *             column whose spread is far below its mean (mean 1e3, spread 1e-2) would otherwise carry the rounding of its mean,
+ *             2^-24 |mean| rstd, as a shift of every entry of y.
+ *   z      = (x - mean) rstd gamma + beta [+ residual]          fp32, every operation rounded on its own, left to right
+ *   y      = z, or leaky != 0: z > 0 ? z : z alpha
+ *   moving <- moving - (moving - batch) * float32(1 - momentum)  in fp32, in TF's operation order (assign_moving_average), for the
+ *             mean and for the biased variance, batch = the float64 statistic rounded to fp32; 1 - momentum is taken in float64 from
+ *             the float argument.  moving_mean and moving_var are both given or both NULL (no update).
+ *   gamma == NULL: the form without batch norm (:162-165), z = x + beta [+ residual] with beta the offset; no statistics, one launch;
+ *             mean, rstd, eps, momentum and the moving pointers are unused.
+ * Backward, from gy f32[n, C] (ldg) and the STORED y (never a recomputation):
+ *   g      = gy (y > 0 ? 1 : alpha) under leaky (y == 0 takes alpha, as LeakyReluGrad), gy otherwise (y is then unused, may be NULL)
+ *   xhat   = (x - mean) rstd
+ *   gbeta_c = sum_i g     ggamma_c = sum_i g xhat
+ *   gx     = gamma rstd (g - gbeta/n - xhat ggamma/n)      gres = g (gres may be NULL)
+ *   gamma == NULL: gbeta (the offset's gradient) and gx = g only; x, mean, rstd and ggamma are unused.
+ * Aliases: y may be residual's buffer; gx may be gy's; gres may be gy's when gx is not.
+ * THE SUMMATION ORDER IS PART OF THE DEFINITION and is a function of the capacity M, n and C only -- never of the device, the leading
+ * dimensions or the alignment.  Rows are cut into slices of S = 256 rows, doubled until at most 128 slices cover M.  With
+ * LQ = min(16, the power of two >= ceil(C / 4)) and R = 256 / LQ, chain r of a slice adds the slice's rows r, r + R, r + 2 R, ... in
+ * ascending order from 0.0; the R chains are added by the tree  chain[r] += chain[r + s]  for r < s,  s = R/2, R/4, ... 1; the slice
+ * partials are added in ascending slice order from 0.0.  All of it in float64 (the summands are the fp32 values widened; for var the
+ * float64 squares of the float64 deviations; for ggamma the float64 products of the fp32 g and the fp32 xhat).  No float atomic, no
+ * read-back, capturable; two calls give equal bits.
+ * Kernels: lanes run across columns, four consecutive columns (a quad) per lane, LQ lanes per row, so a wavefront reads 64 / LQ rows at
+ * a time (C <= 16: 16 to 64 rows; C >= 64: four runs of 256 bytes).  Quads are moved as one 16-byte access when C % 4 == 0, every leading
+ * dimension in the call is a multiple of 4 and every base pointer is 16-byte aligned; as four guarded 4-byte accesses otherwise.  The
+ * thread mapping, and so the order above, is the same on both paths.
+ * Launches.  Forward, three: the column sums; the centred sums, whose last workgroup to finish writes mean and rstd and updates the
+ * moving statistics; the elementwise pass.  (gamma == NULL: the elementwise pass alone.)  Backward, two: the two column sums per slice;
+ * the elementwise pass, in which every workgroup adds the slice partials of its own columns and those of slice 0 write ggamma and gbeta.
+ * Every word of the first n rows (C columns) of y / gx / gres is written and rows at or beyond n are left alone; x, y, gy and residual
+ * rows at or beyond n are never read.  n == 0 writes nothing, leaves the moving statistics untouched and returns D3F_OK.
+ * D3F_ERR_ARG before anything touches the device: M < 0, C < 1 or > 2^20, a leading dimension in use below C, a NULL beta / gbeta,
+ * gamma with a NULL mean or rstd (or ggamma, backward) or eps <= 0, one moving pointer without the other, gres == gx, a NULL x / y /
+ * gy / gx in use with M > 0.
+ * workspace (8-byte aligned) >= d3f_batch_norm_workspace_bytes(M, C): a ticket and two sets of slice partials (slices x C doubles); its
+ * contents before the call do not matter; else D3F_ERR_WORKSPACE. */
+size_t d3f_batch_norm_workspace_bytes(int M, int C);
+int d3f_batch_norm_train(const float* x, int ldx, int M, int C, const float* gamma, const float* beta, float eps, float momentum,
+                         float* moving_mean, float* moving_var, const float* residual, int ldr, int leaky, float alpha, float* y, int ldy,
+                         float* mean, float* rstd, const int* M_dev, void* workspace, size_t workspace_bytes, void* stream);
+int d3f_batch_norm_backward(const float* x, int ldx, const float* y, int ldy, const float* gy, int ldg, int M, int C, const float* gamma,
+                            const float* mean, const float* rstd, int leaky, float alpha, float* gx, int ldgx, float* ggamma,
+                            float* gbeta, float* gres, int ldgr, const int* M_dev, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The KITTI test metric of P * per_pair estimated transforms in two launches (utils/tester.py:326-344 of the reference: relative
  * translation error, relative rotation error, success under both thresholds, and the sums of its three AverageMeters).
  *   T_est f32[P * per_pair, 12], row-major [R | t]; gt f32[P, 12] in the SAME direction as T_est: source -> target, the direction of
