@@ -139,6 +139,10 @@ SIGNATURES = {
                          _vp, _vp, _i, _vp]),
     "d3f_gemm_x3_gres": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _f,
                               _vp, _sz, _vp, _vp, _i, _vp]),
+    "d3f_gemm_pack_x3_chain": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "d3f_gemm_x3_chain_ok": (_i, [_i, _i, _i, _i, _i]),
+    "d3f_gemm_x3_chain": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp,
+                               _vp, _vp, _i, _f, _vp, _i, _vp, _vp, _vp]),
     "d3f_gemm_bf16": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _sz,
                            _vp, _vp, _i, _i, _i, _vp]),
     "d3f_decode_xyz_records": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),

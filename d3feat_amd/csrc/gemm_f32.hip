@@ -12,6 +12,8 @@
 // gemm_x3_kernel (gemm_x3.h)     d3f_gemm_x3_gres                  ops.gemm_upsample_split: the fine-level half of a decoder block,
 //                                                                  the coarse level's product gathered as residual rows
 // gemm_x3r_kernel (gemm_x3.h)    d3f_gemm_x3                       inside it, when d3f_gemm_x3_resident: tall, W fits the LDS
+// gemm_x3r_chain_kernel (same)   d3f_gemm_x3_chain                 ops.gemm_chain (d3f_gemm_x3_chain_ok): a tall contraction to 64 / 128
+//                                                                  columns whose NEXT contraction, to 32 columns, rides on its tile
 // gemm_dma_kernel (gemm_dma.h)   d3f_gemm_f32t                     ops._route: float4-addressable operands that x3 does not
 //                                                                  take (D3F_GEMM_X3=0, K % 32, 32-column layers, row cap)
 // gemm_fast_kernel (here)        d3f_gemm_f32,                     gemm_run: float4-addressable operands.  ops._route calls these
@@ -799,6 +801,18 @@ extern "C" int d3f_gemm_pack_x3(const float* B, int ldb, int K, int N, void* Wx,
     return D3F_OK;
 }
 
+// The packed image of the SECOND weight of d3f_gemm_x3_chain: W2 f32[K2, 32] with K2 = 64 or 128 (the first contraction's columns),
+// same size and layout as d3f_gemm_pack_x3's, the k rows of every 16-block in the order the chained kernel holds them (gemm_x3.h).
+extern "C" int d3f_gemm_pack_x3_chain(const float* B, int ldb, int K, int N, void* Wx, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if ((K != 64 && K != 128) || N != 32 || ldb < N || !B || !Wx || ((uintptr_t)Wx & 15)) return D3F_ERR_ARG;
+    const int nkt = K / GX_BK;
+    const long long total = (long long)nkt * GX_CHUNK;
+    gemm_pack_x3_kernel<<<d3f_cdiv(total, 256), 256, 0, stream>>>(B, ldb, K, N, nkt, total, (unsigned short*)Wx, 1);
+    D3F_LAUNCH_CHECK();
+    return D3F_OK;
+}
+
 // the plan d3f_gemm_x3 will use for a problem: rows / columns of its workgroups and the K slice count (diagnostics and tests)
 extern "C" int d3f_gemm_x3_plan(int M, int N, int K, int M_hint, int* rows, int* cols, int* slices) {
     if (M <= 0 || N <= 0 || K < GX_BK || (K % GX_BK)) return D3F_ERR_ARG;
@@ -827,6 +841,33 @@ extern "C" int d3f_gemm_x3_resident(int M, int N, int K, int M_hint) {
     return (NG == 1 || NG == 2 || NG == 4) && gemm_x3r_lds_bytes(K / GX_BK, NG) <= 160 * 1024 && m_eff >= 65536;
 }
 
+// LDS of the chained resident form: W, the W2 image (one k-tile per column group of the first product), the patches when the
+// first output is stored, both epilogues' vectors
+static size_t gemm_x3r_chain_lds_bytes(int nkt, int NG, int store_first) {
+    return (size_t)(nkt + 1) * NG * GX_CHUNK * sizeof(unsigned short) + (store_first ? GXR_PATCH_BYTES : 0) + GXR_EPI_BYTES + GXR_EPI2_BYTES;
+}
+
+// Can d3f_gemm_x3_chain take the problem, and is it d3f_gemm_x3's resident form that it replaces?  (N = 64 or 128 exactly.)
+extern "C" int d3f_gemm_x3_chain_ok(int M, int N, int K, int store_first, int M_hint) {
+    if (!d3f_gemm_x3_resident(M, N, K, M_hint) || (N != 64 && N != 128)) return 0;
+    return gemm_x3r_chain_lds_bytes(K / GX_BK, N / 32, store_first) <= 160 * 1024;
+}
+
+// CU count of the CURRENT device (cached per device ordinal: a process may drive several); 0: the runtime failed
+static int gemm_cus() {
+    static std::atomic<int> cus_of[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    int cus = cus_of[dev & 63].load(std::memory_order_relaxed);
+    if (!cus) {
+        hipDeviceProp_t pr;
+        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
+        cus = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
+        cus_of[dev & 63].store(cus, std::memory_order_relaxed);
+    }
+    return cus;
+}
+
 // The one launcher of d3f_gemm_x3 / d3f_gemm_x3_gres.  res_idx != NULL: the residual row of output row m is residual[res_idx[m *
 // ld_res_idx]] (GemmEpi::ridx) -- an operand only the tile kernel's epilogue and the K-split reduction know, so such a call takes the
 // tile form whatever d3f_gemm_x3_resident answers.
@@ -848,17 +889,8 @@ static int gemm_x3_run(const float* A, int N1, int lda, int C1, const int* idx, 
     GemmGather G{idx, ld_idx, N1, N1_dev, C2 > 0 ? skip : nullptr, lds, C1};
     const int nkt = K / GX_BK, NG = d3f_cdiv(N, 32);
     if (!res_idx && d3f_gemm_x3_resident(M, N, K, M_hint)) {   // ---- the resident-W persistent form (gemm_x3.h) ----
-        // CU count of the CURRENT device (cached per device ordinal: a process may drive several)
-        static std::atomic<int> cus_of[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return D3F_ERR_HIP;
-        int cus = cus_of[dev & 63].load(std::memory_order_relaxed);
-        if (!cus) {
-            hipDeviceProp_t pr;
-            if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return D3F_ERR_HIP;
-            cus = pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
-            cus_of[dev & 63].store(cus, std::memory_order_relaxed);
-        }
+        const int cus = gemm_cus();
+        if (!cus) return D3F_ERR_HIP;
         static std::atomic<unsigned long long> lds_done{0};
         const void* const fns[3] = {(const void*)gemm_x3r_kernel<1>, (const void*)gemm_x3r_kernel<2>, (const void*)gemm_x3r_kernel<4>};
         if (d3f_opt_in_lds(lds_done, fns, 160 * 1024) != D3F_OK) return D3F_ERR_HIP;
@@ -909,4 +941,45 @@ extern "C" int d3f_gemm_x3_gres(const float* A, int N1, int lda, int C1, const i
     return gemm_x3_run(A, N1, lda, C1, idx, ld_idx, skip, lds, C2, Wx, C, ldc, M, N, row_scale, col_scale, col_shift, residual, ldr,
                        res_idx, ld_res_idx, res_rows, res_rows_dev, leaky, alpha, workspace, workspace_bytes, M_dev, N1_dev, M_hint,
                        stream_);
+}
+
+// d3f_gemm_x3 (resident form, whatever M is) with the NEXT contraction chained in registers:
+//   Y  = act((([ A[idx] | skip ] @ W) * row_scale) * col_scale + col_shift + residual)        [M, N], N = 64 or 128; stored iff C != NULL
+//   C2 = act2((Y @ W2) * col_scale2 + col_shift2)                                             [M, 32]
+// Wx = d3f_gemm_pack_x3(W), W2x = d3f_gemm_pack_x3_chain(W2 f32[N, 32]).  Y is the fp32 value d3f_gemm_x3 would store, split exactly
+// for the second product.  D3F_ERR_ARG: d3f_gemm_x3's rules, N other than 64 / 128, C2 / W2x missing or misaligned, ldc2 < 32 or not
+// a multiple of 4, or an LDS image beyond 160 KB (K <= 96 with N = 128, K <= 224 stored / K <= 288 not stored with N = 64).
+extern "C" int d3f_gemm_x3_chain(const float* A, int N1, int lda, int C1, const int* idx, int ld_idx, const float* skip, int lds, int C2cols,
+                                 const void* Wx, float* C, int ldc, int M, int N, const float* row_scale, const float* col_scale,
+                                 const float* col_shift, const float* residual, int ldr, int leaky, float alpha, const void* W2x,
+                                 const float* col_scale2, const float* col_shift2, int leaky2, float alpha2, float* C2, int ldc2,
+                                 const int* M_dev, const int* N1_dev, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int K = C1 + C2cols, store = C != nullptr;
+    bool empty;
+    if (int rc = gemm_check_composite(true, GX_BK, 15, M, N, N1, C1, C2cols, lda, store ? ldc : N, lds, ldr, ld_idx, A, Wx, store ? C : C2,
+                                      idx, skip, residual, col_scale, col_shift, empty))
+        return rc;
+    if ((N != 64 && N != 128) || ldc2 < 32 || (ldc2 % 4)) return D3F_ERR_ARG;
+    const int nkt = K / GX_BK, NG = N / 32;
+    const size_t lds_bytes = gemm_x3r_chain_lds_bytes(nkt, NG, store);
+    if (lds_bytes > 160 * 1024) return D3F_ERR_ARG;
+    if (empty) return D3F_OK;
+    if (!C2 || !W2x || (((uintptr_t)C2 | (uintptr_t)W2x) & 15)) return D3F_ERR_ARG;
+    GemmEpi E{row_scale, col_scale, col_shift, residual, ldr, leaky, alpha, nullptr, 0, 0, nullptr};
+    GemmGather G{idx, ld_idx, N1, N1_dev, C2cols > 0 ? skip : nullptr, lds, C1};
+    GemmChain H{(const unsigned short*)W2x, col_scale2, col_shift2, leaky2, alpha2, C2, ldc2};
+    const int cus = gemm_cus();
+    if (!cus) return D3F_ERR_HIP;
+    static std::atomic<unsigned long long> lds_done{0};
+    const void* const fns[4] = {(const void*)gemm_x3r_chain_kernel<2, true>, (const void*)gemm_x3r_chain_kernel<2, false>,
+                                (const void*)gemm_x3r_chain_kernel<4, true>, (const void*)gemm_x3r_chain_kernel<4, false>};
+    if (d3f_opt_in_lds(lds_done, fns, 160 * 1024) != D3F_OK) return D3F_ERR_HIP;
+    const int grid = std::min(cus, d3f_cdiv(d3f_cdiv(M, 32), 8));
+#define D3F_GXC(TN_, ST_) gemm_x3r_chain_kernel<TN_, ST_><<<grid, 512, lds_bytes, stream>>>(A, lda, (const unsigned short*)Wx, nkt, C, ldc, M, N, E, M_dev, G, H)
+    if (NG == 4) { if (store) D3F_GXC(4, true); else D3F_GXC(4, false); }
+    else { if (store) D3F_GXC(2, true); else D3F_GXC(2, false); }
+#undef D3F_GXC
+    D3F_LAUNCH_CHECK();
+    return D3F_OK;
 }

@@ -87,9 +87,11 @@ __device__ __forceinline__ void gx_split8(const gx_f4& x0, const gx_f4& x1, uint
     for (int s = 0; s < 3; ++s) pl[s] = make_uint4(p[s][0], p[s][1], p[s][2], p[s][3]);
 }
 
-// W f32[K,N] (ldb) -> Wx (layout above); K rows beyond K and columns beyond N are zero
+// W f32[K,N] (ldb) -> Wx (layout above); K rows beyond K and columns beyond N are zero.  chain: the image of a SECOND contraction
+// fed from the accumulators of gemm_x3r_kernel's chained form -- k slot 16 s + 8 h + i of a k-tile holds source row
+// 16 s + (i < 4 ? 4 h + i : 8 + 4 h + i - 4), the order in which a lane of the first product holds its finished columns.
 __global__ void __launch_bounds__(256) gemm_pack_x3_kernel(const float* __restrict__ B, int ldb, int K, int N, int nkt, long long total,
-                                                           unsigned short* __restrict__ Wx) {
+                                                           unsigned short* __restrict__ Wx, int chain = 0) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
     const int kk = (int)(t % GX_LS);
@@ -98,7 +100,12 @@ __global__ void __launch_bounds__(256) gemm_pack_x3_kernel(const float* __restri
     const int p = (int)(q % 3); q /= 3;
     const int kt = (int)(q % nkt);
     const int ng = (int)(q / nkt);
-    const int k = kt * GX_BK + kk, n = ng * 32 + r;
+    int ks = kk;
+    if (chain && kk < GX_BK) {
+        const int h = (kk >> 3) & 1, i = kk & 7;
+        ks = (kk & 16) + (i < 4 ? 4 * h + i : 8 + 4 * h + i - 4);
+    }
+    const int k = kt * GX_BK + ks, n = ng * 32 + r;
     unsigned out = 0u;
     if (kk < GX_BK && k < K && n < N) {
         float w = B[(size_t)k * ldb + n];
@@ -413,12 +420,37 @@ gemm_x3_kernel(const float* __restrict__ A, int lda, const unsigned short* __res
 #define GXR_PS 36                       // floats per row of a wave's output patch (32 + 4: the b128 accesses of a row group on distinct banks)
 #define GXR_PATCH_BYTES (8 * 32 * GXR_PS * 4)
 #define GXR_EPI_BYTES (2 * 128 * 4)          // per-column scale / shift of up to 128 columns, staged once
-template <int TN>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
-gemm_x3r_kernel(const float* __restrict__ A, int lda, const unsigned short* __restrict__ Wx, int nkt, float* __restrict__ C, int ldc,
-                int M, int N, GemmEpi E, const int* __restrict__ M_dev, GemmGather G) {
+#define GXR_EPI2_BYTES (2 * 32 * 4)          // the chained contraction's, 32 columns
+// Chained form (CH != 0): the NEXT contraction of the network, to 32 columns, rides on the finished tile.  The product is computed
+// transposed, so after the k-loop lane (m, h) holds ITS OWN row's finished columns 32 j + 8 q + 4 h + e -- which is what the second
+// operand of the next v_mfma_f32_32x32x16_bf16 wants from that lane, eight k-values of row m, up to the order of k inside a
+// 16-block.  A contraction sums over k, so the order is free as long as W2 is packed in the same one (gemm_pack_x3_kernel, chain):
+// for k-step s of column group j the lane splits its finished quads q = 2 s and q = 2 s + 1 into three planes and multiplies them
+// with the resident W2 image: twelve MFMAs per column group into one more accumulator, no LDS round trip, no barrier, no memory
+// request.  The operand is the fp32 value the unchained form would have stored, split exactly; only the order of the second sum
+// differs.  CH == 1: the N-column tile is stored as ever and the 32-column result leaves through the same patch; CH == 2: the N-column
+// tile is NOT stored, and (no room for the patch beside a K = 256 image) the result leaves from the accumulators: lanes l and l + 32
+// hold adjacent 16-byte pieces of a row, four store instructions complete each 128-byte line.
+struct GemmChain {
+    const unsigned short* W2x;    // d3f_gemm_pack_x3_chain(W2 f32[32 TN, 32])
+    const float* col_scale;       // second epilogue: per-column scale / shift (NULL: identity), LeakyReLU
+    const float* col_shift;
+    int leaky;
+    float alpha;
+    float* C2;                    // [M, 32] (ldc2)
+    int ldc2;
+};
+template <int TN, int CH>
+__device__ __forceinline__ void gemm_x3r_body(const float* __restrict__ A, int lda, const unsigned short* __restrict__ Wx, int nkt,
+                                              float* __restrict__ C, int ldc, int M, int N, const GemmEpi& E,
+                                              const int* __restrict__ M_dev, const GemmGather& G, const GemmChain& H) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gxr_w[];      // [nkt][TN] chunks of GX_CHUNK bf16
     static_assert(TN == 1 || TN == 2 || TN == 4, "column groups per row tile");
+    static_assert(CH == 0 || TN > 1, "the chained form contracts 64 or 128 columns");
+    // LDS: W | W2 (chained) | the waves' output patches (not CH == 2) | epilogue vectors | the second epilogue's (chained)
+    const size_t w2_ofs = (size_t)nkt * TN * (GX_CHUNK * 2);
+    const size_t patch_ofs = w2_ofs + (CH ? (size_t)TN * (GX_CHUNK * 2) : 0);
+    const size_t ep_ofs = patch_ofs + (CH == 2 ? 0 : GXR_PATCH_BYTES);
     M = d3f_dyn(M, M_dev);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     {   // ---- W: chunk (column group j, k-tile kt) of the packed copy -> chunk (kt, j) of the LDS image ----
@@ -432,24 +464,34 @@ gemm_x3r_kernel(const float* __restrict__ A, int lda, const unsigned short* __re
         }
         // the per-column epilogue operands too (identity where absent): read from LDS in the epilogue -- a global load there is
         // waited for with vmcnt(0) by the compiler and drains the wave's prefetched operand loads once per tile
-        float* ep = (float*)(gxr_w + (size_t)nkt * TN * (GX_CHUNK * 2) + GXR_PATCH_BYTES);
+        float* ep = (float*)(gxr_w + ep_ofs);
         for (int c = tid; c < 32 * TN; c += 512) {
             ep[c] = (E.col_scale && c < N) ? E.col_scale[c] : 1.f;
             ep[32 * TN + c] = (E.col_shift && c < N) ? E.col_shift[c] : 0.f;
         }
+        if constexpr (CH != 0) {        // the W2 image is its packed copy as it stands (one column group: [k-tile][plane][32][40])
+            const uint4* src2 = (const uint4*)H.W2x;
+            uint4* dst2 = (uint4*)(gxr_w + w2_ofs);
+            for (int e = tid; e < TN * 480; e += 512) dst2[e] = src2[e];
+            if (tid < 32) {
+                ep[64 * TN + tid] = H.col_scale ? H.col_scale[tid] : 1.f;
+                ep[64 * TN + 32 + tid] = H.col_shift ? H.col_shift[tid] : 0.f;
+            }
+        }
     }
     __syncthreads();
-    const float* ep_scale = (const float*)(gxr_w + (size_t)nkt * TN * (GX_CHUNK * 2) + GXR_PATCH_BYTES);
+    const float* ep_scale = (const float*)(gxr_w + ep_ofs);
     const float* ep_shift = ep_scale + 32 * TN;
     const int ntiles = (M + 31) >> 5;
     // 8 (lane >> 5), RECOMPUTED where it is used (two instructions, volatile: not kept live): at 256 registers the allocator spilled
     // this one value, and its reload -- a scratch load the compiler waits for with vmcnt(0) -- drained the wave's prefetched
     // operand loads at every tile boundary
-    auto kofs_now = [&]() -> int {
+    auto lane_now = [&]() -> int {
         unsigned l;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-        return (int)((l >> 5) << 3);
+        return (int)l;
     };
+    auto kofs_now = [&]() -> int { return (int)(((unsigned)lane_now() >> 5) << 3); };
     const int K1 = G.K1;
     const int n1 = G.gidx ? d3f_dyn(G.N1, G.N1_dev) : 0;
     const int tstride = 8 * (int)gridDim.x;
@@ -561,21 +603,30 @@ gemm_x3r_kernel(const float* __restrict__ A, int lda, const unsigned short* __re
     // that layer's 238 us: g1).  The finished values of one 32-column group therefore go through a 32 x 36-float patch of LDS that
     // belongs to the wave (no barrier: a wave's LDS operations keep their order) and leave as FULL 128-byte lines: lane l writes
     // 16 bytes of row l / 8 + 8 i, eight lanes per row.
-    float* patch = (float*)(gxr_w + (size_t)nkt * TN * (GX_CHUNK * 2)) + wave * (32 * GXR_PS);
+    float* patch = (float*)(gxr_w + patch_ofs) + wave * (32 * GXR_PS);        // (CH == 2: never touched)
     auto finish_tile = [&]() {
         const int gm_a = c_tile * 32 + (lane & 31);
         const bool mok = gm_a < M;
         float rs = 1.f;
         if (E.row_scale && mok) rs = E.row_scale[gm_a];
+        f32x16 acc2;
+        if constexpr (CH != 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
+        }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
+            float fv[16];       // (chained) the lane's finished values of this column group
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int gn = 32 * j + 8 * q + 4 * (lane >> 5);
                 float v[4] = {acc[j][4 * q], acc[j][4 * q + 1], acc[j][4 * q + 2], acc[j][4 * q + 3]};
-                if (mok && gn < N) {
-                    const float4 c4 = *(const float4*)&ep_scale[gn];
-                    const float4 h4 = *(const float4*)&ep_shift[gn];
+                if (mok && (CH || gn < N)) {       // (chained: N = 32 TN)
+                    // (chained: ONE lane address, recomputed here, and immediate offsets -- left to itself the compiler keeps the 8 TN
+                    // addresses of these reads in registers across the whole walk, which is what spilled at TN = 4)
+                    const float* epl = CH ? ep_scale + (kofs_now() >> 1) : nullptr;
+                    const float4 c4 = *(const float4*)(CH ? &epl[32 * j + 8 * q] : &ep_scale[gn]);
+                    const float4 h4 = *(const float4*)(CH ? &epl[32 * TN + 32 * j + 8 * q] : &ep_shift[gn]);
                     const float4 r4 = E.residual ? *(const float4*)&E.residual[(size_t)gm_a * E.ldr + gn] : make_float4(0.f, 0.f, 0.f, 0.f);
                     const float c[4] = {c4.x, c4.y, c4.z, c4.w}, h[4] = {h4.x, h4.y, h4.z, h4.w}, rr[4] = {r4.x, r4.y, r4.z, r4.w};
 #pragma unroll
@@ -585,21 +636,78 @@ gemm_x3r_kernel(const float* __restrict__ A, int lda, const unsigned short* __re
                         v[e] = (E.leaky && !(tt > 0.f)) ? tt * E.alpha : tt;
                     }
                 }
-                *(float4*)&patch[(lane & 31) * GXR_PS + 8 * q + 4 * (lane >> 5)] = make_float4(v[0], v[1], v[2], v[3]);
+                if constexpr (CH != 2) *(float4*)&patch[(lane & 31) * GXR_PS + 8 * q + 4 * (lane >> 5)] = make_float4(v[0], v[1], v[2], v[3]);
+                if constexpr (CH != 0) { fv[4 * q] = v[0]; fv[4 * q + 1] = v[1]; fv[4 * q + 2] = v[2]; fv[4 * q + 3] = v[3]; }
                 acc[j][4 * q] = acc[j][4 * q + 1] = acc[j][4 * q + 2] = acc[j][4 * q + 3] = 0.f;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int cc = 32 * j + 4 * (lane & 7);                  // this lane's four columns of the group
+            if constexpr (CH != 0) {
+                // k-tile j of the second contraction: the lane's quads 2 s, 2 s + 1 are its eight k-values of 16-deep step s
+                const unsigned short* bp2 = (const unsigned short*)(gxr_w + w2_ofs) + j * GX_CHUNK + (lane & 31) * GX_LS + kofs_now();
+                constexpr int PA2[6] = {2, 1, 0, 1, 0, 0}, PB2[6] = {0, 1, 2, 0, 1, 0};       // smallest terms first
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = (lane >> 3) + 8 * i;
-                const float4 o = *(const float4*)&patch[r * GXR_PS + 4 * (lane & 7)];
-                const int gm = c_tile * 32 + r;
-                if (gm < M && cc < N) *(float4*)&C[(size_t)gm * ldc + cc] = o;
+                for (int s = 0; s < 2; ++s) {
+                    const gx_f4 x0 = {fv[8 * s], fv[8 * s + 1], fv[8 * s + 2], fv[8 * s + 3]};
+                    const gx_f4 x1 = {fv[8 * s + 4], fv[8 * s + 5], fv[8 * s + 6], fv[8 * s + 7]};
+                    uint4 pl[3], b2[3];
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) b2[p] = *(const uint4*)(bp2 + p * (32 * GX_LS) + 16 * s);
+                    gx_split8(x0, x1, pl);
+#pragma unroll
+                    for (int prod = 0; prod < 6; ++prod)
+                        acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(gb_bf16x8, b2[PB2[prod]]),
+                                                                       __builtin_bit_cast(gb_bf16x8, pl[PA2[prod]]), acc2, 0, 0, 0);
+                }
             }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            __builtin_amdgcn_wave_barrier();                         // (the patch is rewritten by the next column group)
+            if constexpr (CH != 2) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                const int sl = CH ? lane_now() : lane;                   // (chained: recomputed, as kofs_now, not kept across the walk)
+                const int cc = 32 * j + 4 * (sl & 7);                    // this lane's four columns of the group
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int r = (sl >> 3) + 8 * i;
+                    const float4 o = *(const float4*)&patch[r * GXR_PS + 4 * (sl & 7)];
+                    const int gm = c_tile * 32 + r;
+                    if (gm < M && (CH || cc < N)) *(float4*)&C[(size_t)gm * ldc + cc] = o;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                __builtin_amdgcn_wave_barrier();                         // (the patch is rewritten by the next column group)
+            }
+        }
+        if constexpr (CH != 0) {       // ---- the 32-column result: second epilogue, then out ----
+            const float* ep2 = ep_scale + 64 * TN;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int gn = 8 * q + 4 * (lane >> 5);
+                float v[4] = {acc2[4 * q], acc2[4 * q + 1], acc2[4 * q + 2], acc2[4 * q + 3]};
+                const float4 c4 = *(const float4*)&ep2[gn];
+                const float4 h4 = *(const float4*)&ep2[32 + gn];
+                const float c[4] = {c4.x, c4.y, c4.z, c4.w}, h[4] = {h4.x, h4.y, h4.z, h4.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float tt = v[e] * c[e] + h[e];
+                    v[e] = (H.leaky && !(tt > 0.f)) ? tt * H.alpha : tt;
+                }
+                if constexpr (CH == 2) {
+                    if (mok) *(float4*)&H.C2[(size_t)gm_a * H.ldc2 + gn] = make_float4(v[0], v[1], v[2], v[3]);
+                } else {
+                    *(float4*)&patch[(lane & 31) * GXR_PS + gn] = make_float4(v[0], v[1], v[2], v[3]);
+                }
+            }
+            if constexpr (CH == 1) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                const int sl = lane_now();
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int r = (sl >> 3) + 8 * i;
+                    const float4 o = *(const float4*)&patch[r * GXR_PS + 4 * (sl & 7)];
+                    const int gm = c_tile * 32 + r;
+                    if (gm < M) *(float4*)&H.C2[(size_t)gm * H.ldc2 + 4 * (sl & 7)] = o;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
         }
         c_tile += tstride;
     };
@@ -633,4 +741,19 @@ gemm_x3r_kernel(const float* __restrict__ A, int lda, const unsigned short* __re
 #undef GXR_STEP
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(rA0), "+v"(rA1), "+v"(rA2), "+v"(rA3), "+v"(rB0), "+v"(rB1), "+v"(rB2), "+v"(rB3), "+v"(rC0),
                  "+v"(rC1), "+v"(rC2), "+v"(rC3) : : "memory");
+}
+
+template <int TN>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
+gemm_x3r_kernel(const float* __restrict__ A, int lda, const unsigned short* __restrict__ Wx, int nkt, float* __restrict__ C, int ldc,
+                int M, int N, GemmEpi E, const int* __restrict__ M_dev, GemmGather G) {
+    gemm_x3r_body<TN, 0>(A, lda, Wx, nkt, C, ldc, M, N, E, M_dev, G, GemmChain{});
+}
+
+// the chained form: N = 32 TN columns contracted on to 32 (STORE: the N-column tile is written too)
+template <int TN, bool STORE>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
+gemm_x3r_chain_kernel(const float* __restrict__ A, int lda, const unsigned short* __restrict__ Wx, int nkt, float* __restrict__ C,
+                      int ldc, int M, int N, GemmEpi E, const int* __restrict__ M_dev, GemmGather G, GemmChain H) {
+    gemm_x3r_body<TN, STORE ? 1 : 2>(A, lda, Wx, nkt, C, ldc, M, N, E, M_dev, G, H);
 }

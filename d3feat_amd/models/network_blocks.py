@@ -162,6 +162,11 @@ def _check_trainable(features, block):
 def last_unary_block(layer_ind, inputs, features, radius, fdim, config, training):
     """:194-205: 1x1 convolution to 32 channels, no batch norm / activation."""
     w = weight_variable([int(features.shape[1]), 32])
+    if isinstance(features, ops.PendingUnary):
+        # the decoder block before this one was not launched: both contractions in one launch, its 64-column tensor never written
+        return features.chain(w)
+    if isinstance(features, ops.UpsampleCat):
+        features = features.materialize()
     with ops.f32_output():      # descriptors and scores are computed from fp32 values whatever the feature storage
         return conv_ops.unary_convolution(features, w)
 
@@ -173,10 +178,17 @@ def unary_block(layer_ind, inputs, features, radius, fdim, config, training):
         vs = _vs()
         w = vs.parameter(vs.weight_variable([int(features.shape[1]), fdim]))
         return _bn_train(unary_trainable(features, w), config.use_batch_norm, config.batch_norm_momentum, leaky=True)
+    if isinstance(features, ops.PendingUnary):
+        features = features.materialize()
     if isinstance(features, ops.UpsampleCat):
         # decoder: nearest upsampling + skip concatenation (models/D3Feat.py:55-63) fused into this contraction
         vs = _vs()
         w = vs.weight_variable([int(features.shape[1]), fdim])
+        if ops.pending_unary_ok(features, fdim):
+            # level 0 (resident form): stays pending -- `last_unary` chains its contraction onto this one (ops.gemm_chain); any
+            # other consumer materialises it, which is the launch below
+            e = _epilogue(fdim, config, True)
+            return ops.PendingUnary(features, vs.tensor(w), e['col_scale'], e['col_shift'], True, 0.2)
         if ops.upsample_split_ok(features, fdim):
             # ... with the upsampled half contracted once per COARSE row and gathered in the fine level's epilogue
             if config.use_batch_norm:
@@ -241,11 +253,50 @@ def _resnetb_train(layer_ind, inputs, features, radius, fdim, config):
         return _bn_train(unary_trainable(x, w3), bn, momentum, leaky=True, residual=shortcut)
 
 
+# While assemble_CNN_blocks runs a block that is followed by a resnetb* block at the SAME level: (depth of the variable scopes
+# around the blocks, scope name of the following block).  _resnetb then chains that block's conv1 onto its own last contraction.
+_NEXT_RESNETB = None
+_CHAINED = '_d3f_chained_conv1'
+
+
+def _chain_next_conv1(x, shortcut, W, shift, fdim, config):
+    """conv3 + shortcut of a resnetb block AND the conv1 of the resnetb* block that follows, in one launch (ops.gemm_chain): the
+    128-column tensor is stored as ever, the following block does not read it back for its conv1.  The following block's
+    `conv1/weights` and batch-norm variables are created here -- the very next variables the reference creates -- and the result is
+    attached to the returned tensor under that weight's name and epilogue.  -> the block's output, or None (launch as ever)."""
+    if _NEXT_RESNETB is None or fdim // 2 != 32 or not isinstance(x, torch.Tensor) or not isinstance(shortcut, torch.Tensor):
+        return None
+    M, K = int(x.shape[0]), int(x.shape[1]) + int(shortcut.shape[1])
+    ok = all(t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+             and t.shape[1] % 32 == 0 for t in (x, shortcut))
+    if not ok or not ops.gemm_chain_ok(M, 2 * fdim, K, True, int(getattr(x, 'n_hint', 0) or 0)):
+        return None
+    vs = _vs()
+    depth, scope = _NEXT_RESNETB
+    saved = vs._scope
+    vs._scope = saved[:depth] + [scope, 'conv1']
+    try:
+        wn = vs.weight_variable([2 * fdim, fdim // 2])
+        e = _epilogue(fdim // 2, config, True)
+    finally:
+        vs._scope = saved
+    out, x_next = ops.gemm_chain(x, W, vs.tensor(wn), skip=shortcut, store_first=True, col_shift=shift, leaky=True, alpha=0.2,
+                                 col_scale2=e['col_scale'], col_shift2=e['col_shift'], leaky2=True, alpha2=0.2)
+    setattr(out, _CHAINED, (wn, e['col_scale'], e['col_shift'], x_next))
+    return out
+
+
 def _resnetb(layer_ind, inputs, features, radius, fdim, config, strided, deformable=False):
     cin = int(features.shape[1])
     with variable_scope('conv1'):
-        w = weight_variable([cin, fdim // 2])
-        x = conv_ops.unary_convolution(features, w, epilogue=_epilogue(fdim // 2, config, True))
+        vs = _vs()
+        wn = vs.weight_variable([cin, fdim // 2])
+        e = _epilogue(fdim // 2, config, True)
+        att = features.__dict__.pop(_CHAINED, None) if isinstance(features, torch.Tensor) else None
+        if att is not None and ops.GEMM_CHAIN and att[0] == wn and att[1] is e['col_scale'] and att[2] is e['col_shift']:
+            x = att[3]          # computed by the block before, chained onto its last contraction (_chain_next_conv1)
+        else:
+            x = conv_ops.unary_convolution(features, vs.tensor(wn), epilogue=e)
     with variable_scope('conv2'):
         w = weight_variable([config.num_kernel_points, fdim // 2, fdim // 2])
         if strided:
@@ -282,7 +333,8 @@ def _resnetb(layer_ind, inputs, features, radius, fdim, config, strided, deforma
         vs = _vs()
         if fuse:
             W, shift = vs.stacked_branches(w3, bn3, sc_w, sc_bn)
-            return ops.gemm_cat2(x, shortcut, W, col_shift=shift, leaky=True, alpha=0.2)
+            out = None if (strided or ops.BF16_CONTRACTION) else _chain_next_conv1(x, shortcut, W, shift, fdim, config)
+            return out if out is not None else ops.gemm_cat2(x, shortcut, W, col_shift=shift, leaky=True, alpha=0.2)
         # leaky_relu(batch_norm(conv3) + shortcut): the add and the activation ride in the contraction's epilogue
         return conv_ops.unary_convolution(x, vs.tensor(w3), epilogue=_epilogue(2 * fdim, config, True, residual=shortcut))
 
@@ -321,7 +373,8 @@ def nearest_upsample_block(layer_ind, inputs, features, radius, fdim, config, tr
 
 
 def _materialized(block_fn):
-    """Blocks other than `unary` take a real tensor: materialise a pending nearest-upsample concatenation first."""
+    """Blocks other than `unary` / `last_unary` take a real tensor: materialise a pending nearest-upsample concatenation (or a pending
+    unary block over one) first."""
     def wrapped(layer_ind, inputs, features, radius, fdim, config, training):
         if isinstance(features, ops.UpsampleCat):
             features = features.materialize()
@@ -338,7 +391,7 @@ def get_block_ops(block_name):
              'resnetb_strided': resnetb_strided_block, 'resnetb_deformable': resnetb_deformable_block,
              'resnetb_deformable_strided': resnetb_deformable_strided_block, 'nearest_upsample': nearest_upsample_block}
     if block_name in table:
-        return table[block_name] if block_name == 'unary' else _materialized(table[block_name])
+        return table[block_name] if block_name in ('unary', 'last_unary') else _materialized(table[block_name])
     known_unsupported = ('simple_strided', 'resnet', 'resnetb_light', 'inception_deformable',
                          'resnetb_light_strided', 'inception_deformable_strided', 'vgg',
                          'max_pool', 'max_pool_wide', 'global_average', 'simple_upsample', 'resnetb_upsample')
@@ -357,13 +410,22 @@ def assemble_CNN_blocks(inputs, config, dropout_prob):
     F = []
     training = dropout_prob < 0.99
     block_in_layer = 0
-    for block in config.architecture:
+    global _NEXT_RESNETB
+    for i, block in enumerate(config.architecture):
         if any(tmp in block for tmp in ('pool', 'strided', 'upsample', 'global')):
             F += [features]
         if 'upsample' in block:
             break
-        with variable_scope('layer_{:d}/{:s}_{:d}'.format(layer, block.replace('_deformable', ''), block_in_layer)):
-            features = get_block_ops(block)(layer, inputs, features, r, fdim, config, training)
+        # a resnetb* block that follows at the same level: this block may chain that block's conv1 (_chain_next_conv1)
+        nxt = config.architecture[i + 1] if i + 1 < len(config.architecture) else ''
+        same_level = not ('pool' in block or 'strided' in block)
+        if same_level and nxt.startswith('resnetb') and not training:
+            _NEXT_RESNETB = (len(_vs()._scope), 'layer_{:d}/{:s}_{:d}'.format(layer, nxt.replace('_deformable', ''), block_in_layer + 1))
+        try:
+            with variable_scope('layer_{:d}/{:s}_{:d}'.format(layer, block.replace('_deformable', ''), block_in_layer)):
+                features = get_block_ops(block)(layer, inputs, features, r, fdim, config, training)
+        finally:
+            _NEXT_RESNETB = None
         block_in_layer += 1
         if 'pool' in block or 'strided' in block:
             layer += 1

@@ -878,6 +878,122 @@ def gemm_cat2(A1, A2, W, col_scale=None, col_shift=None, leaky=False, alpha=0.2)
     return _tag(out, A1)
 
 
+# Chained contractions (D3F_GEMM_CHAIN=0: every launch as before).  Two level-0 launches of the resident form write a tall tensor that
+# the very next launch reads back and contracts to 32 columns: the decoder's last unary block before `last_unary` (its 64-column
+# output has no other consumer) and a resnetb block's conv3 + shortcut before the next block's conv1.  d3f_gemm_x3_chain computes the
+# second product from the first one's accumulators (csrc/gemm_x3.h): one launch, the tall tensor not written / not read back.
+GEMM_CHAIN = os.environ.get("D3F_GEMM_CHAIN", "1") != "0"
+CHAIN_MIN_ROWS = None       # tests only: expected rows from which gemm_chain_ok answers as if the call were a tall (resident) one
+
+
+def packed_x3_chain_weights(W2):
+    """W2 f32[64 or 128, 32] (contiguous rows) -> the pre-split planes d3f_gemm_x3_chain stages for its SECOND product: the layout of
+    packed_x3_weights with the k rows of every 16-block in the kernel's accumulator order; made once per (weight tensor, view, version)."""
+    lib = _lib.load()
+    return _packed_weights(W2, "_d3f_x3c", lambda K, N: torch.empty((int(lib.d3f_gemm_x3_packed_bytes(K, N)) // 2,), dtype=torch.int16,
+                                                                    device=W2.device), lib.d3f_gemm_pack_x3_chain, "gemm_pack_x3_chain")
+
+
+def gemm_chain_ok(M, N, K, store_first, hint=0):
+    """Is a contraction of M rows, K -> N columns, followed by one to 32 columns, taken as ONE chained launch?  fp32 only, and only
+    where the first contraction alone would run the resident form of d3f_gemm_x3 (the library's predicate d3f_gemm_x3_chain_ok)."""
+    if not (GEMM_CHAIN and GEMM_X3) or BF16_CONTRACTION or BF16_FEATURES or M > X3_MAX_ROWS:
+        return False
+    rows = hint if 0 < hint < M else M
+    if CHAIN_MIN_ROWS is not None and rows >= CHAIN_MIN_ROWS:
+        M, hint = max(M, 65536), 0
+    return bool(_lib.load().d3f_gemm_x3_chain_ok(M, N, K, 1 if store_first else 0, hint))
+
+
+def _chain_addressable(N, *operands):
+    """float4-addressable fp32 operands ((tensor, leading dimension, columns) triples) with whole k-tiles: what _route asks of a call
+    before it hands it to d3f_gemm_x3."""
+    for t, ld, cols in operands:
+        if t is not None and (t.dtype != torch.float32 or cols % 32 or ld % 4 or t.data_ptr() % 16):
+            return False
+    return N % 4 == 0
+
+
+def gemm_chain(A, W, W2, idx=None, skip=None, store_first=True, col_scale=None, col_shift=None, leaky=False, alpha=0.2,
+               col_scale2=None, col_shift2=None, leaky2=False, alpha2=0.2, out=None, out2=None):
+    """Y = act(([ A[idx[:,0]] (A itself when idx is None) | skip ] @ W) * col_scale + col_shift), out2 = act2((Y @ W2) * col_scale2 +
+    col_shift2) in ONE launch of the resident form, whatever the row count.  W f32[K, N] with N = 64 or 128, W2 f32[N, 32].
+    -> (Y, out2); Y is None -- and never written -- with store_first=False.  Rows at and beyond the device-resident row count of a
+    capacity-sized operand are not written."""
+    lib = _lib.load()
+    A, lda = _rows(_req(A, torch.float32, "A"), "A")
+    W, _ = _rows(_req(W, torch.float32, "W"), "W")
+    W2, _ = _rows(_req(W2, torch.float32, "W2"), "W2")
+    C1, C2, lds, ldi = A.shape[1], 0, 0, 0
+    src = A
+    if idx is not None:
+        idx, ldi = _rows(_req(idx, torch.int32, "idx"), "idx")
+        src = idx
+    if skip is not None:
+        skip, lds = _rows(_req(skip, torch.float32, "skip"), "skip")
+        C2 = skip.shape[1]
+    M, K, N, dev = src.shape[0], C1 + C2, W.shape[1], A.device
+    if W.shape[0] != K or tuple(W2.shape) != (N, 32) or not (W.is_contiguous() and W2.is_contiguous()) or (skip is not None and skip.shape[0] != M):
+        raise ValueError("gemm_chain: operands %d + %d columns, W %s, W2 %s" % (C1, C2, tuple(W.shape), tuple(W2.shape)))
+    if not _chain_addressable(N, (A, lda, C1), (skip, lds, C2)):
+        raise ValueError("gemm_chain: operands must be float32, 16-byte aligned, with whole k-tiles of 32 columns")
+    for v, n, name in ((col_scale, N, "col_scale"), (col_shift, N, "col_shift"), (col_scale2, 32, "col_scale2"), (col_shift2, 32, "col_shift2")):
+        if v is not None and (_req(v, torch.float32, name).numel() != n or not v.is_contiguous() or v.data_ptr() % 16):
+            raise ValueError("gemm_chain: %s must be a contiguous, 16-byte aligned vector of %d" % (name, n))
+    Y, ldc = None, N
+    if store_first:
+        Y = torch.empty((M, N), dtype=torch.float32, device=dev) if out is None else out
+        Y, ldc = _rows(_req(Y, torch.float32, "out"), "out")
+        if tuple(Y.shape) != (M, N):
+            raise ValueError("gemm_chain: out must be [%d, %d]" % (M, N))
+    out2 = torch.empty((M, 32), dtype=torch.float32, device=dev) if out2 is None else out2
+    out2, ldc2 = _rows(_req(out2, torch.float32, "out2"), "out2")
+    if tuple(out2.shape) != (M, 32):
+        raise ValueError("gemm_chain: out2 must be [%d, 32]" % M)
+    Wp, W2p = packed_x3_weights(W), packed_x3_chain_weights(W2)
+    # (recorded under the resident family with the FIRST contraction's shape: the chained product is not in the record's flops)
+    with _timed("gemm_x3r", dict(M=M, N=N, K=K), dev):
+        rc = lib.d3f_gemm_x3_chain(A.data_ptr(), A.shape[0], lda, C1, _ptr(idx), ldi, _ptr(skip), lds, C2, Wp.data_ptr(), _ptr(Y), ldc, M, N,
+                                   None, _ptr(col_scale), _ptr(col_shift), None, 0, 1 if leaky else 0, float(alpha), W2p.data_ptr(),
+                                   _ptr(col_scale2), _ptr(col_shift2), 1 if leaky2 else 0, float(alpha2), out2.data_ptr(), ldc2,
+                                   _nd(src), _nd(A), _stream(dev))
+    _lib.check(rc, "gemm_x3_chain")
+    return (_tag(Y, src) if Y is not None else None), _tag(out2, src)
+
+
+class PendingUnary(UpsampleCat):
+    """The not-yet-launched unary block act(([ x'[inds[:,0]] | skip ] @ W) * col_scale + col_shift) over a pending concatenation `u`
+    (the level-0 decoder block, 64 columns).  `last_unary` consumes it with one chained launch (chain) and the 64-column tensor is
+    never written; every other consumer calls .materialize(), the ordinary launch, and sees the tensor it always saw."""
+
+    def __init__(self, u, W, col_scale, col_shift, leaky, alpha):
+        self.u, self.W, self.col_scale, self.col_shift, self.leaky, self.alpha = u, W, col_scale, col_shift, leaky, alpha
+        self.shape = (u.shape[0], W.shape[1])
+        self.device = u.device
+        self.dtype = torch.float32
+        _tag(self, u.inds)
+
+    def materialize(self):
+        return gemm_upsample_cat(self.u, self.W, col_scale=self.col_scale, col_shift=self.col_shift, leaky=self.leaky, alpha=self.alpha)
+
+    def chain(self, W2):
+        u = self.u
+        return gemm_chain(u.x, self.W, W2, idx=u.inds, skip=u.skip, store_first=False, col_scale=self.col_scale,
+                          col_shift=self.col_shift, leaky=self.leaky, alpha=self.alpha)[1]
+
+
+def pending_unary_ok(u, N):
+    """Does the unary block (N columns) over the pending concatenation `u` stay pending for a chained `last_unary`?"""
+    if not isinstance(u, UpsampleCat) or isinstance(u, PendingUnary) or u.x.dim() != 2 or u.inds.dim() != 2:
+        return False
+    C1, C2 = u.x.shape[1], (u.skip.shape[1] if u.skip is not None else 0)
+    if u.skip is not None and (u.skip.dim() != 2 or u.skip.stride(1) != 1):
+        return False
+    if u.x.stride(1) != 1 or u.inds.dtype != torch.int32 or not _chain_addressable(N, (u.x, u.x.stride(0), C1), (u.skip, u.skip.stride(0) if C2 else 0, C2)):
+        return False
+    return gemm_chain_ok(u.inds.shape[0], N, C1 + C2, False, int(getattr(u.inds, "n_hint", 0) or 0))
+
+
 def _kp_front(what, query_points, support_points, neighbors_indices, features, K_points, K_values, KP_extent, KP_influence,
               aggregation_mode, col_scale=None, col_shift=None, residual=None, leaky=False, alpha=0.2, row_pos=True, feat=_feat):
     """The operand preparation every KPConv wrapper shares -> (gather, kpar, row_pos, epi, tail, f): the argument groups of the
@@ -1044,6 +1160,7 @@ def packed_kpconv_weights_x3(K_values):
 
 # every packed copy that can ride on a weight tensor: its slot and the packer that (re-)makes it
 _PACKERS = (("_d3f_bf16t", packed_bf16_weights), ("_d3f_f32t", packed_f32t_weights), ("_d3f_x3", packed_x3_weights),
+            ("_d3f_x3c", packed_x3_chain_weights),
             ("_d3f_packed", packed_kpconv_weights), ("_d3f_packed_x3", packed_kpconv_weights_x3))
 
 

@@ -508,6 +508,25 @@ int d3f_gemm_x3_gres(const float* A, int N1, int lda, int C1, const int* idx, in
                      const int* res_rows_dev, int leaky, float alpha, void* workspace, size_t workspace_bytes, const int* M_dev,
                      const int* N1_dev, int M_hint, void* stream);
 
+/* d3f_gemm_x3's resident-W form with the NEXT contraction of the network chained in registers (d3feat_amd/csrc/gemm_x3.h):
+ *   Y  = act((([ A[idx] | skip ] @ W) * row_scale) * col_scale + col_shift + residual)     [M, N], N = 64 or 128; stored iff C != NULL
+ *   C2 = act2((Y @ W2) * col_scale2 + col_shift2)                                          [M, 32] (ldc2 >= 32, a multiple of 4)
+ * One launch instead of two; Y is not written (C == NULL) or not read back (C != NULL).  Y is the fp32 value d3f_gemm_x3 stores, split
+ * exactly into three bf16 planes for the second product: only the order of the second sum differs from the two-launch form.
+ * Wx = d3f_gemm_pack_x3(W); W2x = d3f_gemm_pack_x3_chain(W2 f32[N, 32]), d3f_gemm_x3_packed_bytes(N, 32) bytes: the same planes with the
+ * k rows of every 16-block in the order the kernel holds its finished columns.  Always the resident form, whatever M is.
+ * d3f_gemm_x3_chain_ok(M, N, K, store_first, M_hint): 1 where d3f_gemm_x3 would take its resident form for the first contraction AND
+ * the chained LDS image (W, W2, the output patches when the first output is stored) fits 160 KB -- where the chained launch replaces
+ * two launches of the same family; else 0.  D3F_ERR_ARG on top of d3f_gemm_x3's rules: N other than 64 / 128, C2 / W2x missing or not
+ * 16-byte aligned, ldc2 < 32 or not a multiple of 4, an LDS image beyond 160 KB. */
+int d3f_gemm_pack_x3_chain(const float* W2, int ldb, int K, int N, void* W2x, void* stream);
+int d3f_gemm_x3_chain_ok(int M, int N, int K, int store_first, int M_hint);
+int d3f_gemm_x3_chain(const float* A, int N1, int lda, int C1, const int* idx, int ld_idx, const float* skip, int lds, int C2cols,
+                      const void* Wx, float* C, int ldc, int M, int N, const float* row_scale, const float* col_scale,
+                      const float* col_shift, const float* residual, int ldr, int leaky, float alpha, const void* W2x,
+                      const float* col_scale2, const float* col_shift2, int leaky2, float alpha2, float* C2, int ldc2,
+                      const int* M_dev, const int* N1_dev, void* stream);
+
 /* bf16-operand form of the contractions (BASELINE.json configs[4]: batched inference, bf16 MFMA contraction): the operator of
  * d3f_gemm_f32 / d3f_gemm_upsample_cat_f32 -- A f32[M, C1] (rows in place when idx == NULL, else the gathered rows
  * x'[idx[m,0]], zero row for indices outside [0, N1)), optional second operand skip f32[M, C2], K = C1 + C2, same epilogue --
