@@ -948,7 +948,9 @@ extern "C" int d3f_gemm_x3_gres(const float* A, int N1, int lda, int C1, const i
 //   C2 = act2((Y @ W2) * col_scale2 + col_shift2)                                             [M, 32]
 // Wx = d3f_gemm_pack_x3(W), W2x = d3f_gemm_pack_x3_chain(W2 f32[N, 32]).  Y is the fp32 value d3f_gemm_x3 would store, split exactly
 // for the second product.  D3F_ERR_ARG: d3f_gemm_x3's rules, N other than 64 / 128, C2 / W2x missing or misaligned, ldc2 < 32 or not
-// a multiple of 4, or an LDS image beyond 160 KB (K <= 96 with N = 128, K <= 224 stored / K <= 288 not stored with N = 64).
+// a multiple of 4, or an LDS image beyond 160 KB (gemm_x3r_chain_lds_bytes: K <= 96 stored / K <= 128 not stored with N = 128, K <= 224
+// stored / K <= 288 not stored with N = 64; at K = 288 d3f_gemm_x3 itself has no resident form, so d3f_gemm_x3_chain_ok answers 0
+// there and only a direct call reaches that image).
 extern "C" int d3f_gemm_x3_chain(const float* A, int N1, int lda, int C1, const int* idx, int ld_idx, const float* skip, int lds, int C2cols,
                                  const void* Wx, float* C, int ldc, int M, int N, const float* row_scale, const float* col_scale,
                                  const float* col_shift, const float* residual, int ldr, int leaky, float alpha, const void* W2x,

@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY.  Seeded operands and integer / float64 expectations for the branch tests of the contraction family
 (tests/test_gpu_gemm_branches.py on the GPU, tests/test_gemm_cases.py on the CPU): d3f_gemm_f32, d3f_gemm_upsample_cat_f32,
-d3f_gemm_f32t, d3f_gemm_bf16, d3f_gemm_x3, d3f_gemm_x3_gres and the three pack kernels (csrc/gemm_f32.hip, gemm_dma.h, gemm_x3.h,
-gemm_common.h).  numpy only; no kernel has a part in any expectation, and NO TOLERANCE exists anywhere: the operands are chosen so
+d3f_gemm_f32t, d3f_gemm_bf16, d3f_gemm_x3, d3f_gemm_x3_gres, d3f_gemm_x3_chain and the four pack entry points (csrc/gemm_f32.hip,
+gemm_dma.h, gemm_x3.h, gemm_common.h).  numpy only; no kernel has a part in any expectation, and NO TOLERANCE exists anywhere: the operands are chosen so
 that fp32 arithmetic is exact, whatever the order of the sums.
 
   lattice   A, skip, x, W and the residual hold small integers, row_scale / col_scale come from {0.5, 1, 2, 4}, col_shift holds
@@ -15,14 +15,23 @@ that fp32 arithmetic is exact, whatever the order of the sums.
             rounding differs from truncation).
   leaky     every 32 x 32 output tile holds both signs and exact zeros (a zero column of W per column group whose shift is zero; a
             group of one column copies column 0 of the operand, zero in every third row).
+  chain     d3f_gemm_x3_chain: a first-level case (built by the x3 builder itself: its expectation IS the x3 expectation) and on top
+            of it W2 f32[N, 32] in small integers with one zero column, cs2 from {0.5, 1, 2, 4}, ch2 in integers and halves,
+            want2 = act2((Y @ W2) cs2 + ch2) in float64 from the exact first output Y.  |A| <= 3, |W| <= 2, |W2| <= 2 (CHAIN_RANGES):
+            the first-level budget of ranges() is for ONE product.  Exactness of the second level is COMPUTED and recorded (exact2):
+            with u the finest power of two that divides every Y, max(|Y| @ |W2|) / u < 2^24, and every intermediate of the second
+            epilogue equals its own float32 rounding.  select2: W and W2 both 0/1 selections, identity epilogues -- every element
+            of the second output is one full-mantissa operand of A, which holds only if the finished value is split into three
+            planes without loss and the W2 image's k order is the kernel's.
   poison    poisoned() writes NaN / Inf into every float the contract says is not read: rows of A / skip / residual / row_scale past
             *M_dev, rows of x past *N1_dev, rows of a gathered residual past *res_rows_dev, the columns between the rows of every
             operand whose leading dimension exceeds its width.  Outputs are PAD rows longer than documented, ldc = N + 4 where the
             case says so, pre-filled with SENT.
 
-The host plans are restated below (gemm_plan, gemm_bf16_split, gemm_x3_cost / gemm_x3_plan, gemm_x3_resident); every case records
-the branch it MEANS to exercise (kernel instance, S, k-tiles of every slice -- written down from the shape tables, not computed
-by the restatement) and tests/test_gemm_cases.py checks that the restatement, and where it is built the library, agree."""
+The host plans are restated below (gemm_plan, gemm_bf16_split, gemm_x3_cost / gemm_x3_plan, gemm_x3_resident,
+gemm_x3r_chain_lds_bytes / gemm_x3_chain_ok); every case records the branch it MEANS to exercise (kernel instance, S, k-tiles of
+every slice -- written down from the shape tables, not computed by the restatement) and tests/test_gemm_cases.py checks that the
+restatement, and where it is built the library, agree."""
 import numpy as np
 
 SENT = np.float32(-7.25e9)
@@ -94,6 +103,42 @@ def gemm_x3_resident(M, N, K, hint=0):
     return int(NG in (1, 2, 4) and lds <= 160 * 1024 and m_eff >= 65536)
 
 
+LDS_LIMIT = 160 * 1024
+
+
+def gemm_x3r_chain_lds_bytes(nkt, NG, store_first):
+    """LDS of gemm_x3r_chain_kernel: W, the W2 image (one k-tile per column group), the eight output patches when the first output
+    is stored, both epilogues' vectors"""
+    return (nkt + 1) * NG * X3_CHUNK_BYTES + (8 * 32 * 36 * 4 if store_first else 0) + 2 * 128 * 4 + 2 * 32 * 4
+
+
+def gemm_x3_chain_accepts(N, K, store_first):
+    """what the entry point d3f_gemm_x3_chain launches (whatever M is)"""
+    return int(N in (64, 128) and K >= GX_BK and K % GX_BK == 0 and gemm_x3r_chain_lds_bytes(K // GX_BK, N // 32, store_first) <= LDS_LIMIT)
+
+
+def gemm_x3_chain_ok(M, N, K, store_first, hint=0):
+    """d3f_gemm_x3_chain_ok: the router's predicate -- the call is one of d3f_gemm_x3's resident form AND the chained image fits"""
+    return int(bool(gemm_x3_resident(M, N, K, hint)) and bool(gemm_x3_chain_accepts(N, K, store_first)))
+
+
+def chain_largest_k(N, store_first):
+    """the largest K whose chained LDS image fits, from the formula"""
+    K = GX_BK
+    while gemm_x3r_chain_lds_bytes(K // GX_BK + 1, N // 32, store_first) <= LDS_LIMIT:
+        K += GX_BK
+    return K
+
+
+# the four instances, written down: (N, first output stored) -> kernel
+CHAIN_KERNELS = {(64, False): "gemm_x3r_chain_kernel<2,false>", (64, True): "gemm_x3r_chain_kernel<2,true>",
+                 (128, False): "gemm_x3r_chain_kernel<4,false>", (128, True): "gemm_x3r_chain_kernel<4,true>"}
+
+
+def chain_kernel(N, store_first):
+    return CHAIN_KERNELS[(N, bool(store_first))]
+
+
 def slab_bytes(S, M, N):
     """what a *_workspace_bytes function answers for S slices"""
     return (S * M * N * 4 + 255) // 256 * 256 + 256 if S > 1 else 256
@@ -107,6 +152,10 @@ def slices(nt, tps):
 def planned_branch(spec):
     """(kernel instance, S, k-tiles per slice) the restated plans give for a case"""
     e, M, N, K, hint = spec["entry"], spec["M"], spec["N"], spec["C1"] + spec["C2"], spec.get("hint", 0)
+    if e == "chain":
+        if not gemm_x3_chain_accepts(N, K, spec["store"]):
+            return None, 0, ()
+        return "gemm_x3r_chain_kernel<%d,%s>" % (N // 32, "true" if spec["store"] else "false"), 1, (K // 32,)
     if e in ("x3", "x3_gres"):
         if e == "x3" and gemm_x3_resident(M, N, K, hint):
             return "gemm_x3r_kernel<%d>" % cdiv(N, 32), 1, (K // 32,)
@@ -186,7 +235,8 @@ def zero_columns(N):
 
 SPEC_DEFAULTS = dict(C2=0, gather=False, ld_idx=1, n1=0, epi=0, col=False, leaky=False, alpha=0.25, kind="lattice", hint=0,
                      lda_pad=0, lds_pad=0, ldb_pad=0, ldc_pad=0, ldr_pad=0, a_off=0, b_off=0, a_bf16=0, c_bf16=0,
-                     gres=False, ld_res_idx=1, res_rows=0, seed=0)
+                     gres=False, ld_res_idx=1, res_rows=0, seed=0, amax=0, wmax=0,
+                     store=False, cs2=False, ch2=False, leaky2=False, alpha2=0.25, ldc2_pad=4, w2="lattice", w2max=2)
 
 
 def spec(entry, M, N, C1, **kw):
@@ -212,12 +262,17 @@ def shadow_indices(rng, M, n1, n1_dev, ld):
 def build(s):
     """-> the case of a spec: clean operands (no poison), the expectation and its pre-activation value.
     Effective operand: Aeff[m] = [ x'[idx[m, 0]] (x[m] without a gather) | skip[m] ]; t = (Aeff @ W) rs cs + ch + res; out = act(t)."""
+    if s["entry"] == "chain":
+        return build_chain(s)
     M, N, C1, C2 = s["M"], s["N"], s["C1"], s["C2"]
     K = C1 + C2
     rng = np.random.default_rng([s["seed"], M, N, C1, C2, s["epi"], len(s["entry"])])
     bf = s["entry"] == "bf16"
     epilogue = bool(s["col"] or s["epi"] or s["leaky"])
     amax, wmax = ranges(K, epilogue, bf)
+    if s["amax"]:                                       # (a case that budgets its own magnitudes: the chained ones)
+        assert s["amax"] <= amax and s["wmax"] <= wmax
+        amax, wmax = s["amax"], s["wmax"]
     c = dict(spec=s, K=K, amax=amax, wmax=wmax)
     n1 = s["n1"] if s["gather"] else M
     n1_dev = s.get("n1_dev")
@@ -348,6 +403,72 @@ def build(s):
     return c
 
 
+def first_level_spec(s):
+    """the d3f_gemm_x3 case with the first-level operands of a chained case (the resident walk takes it wherever M >= 65536)"""
+    return dict(s, entry="x3", kind="select" if s["kind"] == "select2" else s["kind"], intent=None, hint=0)
+
+
+def lattice_unit(v, finest=12):
+    """the largest 2^-k (k = 0 .. finest) of which every element of v is an integer multiple; None: there is none"""
+    q = v * float(1 << finest)
+    n = q.astype(np.int64)
+    if not (n == q).all():
+        return None
+    bits = int(np.bitwise_or.reduce(np.abs(n), axis=None))
+    low = (bits & -bits).bit_length() - 1 if bits else finest          # the lowest bit set anywhere
+    return 2.0 ** (min(low, finest) - finest)
+
+
+def build_chain(s):
+    """-> the case of a `chain` spec: the first-level case as build() makes it for d3f_gemm_x3 (c["first"]; every key of it is here
+    too, want = Y), and on top W2, cs2, ch2, pre2, want2 = act2((Y @ W2) cs2 + ch2), exact2, unit2 (the lattice unit u of Y),
+    bound2 (max(|Y| @ |W2|) / u)"""
+    f = build(first_level_spec(s))
+    M, N = s["M"], s["N"]
+    rng = np.random.default_rng([s["seed"], M, N, s["C1"], s["C2"], s["epi"], 1 + 2 * s["cs2"] + 4 * s["ch2"], 77])
+    Y = f["want"].astype(np.float64)                    # the exact first output
+    zc2 = zero_columns(32)
+    sel2 = None
+    if s["kind"] == "select2" or s["w2"] == "select":
+        sel2 = rng.integers(0, N, 32)
+        W2 = np.zeros((N, 32), np.float32)
+        W2[sel2, np.arange(32)] = 1.0
+    else:
+        W2 = rng.integers(-s["w2max"], s["w2max"] + 1, (N, 32)).astype(np.float32)
+    cs2 = rng.choice([0.5, 1.0, 2.0, 4.0], 32).astype(np.float32) if s["cs2"] else None
+    ch2 = (rng.integers(-255, 256, 32) * 0.5).astype(np.float32) if s["ch2"] else None
+    if s["kind"] != "select2":
+        W2[:, zc2] = 0.0
+        if ch2 is not None:
+            ch2[zc2] = 0.0
+
+    def is32(v):
+        return bool((v.astype(np.float32).astype(np.float64) == v).all())
+    unit2 = bound2 = None
+    if sel2 is not None:
+        # one operand per output, taken: the three planes of a value add up to it in the kernel's order (smallest first), the other
+        # 32 TN - 1 products of the sum are zeros
+        t = np.where((W2 != 0).any(0), Y[:, sel2], 0.0)
+        exact2 = f["exact"]
+    else:
+        t = Y @ W2.astype(np.float64)
+        unit2 = lattice_unit(Y)
+        bound2 = float((np.abs(Y) @ np.abs(W2).astype(np.float64)).max() / unit2) if unit2 else None
+        exact2 = bool(f["exact"] and unit2 and bound2 < 2 ** 24 and is32(t))
+    if cs2 is not None:
+        t = t * cs2.astype(np.float64)
+        exact2 = exact2 and is32(t)
+    if ch2 is not None:
+        t = t + ch2.astype(np.float64)
+        exact2 = exact2 and is32(t)
+    out2 = t.astype(np.float32)
+    if s["leaky2"]:
+        out2 = np.where(t > 0, out2, np.float32(out2) * np.float32(s["alpha2"])).astype(np.float32)
+    c = dict(f, spec=s, first=f, W2=W2, cs2=cs2, ch2=ch2, sel2=sel2, pre2=t, want2=out2, exact2=bool(exact2), unit2=unit2,
+             bound2=bound2, zero_cols2=zc2)
+    return c
+
+
 # ---- poison and buffers ---------------------------------------------------------------------------------------------------------------
 def widen(a, pad, rows_extra=0, off=0, fill=np.nan):
     """[rows, w] -> flat buffer of `off` + (rows + rows_extra) x (w + pad) floats, everything that is not the matrix filled with
@@ -370,7 +491,8 @@ def poisoned(c, m_dev=None):
 
     def rows_from(a, r0):
         if a is not None and r0 < len(a):
-            a[r0:] = np.resize(bad, a[r0:].shape)
+            flat = a[r0:].reshape(-1)                   # (a view: the operands are contiguous) bad, repeated in flat order
+            flat[:] = np.tile(bad, cdiv(flat.size, len(bad)))[:flat.size]
     if s["gather"]:
         if c["n1_dev"] is not None:
             rows_from(o["x"], c["n1_dev"])
@@ -387,24 +509,32 @@ def poisoned(c, m_dev=None):
             o["ridx"][m:] = -1
     else:
         rows_from(o["res"], m)
+    if s["entry"] == "chain":
+        # nothing of the second level depends on a row; W2 goes to d3f_gemm_pack_x3_chain as a column view of a wider matrix
+        o["W2"], o["ldb2"] = widen(c["W2"], 4)
     return o
 
 
-def expected_buffer(c, m_dev=None):
-    """the whole output buffer [M + PAD, ldc] after the call: rows below *M_dev hold the expectation, every other element the sentinel"""
+def expected_buffer(c, m_dev=None, second=False):
+    """the whole output buffer [M + PAD, ldc] after the call: rows below *M_dev hold the expectation, every other element the sentinel.
+    second: the 32-column output of a chained case, [M + PAD, 32 + ldc2_pad]"""
     s = c["spec"]
     M, N = s["M"], s["N"]
     m = M if m_dev is None else min(m_dev, M)
+    if second:
+        buf = np.full((M + PAD, 32 + s["ldc2_pad"]), SENT, np.float32)
+        buf[:m, :32] = c["want2"][:m]
+        return buf
     sent = SENT_H if s["c_bf16"] else SENT
     buf = np.full((M + PAD, N + s["ldc_pad"]), sent, c["want"].dtype)
     buf[:m, :N] = c["want"][:m]
     return buf
 
 
-def tile_statements(c):
+def tile_statements(c, key="pre"):
     """leaky coverage of a case: (every 32 x 32 output tile of three rows or more holds a positive, a negative and an exactly zero
-    pre-activation value, the last (ragged) tile holds a negative one)"""
-    t = c["pre"]
+    pre-activation value, the last (ragged) tile holds a negative one).  key = "pre2": of the second output of a chained case"""
+    t = c[key]
     M, N = t.shape
     ok = True
     for n0 in range(0, N, 32):
@@ -505,6 +635,53 @@ def x3r_extra_cases():
         out.append(spec("x3", X3R_M, N, 32, kind="select", intent=_intent("gemm_x3r_kernel<%d>" % (N // 32), (1,)), id="select-N%d" % N))
     out.append(spec("x3", X3R_M, 64, 128, C2=32, gather=True, n1=700, n1_dev=650, intent=_intent("gemm_x3r_kernel<2>", (5,)),
                     id="alpha0.2", **dict(FULL, alpha=0.2, lds_pad=4)))
+    return out
+
+
+# d3f_gemm_x3_chain at the walk size: (K, N, first output stored) -> (C1, C2, gathered); every instance, both LDS boundaries
+CHAIN_RANGES = dict(amax=3, wmax=2, w2max=2)
+CHAIN_SHAPES = {(256, 64, False): (128, 128, True),     # <2,false>  the decoder pair
+                (288, 64, False): (288, 0, False),      #            the largest image the entry point accepts
+                (32, 64, False): (32, 0, False),        #            one k-tile: every rotation step is a tile boundary
+                (224, 64, True): (96, 128, False),      # <2,true>   the largest stored image at 64 columns
+                (160, 64, True): (160, 0, False),       #            five k-tiles
+                (96, 128, True): (32, 64, False),       # <4,true>   the encoder pair, a_rebase at k-tile 1
+                (32, 128, True): (32, 0, False),        #            one k-tile
+                (128, 128, False): (64, 64, False),     # <4,false>  the largest image at 128 columns
+                (64, 128, False): (32, 32, True)}       #            gathered + skip
+CHAIN_GATHER = dict(gather=True, n1=700, n1_dev=650, ld_idx=3)
+SECOND = dict(cs2=True, ch2=True, leaky2=True)
+
+
+def _chain_spec(K, N, store, id, M=None, **kw):
+    C1, C2, gathered = CHAIN_SHAPES[(K, N, store)]
+    kw = dict(CHAIN_RANGES, **kw)
+    if gathered:
+        kw.update(CHAIN_GATHER)
+    return spec("chain", X3R_M if M is None else M, N, C1, C2=C2, store=store, intent=_intent(chain_kernel(N, store), (K // 32,)), id=id, **kw)
+
+
+def chain_cases(K, N, store):
+    """raw: no epilogue operand at either level; full: row scale, column scale and shift, residual (ldr = N + 4), LeakyReLU, ldc = N + 4
+    where the first output is stored, and the second epilogue"""
+    C2 = CHAIN_SHAPES[(K, N, store)][1]
+    full = dict(FULL, lds_pad=4 if C2 else 0, ldc_pad=4 if store else 0, **SECOND)
+    return [_chain_spec(K, N, store, "raw"), _chain_spec(K, N, store, "full", **full)]
+
+
+def chain_extra_cases():
+    out = []
+    for K, N, store in ((256, 64, False), (96, 128, True)):
+        out.append(_chain_spec(K, N, store, "select2", kind="select2", amax=0, wmax=0))
+    full = lambda K, N, store, **kw: dict(FULL, lds_pad=4 if CHAIN_SHAPES[(K, N, store)][1] else 0, ldc_pad=4 if store else 0, **kw)
+    # alpha = alpha2 = 0.2: ONE fp32 multiply of an exact value at either level.  The first output then has full mantissas, so W2 is
+    # a selection and the second epilogue a scale (a power of two) and the LeakyReLU
+    out.append(_chain_spec(160, 64, True, "alpha0.2", **full(160, 64, True, alpha=0.2, alpha2=0.2, w2="select", cs2=True, leaky2=True)))
+    out.append(_chain_spec(64, 128, False, "alpha0.2", **full(64, 128, False, alpha=0.2, alpha2=0.2, w2="select", cs2=True, leaky2=True)))
+    out.append(_chain_spec(96, 128, True, "scale2-only", **full(96, 128, True, cs2=True, leaky2=True)))
+    out.append(_chain_spec(256, 64, False, "shift2-only", **full(256, 64, False, ch2=True, leaky2=True)))
+    out.append(_chain_spec(224, 64, True, "ldc2-32", **full(224, 64, True, ldc2_pad=0, **SECOND)))
+    out.append(_chain_spec(128, 128, False, "ldc2-32", **full(128, 128, False, ldc2_pad=0, **SECOND)))
     return out
 
 
@@ -638,4 +815,6 @@ def all_small_specs():
 
 def case_id(s):
     e = s["entry"] + ("%d%d" % (s["a_bf16"], s["c_bf16"]) if s["entry"] == "bf16" else "") + ("-hint%d" % s["hint"] if s["hint"] else "")
+    if s["entry"] == "chain":
+        e += "-stored" if s["store"] else "-unstored"
     return "%s-M%d-N%d-K%d+%d-%s" % (e, s["M"], s["N"], s["C1"], s["C2"], s["id"])

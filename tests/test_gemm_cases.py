@@ -2,8 +2,10 @@
 (max(|A| @ |W|) < 2^24, every intermediate of the epilogue equal to its own float32 rounding), the placement of signs, exact zeros
 and bfloat16 ties, the shadow indices, what poisoned() poisons, and that the branch a case records (written down from the shape
 tables) is what the restated host plans give.  Where libd3feat_amd.so is built, the restated plans are compared with the library's own
-(d3f_gemm_x3_plan, d3f_gemm_x3_resident, the S implied by the three *_workspace_bytes functions) over a grid of (M, N, K, hint) that
-includes every case.  The host-side refusals of the six entry points are tests/test_cabi.py::test_gemm_entry_points_refuse_*."""
+(d3f_gemm_x3_plan, d3f_gemm_x3_resident, d3f_gemm_x3_chain_ok, the S implied by the three *_workspace_bytes functions) over a grid
+of (M, N, K, hint) that includes every case.  The chained cases (d3f_gemm_x3_chain) add the second level: exact2 -- the recorded
+condition that fp32 arithmetic of the second product and epilogue is exact -- the leaky statements of the second output, the
+restated LDS image and the instance a case names.  The host-side refusals of the six entry points are tests/test_cabi.py::test_gemm_entry_points_refuse_*."""
 import ctypes
 import os
 
@@ -128,6 +130,105 @@ def test_every_statement_of_the_resident_walk_cases(N, K):
     assert set(per_wave) == {3, 4}
 
 
+def _check_chain_case(s):
+    """the first level by _check_case (the case IS an x3 case with its own magnitudes); then every statement of the second level"""
+    c = _check_case(s)
+    M, N, K, cid = s["M"], s["N"], c["K"], gc.case_id(s)
+    f = c["first"]
+    assert f["spec"]["entry"] == "x3" and c["want"] is f["want"] and c["x"] is f["x"] and c["W"] is f["W"]
+    assert c["exact"] and c["exact2"], cid
+    assert c["want2"].shape == (M, 32) and c["want2"].dtype == np.float32 and np.isfinite(c["want2"]).all()
+    # the instance and its LDS image
+    assert s["intent"]["kernel"] == "gemm_x3r_chain_kernel<%d,%s>" % (N // 32, "true" if s["store"] else "false"), cid
+    assert gc.gemm_x3r_chain_lds_bytes(K // 32, N // 32, s["store"]) <= gc.LDS_LIMIT and gc.gemm_x3_chain_accepts(N, K, s["store"])
+    assert gc.gemm_x3_resident(M, N, K, 0) == gc.gemm_x3_chain_ok(M, N, K, s["store"])
+    W2 = c["W2"]
+    assert W2.shape == (N, 32)
+    if s["kind"] == "select2":
+        assert not (s["cs2"] or s["ch2"] or s["leaky2"] or s["leaky"])
+        assert ((W2 == 1).sum(0) == 1).all() and (W2 != 0).sum() == 32
+        # every element of the second output is ONE operand of A, bit for bit -- restated from the operands alone
+        sel = c["W"].argmax(0)[W2.argmax(0)]
+        if s["gather"]:
+            rows = c["idx"][:, 0].astype(np.int64)
+            ok = (rows >= 0) & (rows < c["n1_dev"])
+            a = np.where(ok[:, None], c["x"][np.where(ok, rows, 0)], np.float32(0))
+        else:
+            a = c["x"][:M]
+        a = np.concatenate([a, c["skip"]], 1) if c["skip"] is not None else a
+        assert np.array_equal(c["want2"].view(np.uint32), np.ascontiguousarray(a[:, sel]).view(np.uint32)), cid
+        low = c["want2"].view(np.uint32) & 0xFF
+        assert (low != 0).mean() > 0.9                                  # bits in the third plane of nearly every output
+    elif s["w2"] == "select":
+        assert s["alpha"] == 0.2 and s["alpha2"] == 0.2 and s["leaky"] and s["leaky2"] and not s["ch2"]
+        assert ((W2 == 1).sum(0) <= 1).all() and (W2 != 0).sum() == 31
+        neg = c["pre2"] < 0
+        assert neg.any() and np.array_equal(c["want2"][neg], c["pre2"][neg].astype(np.float32) * np.float32(0.2))
+        assert (c["want"].view(np.uint32) & 0xFF).any()                 # the first output is no lattice: full mantissas
+    else:
+        assert np.abs(W2).max() <= s["w2max"] == 2 and (W2 == np.rint(W2)).all() and not W2[:, c["zero_cols2"]].any()
+        assert c["amax"] == 3 and c["wmax"] == 2 and np.abs(c["W"]).max() <= 2
+        # u is 1/16 after a LeakyReLU with alpha 0.25 on multiples of 1/4, 1 on a raw product; the sums keep a margin of 16
+        assert c["unit2"] == (1 / 16 if s["leaky"] else 1.0), cid
+        assert c["bound2"] < 2 ** 20, (cid, c["bound2"])
+        q = c["pre2"] / (c["unit2"] / 2)
+        assert (q == np.rint(q)).all() and np.abs(q).max() < 2 ** 22, cid
+    if c["ch2"] is not None:
+        assert not c["ch2"][c["zero_cols2"]].any()
+    if s["leaky2"]:
+        assert gc.tile_statements(c, "pre2") == (True, True), cid
+        assert s["alpha2"] in (0.25, 0.2)
+    # the poison leaves the expectation alone: no operand of the second level depends on a row, W2 keeps its values inside NaN
+    for m_dev in (None, 33):
+        o = gc.poisoned(c, m_dev)
+        w2 = o["W2"].reshape(N, o["ldb2"])
+        assert o["ldb2"] == 36 and np.array_equal(w2[:, :32], W2) and np.isnan(w2[:, 32:]).all()
+        m = M if m_dev is None else m_dev
+        buf = gc.expected_buffer(c, m_dev, second=True)
+        assert buf.shape == (M + gc.PAD, 32 + s["ldc2_pad"])
+        assert (buf[m:] == gc.SENT).all() and (buf[:, 32:] == gc.SENT).all() and np.array_equal(buf[:m, :32], c["want2"][:m])
+    return c
+
+
+@pytest.mark.parametrize("K,N,store", sorted(gc.CHAIN_SHAPES))
+def test_every_statement_of_the_chain_walk_cases(K, N, store):
+    raw, full = gc.chain_cases(K, N, store)
+    assert raw["M"] == gc.X3R_M and not (raw["epi"] or raw["col"] or raw["cs2"] or raw["ch2"] or raw["leaky2"])
+    assert full["epi"] == 3 and full["leaky"] and full["cs2"] and full["ch2"] and full["leaky2"] and full["alpha2"] == 0.25
+    assert full["ldr_pad"] == 4 and full["ldc_pad"] == (4 if store else 0) and full["ldc2_pad"] == 4
+    for s in (raw, full):
+        assert s["C1"] + s["C2"] == K and bool(s["gather"]) == gc.CHAIN_SHAPES[(K, N, store)][2]
+        _check_chain_case(s)
+
+
+@pytest.mark.parametrize("s", gc.chain_extra_cases(), ids=gc.case_id)
+def test_every_statement_of_the_other_chain_cases(s):
+    _check_chain_case(s)
+
+
+def test_the_chain_shapes_cover_every_instance_and_both_boundaries():
+    shapes = sorted(gc.CHAIN_SHAPES)
+    assert len(shapes) == 9 and {(N, st) for _, N, st in shapes} == set(gc.CHAIN_KERNELS)
+    for N in (64, 128):
+        for st in (False, True):
+            Kmax = gc.chain_largest_k(N, st)
+            assert (Kmax, N, st) in gc.CHAIN_SHAPES                      # the largest image of every instance is walked
+            assert gc.gemm_x3_chain_accepts(N, Kmax, st) and not gc.gemm_x3_chain_accepts(N, Kmax + 32, st)
+    assert {(N, st): gc.chain_largest_k(N, st) for N in (64, 128) for st in (False, True)} == \
+        {(64, False): 288, (64, True): 224, (128, False): 128, (128, True): 96}
+    assert gc.gemm_x3r_chain_lds_bytes(4, 4, False) == 5 * 4 * 7680 + 1280 == 154880
+    # the entry point takes K = 288 at 64 columns, the router's predicate does not (d3f_gemm_x3 has no resident form there)
+    assert gc.gemm_x3_chain_ok(100000, 64, 288, False) == 0 and gc.gemm_x3_chain_ok(100000, 64, 256, False) == 1
+    # every wave of a chip of up to 384 CUs walks three tiles or more
+    assert gc.cdiv(gc.X3R_M, 32) > 2 * 8 * 384
+    ids = [gc.case_id(s) for k in shapes for s in gc.chain_cases(*k)] + [gc.case_id(s) for s in gc.chain_extra_cases()]
+    assert len(set(ids)) == len(ids)
+    kinds = [s["id"] for s in gc.chain_extra_cases()]
+    assert kinds.count("select2") == 2 and kinds.count("alpha0.2") == 2 and "scale2-only" in kinds and "shift2-only" in kinds
+    assert {s["intent"]["kernel"] for s in gc.chain_extra_cases() if s["id"] == "select2"} == \
+        {"gemm_x3r_chain_kernel<2,false>", "gemm_x3r_chain_kernel<4,true>"}
+
+
 def test_every_resident_and_gres_shape_records_its_branch():
     for N, K in gc.X3R_SHAPES:
         assert gc.gemm_x3_resident(gc.X3R_M, N, K, 0) == 1 and gc.gemm_x3_resident(gc.X3R_M, N, K, gc.X3R_TILE_HINT) == 0
@@ -209,3 +310,19 @@ def test_the_restated_plans_are_the_librarys(lib):
             assert lib.d3f_gemm_x3_workspace_bytes(M, N, K, hint) == gc.slab_bytes(S, M, N), (M, N, K, hint)
             n += 1
     assert n > 3000
+
+
+def test_the_restated_chain_predicate_is_the_librarys(lib):
+    n = 0
+    for M in (1, 1000, 65535, 65536, 100000, gc.X3R_M, 707592):
+        for N in (32, 64, 96, 100, 128, 256):
+            for K in list(range(32, 385, 32)) + [0, 16, 48]:
+                for store in (0, 1):
+                    for hint in (0, 1000, 70000):
+                        assert lib.d3f_gemm_x3_chain_ok(M, N, K, store, hint) == gc.gemm_x3_chain_ok(M, N, K, store, hint), (M, N, K, store, hint)
+                        n += 1
+    for k in gc.CHAIN_SHAPES:
+        for s in gc.chain_cases(*k) + gc.chain_extra_cases():
+            K = s["C1"] + s["C2"]
+            assert lib.d3f_gemm_x3_chain_ok(s["M"], s["N"], K, int(s["store"]), 0) == gc.gemm_x3_resident(s["M"], s["N"], K, 0)
+    assert n > 2000

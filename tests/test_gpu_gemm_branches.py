@@ -9,7 +9,7 @@ Entry points are called through _lib.load() with a workspace of exactly the adve
 the reduction reads must have been written); every operand carries NaN / Inf in every float the contract says is not read
 (oracle.gemm_cases.poisoned and .widen: rows past *M_dev / *N1_dev / *res_rows_dev, the columns between the rows where a leading
 dimension exceeds the width, the floats in front of a shifted base).  Packed weights are made from a column view of a wider matrix
-(ldb = N + 4, NaN beside it), so the three pack kernels are checked through every product.  Every case first asserts, from the
+(ldb = N + 4, NaN beside it), so the pack kernels are checked through every product.  Every case first asserts, from the
 library's own plan functions, that it lands in the branch it names; no case skips.  Every K-split case runs twice on one workspace,
 with other operands the second time (a stale slab).  Where the branch is the Python router (bfloat16 tensors, gemm_upsample_split)
 the call goes through d3feat_amd.ops.
@@ -33,6 +33,24 @@ Branch -> test
     *M_dev = 0 / 1 / 33 (most waves leave after the barrier) / 65535 the same tests, on the full case
     the same shapes with M_hint < 65536: the tile form, same values  the same tests
     selection operands, alpha = 0.2                                  test_x3_resident_more[id]
+  gemm_x3r_chain_kernel<2,false>: K 256 (gathered 128 + skip 128:    test_x3_chain_walk[N-K-store] (d3f_gemm_x3_chain): M = 3 * 65536 + 37 and, asserted
+    the decoder pair), 288 (the largest image the entry point        first, more than 2 * 8 * CUs row tiles -- EVERY wave walks three tiles or more:
+    takes), 32 (one k-tile: a tile boundary on every step)           the accumulators cleared in finish_tile, the fresh acc2, the patch reused for
+  gemm_x3r_chain_kernel<2,true>: K 224 (96 + 128: the largest        the N-column and the 32-column stores of consecutive tiles, requests across a
+    stored image at 64 columns), 160 (five k-tiles)                  tile boundary (rq_rows of the next tile, gathered indices included), a_rebase at
+  gemm_x3r_chain_kernel<4,true>: K 96 (32 + 64: the encoder pair,    K1 inside the walk, c_tile += tstride.  Raw (no epilogue operand at either level)
+    a_rebase at k-tile 1), 32                                        and full: row scale, column scale and shift, residual (ldr = N + 4), LeakyReLU,
+  gemm_x3r_chain_kernel<4,false>: K 128 (64 + 64: the largest        ldc = N + 4 where stored (C = NULL where not), the second epilogue on, ldc2 = 36.
+    image at 128 columns), 64 (gathered 32 + skip 32)                Whole buffers: the second output always, the first where stored -- and that one
+    *M_dev = 0 / 1 / 33 / 65535: a walk that ends early              against the expectation of the d3f_gemm_x3 case of the same operands.  The full
+                                                                     case at every *M_dev of X3R_MDEV
+    both 0/1 selections of full mantissas (select2): the exact       test_x3_chain_more[*select2] on <2,false> and <4,true>
+    three-plane split of the finished value, W2's k order
+    alpha = alpha2 = 0.2; second epilogue scale only / shift only    test_x3_chain_more[*alpha0.2], [*scale2-only], [*shift2-only], [*ldc2-32] (the
+    (NULL pointers); ldc2 = 32                                       last also with *M_dev = 65535)
+    the LDS boundary of the entry point and of the predicate         test_x3_chain_lds_boundary[N-store]: the largest K of the restated formula is
+                                                                     launched, K + 32 is D3F_ERR_ARG with both outputs untouched,
+                                                                     d3f_gemm_x3_chain_ok draws the same line where d3f_gemm_x3 is resident
   d3f_gemm_x3_gres: gemm_residual_row in the direct epilogue (K 64)  test_x3_gathered_residual[id]: ld_res_idx 1 / 3, indices negative, equal
     and in gemm_splitk_reduce_kernel (K 352)                         to and beyond the row count, *res_rows_dev < res_rows, a row scale
     a call for which d3f_gemm_x3_resident answers 1                  test_x3_gathered_residual[*resident-shape]: still the tile form
@@ -51,14 +69,25 @@ Branch -> test
     RNE of the output: planted 257 (tie down), 259 (tie up), 515     concatenated; <1,1>, <1,0>, <0,0> also through ops.gemm,
                                                                      gemm_upsample_cat and gemm_cat2 under ops.bf16_contraction
   gemm_pack_x3_kernel, gemm_pack_f32t_kernel, gemm_pack_bf16_kernel  every test above: ldb = N + 4, NaN beside the matrix
+  gemm_pack_x3_kernel, chain = 1 (d3f_gemm_pack_x3_chain)            every test_x3_chain_* case: W2 from a column view, ldb = 36, NaN beside it
   gemm_splitk_reduce_kernel: stale slab                              every split case above runs twice on one workspace
 
-No defect found: every case passes on the library as it was before this file.
+No defect found: every case passes on the library as it was before this file, and the chained cases on the library as it was before
+them (the header comment of d3f_gemm_x3_chain named K <= 96 for N = 128 whatever is stored; the code takes, and
+test_x3_chain_walk[128-128-0] runs, K = 128 with the first output not stored: the comment was wrong, not the code).
+What the chained cases catch, tried on scratch copies of the library (value-only edits, one at a time): W2 packed in
+d3f_gemm_pack_x3's plain k order -- every test_x3_chain_walk and test_x3_chain_more case fails; the accumulators of the first product
+not cleared at the end of finish_tile -- every test_x3_chain_walk and test_x3_chain_more case fails (and the walk-size rows of
+tests/test_gpu_gemm_chain.py) while every test at one tile per wave still passes; the second epilogue reading the first epilogue's
+vectors -- every case fails; the finished value split into two planes only -- the select2 and alpha0.2 cases fail, the lattice cases
+(at most 16 significant bits) do not.
 
-Cost, measured on an MI355X: the 317 tests take 34.5 s run alone (pytest's figure); the fifteen
-test_x3_resident_walk cases are the slowest with 0.7 .. 3.5 s each (eight launches of 196 645 rows each, expectations of up to
-25 M outputs in float64 on the host), nothing else reaches 0.5 s.  One complete `pytest -m gpu tests` run with this file took 390.8 s
-(1333 passed, 5 skipped).
+Cost, measured on an MI355X: the 338 tests take 38.9 s run alone (pytest's figure; 34.5 s for the 317 before the chained cases).
+The nine test_x3_chain_walk cases are the slowest with 0.8 .. 2.0 s each (six launches of 196 645 rows each, operands of up to 57 M
+floats, two expectations in float64 on the host), the fifteen test_x3_resident_walk cases take 0.3 .. 1.6 s (eight launches), the
+eight test_x3_chain_more cases 0.6 .. 1.1 s, test_x3_chain_lds_boundary under 0.1 s; nothing else reaches 0.5 s.  One complete
+`pytest -m gpu tests` run with this file took 331.3 s (1680 passed, 5 skipped); the figure before the chained cases, from an earlier
+state of the suite, was 390.8 s (1333 passed, 5 skipped).
 """
 import ctypes as C
 
@@ -97,6 +126,13 @@ def workspace_bytes(lib, s):
 def assert_branch(lib, s, ptrs=None):
     """the case lands in the branch it names, by the library's own plan functions"""
     M, N, K, hint, it = s["M"], s["N"], s["C1"] + s["C2"], s["hint"], s["intent"]
+    if s["entry"] == "chain":
+        # the instance follows from N and from whether a first output is handed over; the LDS image must fit; no workspace
+        stored = bool(ptrs["C"])
+        assert stored == bool(s["store"]) and it["kernel"] == gc.CHAIN_KERNELS[(N, stored)] and it["tiles"] == (K // 32,)
+        assert gc.gemm_x3r_chain_lds_bytes(K // 32, N // 32, stored) <= gc.LDS_LIMIT
+        assert lib.d3f_gemm_x3_chain_ok(M, N, K, int(stored), hint) == lib.d3f_gemm_x3_resident(M, N, K, hint)
+        return 0
     wsb = workspace_bytes(lib, s)
     if s["entry"] in ("x3", "x3_gres"):
         resident = lib.d3f_gemm_x3_resident(M, N, K, hint)
@@ -159,7 +195,7 @@ class Launch:
         pn1 = vec(np.array([c["n1_dev"]], np.int32)) if c["n1_dev"] is not None else None
         prr = vec(np.array([s["res_rows_dev"]], np.int32)) if s.get("res_rows_dev") is not None else None
         # the weights: a column view of a wider matrix (packed entries: always ldb = N + 4)
-        packed = e in ("x3", "x3_gres", "f32t", "bf16")
+        packed = e in ("x3", "x3_gres", "chain", "f32t", "bf16")
         ldb_pad = 4 if packed else s["ldb_pad"]
         pW = ldb = None
         if K:
@@ -169,7 +205,7 @@ class Launch:
             pW = tw.data_ptr() + (0 if packed else 4 * s["b_off"])
         if packed:
             Kp = gc.cdiv(K, 32) * 32
-            if e in ("x3", "x3_gres"):
+            if e in ("x3", "x3_gres", "chain"):
                 nb = int(lib.d3f_gemm_x3_packed_bytes(K, N))
                 assert nb == gc.cdiv(N, 32) * (K // 32) * gc.X3_CHUNK_BYTES
                 wp = torch.full((nb,), 0x7F, dtype=torch.uint8, device=dev)
@@ -183,11 +219,24 @@ class Launch:
             self.keep.append(wp)
             pW = wp.data_ptr()
         ldc = N + s["ldc_pad"]
-        if s["c_bf16"]:
+        if e == "chain":
+            # W2 through d3f_gemm_pack_x3_chain from a column view (ldb = 36, NaN beside it); the second output with its own sentinel
+            tw2 = _up(o["W2"], dev)
+            nb2 = int(lib.d3f_gemm_x3_packed_bytes(N, 32))
+            assert o["ldb2"] == 36 and nb2 == (N // 32) * gc.X3_CHUNK_BYTES
+            w2p = torch.full((nb2,), 0x7F, dtype=torch.uint8, device=dev)
+            assert lib.d3f_gemm_pack_x3_chain(tw2.data_ptr(), o["ldb2"], N, 32, w2p.data_ptr(), None) == 0
+            self.keep += [tw2, w2p]
+            self.ldc2 = 32 + s["ldc2_pad"]
+            self.out2 = torch.full(((M + gc.PAD) * self.ldc2,), float(gc.SENT), dtype=torch.float32, device=dev)
+        if e == "chain" and not s["store"]:
+            self.out = None                              # C = NULL: the first output is not stored
+        elif s["c_bf16"]:
             self.out = torch.full(((M + gc.PAD) * ldc,), int(np.uint16(gc.SENT_H).view(np.int16)), dtype=torch.int16, device=dev)
         else:
             self.out = torch.full(((M + gc.PAD) * ldc,), float(gc.SENT), dtype=torch.float32, device=dev)
-        self.wsb = assert_branch(lib, s, dict(lds=[lda, lds, ldb or 0, ldc, ldr], bases=[p or 0 for p in (pA, pS, pW, pR, pcs, pch, self.out.data_ptr())]))
+        self.wsb = assert_branch(lib, s, dict(lds=[lda, lds, ldb or 0, ldc, ldr], bases=[p or 0 for p in (pA, pS, pW, pR, pcs, pch, self.out.data_ptr() if self.out is not None else 0)],
+                                                C=self.out is not None))
         if ws is None:
             ws = torch.full((self.wsb // 4,), float("nan"), dtype=torch.float32, device=dev)
         assert ws.numel() * 4 == self.wsb
@@ -195,8 +244,13 @@ class Launch:
         n1 = c["n1"]
         tail = [ws.data_ptr(), C.c_size_t(self.wsb), pmd]
         flags = [1 if s["leaky"] else 0, float(s["alpha"])]
-        pC = self.out.data_ptr()
-        if e == "f32":
+        pC = self.out.data_ptr() if self.out is not None else None
+        if e == "chain":
+            self.fn = lib.d3f_gemm_x3_chain
+            self.args = [pA, n1, lda, C1, pidx, s["ld_idx"], pS, lds, C2, pW, pC, ldc, M, N, prs, pcs, pch, pR, ldr] + flags + \
+                        [w2p.data_ptr(), vec(c["cs2"]), vec(c["ch2"]), 1 if s["leaky2"] else 0, float(s["alpha2"]), self.out2.data_ptr(), self.ldc2,
+                         pmd, pn1, None]
+        elif e == "f32":
             self.fn, self.args = lib.d3f_gemm_f32, [pA, max(lda, K), pW, ldb or N, pC, ldc, M, N, K, prs, pcs, pch, pR, ldr] + flags + tail + [s["hint"], None]
         elif e == "upcat":
             self.fn = lib.d3f_gemm_upsample_cat_f32
@@ -215,21 +269,47 @@ class Launch:
         assert rc == 0, (gc.case_id(self.s), rc)
         torch.cuda.synchronize()
         s = self.s
+        if self.out is None:
+            return None
         got = self.out.cpu().numpy().reshape(s["M"] + gc.PAD, s["N"] + s["ldc_pad"])
         return got.view(np.uint16) if s["c_bf16"] else got
+
+    def second(self):
+        """(after run) the whole second output buffer of a chained case"""
+        return self.out2.cpu().numpy().reshape(self.s["M"] + gc.PAD, self.ldc2)
+
+
+def _same(c, m_dev, got, want, what=""):
+    if not np.array_equal(got, want):
+        bad = np.argwhere(~(got == want))
+        s = c["spec"]
+        raise AssertionError("%s%s (*M_dev %s): %d elements differ, first at %s: got %r, want %r; rows %d..%d, columns %d..%d"
+                             % (gc.case_id(s), what, m_dev, len(bad), tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])],
+                                bad[:, 0].min(), bad[:, 0].max(), bad[:, 1].min(), bad[:, 1].max()))
 
 
 def check(lib, dev, c, m_dev=None, ws=None):
     """launch, compare the WHOLE buffer (expectation + every sentinel); -> the workspace, for a second call on it"""
     L = Launch(lib, dev, c, m_dev, ws)
-    got, want = L.run(), gc.expected_buffer(c, m_dev)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(~(got == want))
-        s = c["spec"]
-        raise AssertionError("%s (*M_dev %s): %d elements differ, first at %s: got %r, want %r; rows %d..%d, columns %d..%d"
-                             % (gc.case_id(s), m_dev, len(bad), tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])],
-                                bad[:, 0].min(), bad[:, 0].max(), bad[:, 1].min(), bad[:, 1].max()))
+    _same(c, m_dev, L.run(), gc.expected_buffer(c, m_dev))
     return L.ws
+
+
+def check_chain(lib, dev, c, m_dev=None):
+    """a chained case: the WHOLE second output buffer and, where it is stored, the WHOLE first one -- against the chained case's
+    expectation and against what the d3f_gemm_x3 case of the same first-level operands (c["first"]) expects, which must be the same"""
+    s = c["spec"]
+    assert s["entry"] == "chain" and c["exact"] and c["exact2"], gc.case_id(s)
+    L = Launch(lib, dev, c, m_dev)
+    got = L.run()
+    _same(c, m_dev, L.second(), gc.expected_buffer(c, m_dev, second=True), " second output")
+    if s["store"]:
+        x3 = c["first"]
+        assert x3["spec"]["entry"] == "x3" and lib.d3f_gemm_x3_resident(s["M"], s["N"], c["K"], 0) == 1
+        _same(c, m_dev, got, gc.expected_buffer(x3, m_dev), " first output")
+        assert np.array_equal(gc.expected_buffer(x3, m_dev), gc.expected_buffer(c, m_dev))
+    else:
+        assert got is None
 
 
 def check_twice_if_split(lib, dev, s, c=None):
@@ -292,6 +372,63 @@ def test_x3_resident_walk(lib, device, N, K):
 @pytest.mark.parametrize("s", gc.x3r_extra_cases(), ids=gc.case_id)
 def test_x3_resident_more(lib, device, s):
     check(lib, device, gc.build(s))
+
+
+# ---- gemm_x3r_chain_kernel: the chained form in the multi-tile walk -----------------------------------------------------------------------
+@pytest.mark.parametrize("N,K,store", [(N, K, st) for K, N, st in sorted(gc.CHAIN_SHAPES, key=lambda k: (k[1], k[0], k[2]))],
+                         ids=lambda v: str(int(v)))
+def test_x3_chain_walk(lib, device, N, K, store):
+    M = gc.X3R_M
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    assert gc.cdiv(M, 32) > 2 * 8 * cus                  # every wave of THIS device walks three tiles or more
+    raw, full = gc.chain_cases(K, N, store)
+    check_chain(lib, device, gc.build(raw))
+    c = gc.build(full)
+    for m_dev in gc.X3R_MDEV:
+        check_chain(lib, device, c, None if m_dev == M else m_dev)
+
+
+@pytest.mark.parametrize("s", gc.chain_extra_cases(), ids=gc.case_id)
+def test_x3_chain_more(lib, device, s):
+    c = gc.build(s)
+    check_chain(lib, device, c)
+    if s["id"] == "ldc2-32":
+        assert s["ldc2_pad"] == 0
+        check_chain(lib, device, c, 65535)
+
+
+@pytest.mark.parametrize("store", (0, 1))
+@pytest.mark.parametrize("N", (64, 128))
+def test_x3_chain_lds_boundary(lib, device, N, store):
+    """the largest K the restated LDS formula admits is launched, the next one is refused with nothing written, and the router's
+    predicate draws the same line wherever d3f_gemm_x3 has a resident form (the walk test runs the image at that K)"""
+    Kmax = gc.chain_largest_k(N, store)
+    assert (Kmax, N, bool(store)) in gc.CHAIN_SHAPES
+    M, D3F_OK, D3F_ERR_ARG = 70, 0, -3
+    for K in (Kmax, Kmax + 32):
+        A = torch.zeros((M, K), device=device)
+        wx = torch.zeros(int(lib.d3f_gemm_x3_packed_bytes(K, N)), dtype=torch.uint8, device=device)
+        w2x = torch.zeros(int(lib.d3f_gemm_x3_packed_bytes(N, 32)), dtype=torch.uint8, device=device)
+        first = torch.full((M + gc.PAD, N), float(gc.SENT), device=device)
+        out2 = torch.full((M + gc.PAD, 32), float(gc.SENT), device=device)
+        rc = lib.d3f_gemm_x3_chain(A.data_ptr(), M, K, K, None, 1, None, 0, 0, wx.data_ptr(), first.data_ptr() if store else None, N, M, N,
+                                   None, None, None, None, 0, 0, 0.25, w2x.data_ptr(), None, None, 0, 0.25, out2.data_ptr(), 32, None, None, None)
+        torch.cuda.synchronize()
+        if K == Kmax:
+            assert rc == D3F_OK
+            assert bool((out2[:M] == 0).all()) and bool((out2[M:] == float(gc.SENT)).all())
+            assert bool((first[:M] == 0).all()) == bool(store) and bool((first[M:] == float(gc.SENT)).all())
+        else:
+            assert rc == D3F_ERR_ARG
+            assert bool((out2 == float(gc.SENT)).all()) and bool((first == float(gc.SENT)).all())
+    seen = 0
+    for K in range(32, Kmax + 97, 32):
+        if lib.d3f_gemm_x3_resident(100000, N, K, 0):
+            assert lib.d3f_gemm_x3_chain_ok(100000, N, K, store, 0) == int(K <= Kmax) == gc.gemm_x3_chain_ok(100000, N, K, store)
+            seen += 1
+        else:
+            assert lib.d3f_gemm_x3_chain_ok(100000, N, K, store, 0) == 0
+    assert seen >= 3
 
 
 @pytest.mark.parametrize("s", gc.gres_cases(), ids=gc.case_id)

@@ -8,7 +8,9 @@ takes the resident form; the routing threshold of 65536 rows is not under test):
   * rows at and beyond a device-resident row count are not written; the argument rules; the network routing and its switch.
 Shapes: (K, N) = (256, 64), [ gathered (indices -1 and >= N1 among them) | skip ], first output not stored -- the decoder pair; and
 (32 + 64, 128) as [A1 | A2], first output stored -- the encoder pair.  Rows 1, 31, 32, 33 (less than a tile, the tile edge), 257 (more
-tiles than one workgroup's first round: waves without a tile beside waves with one), 773 (more than one workgroup)."""
+tiles than one workgroup's first round: waves without a tile beside waves with one), 773 (more than one workgroup); the float64
+comparison also at 32 * 8 * CUs * 2 + 33 rows, where every wave walks two or three tiles (the bit-for-bit tests of that regime are
+tests/test_gpu_gemm_branches.py::test_x3_chain_walk)."""
 import numpy as np
 import pytest
 import torch
@@ -91,9 +93,11 @@ def second_reference(c, Y, second_epilogue):
 
 
 @pytest.mark.parametrize("second_epilogue", [False, True], ids=["identity", "bn_leaky"])
-@pytest.mark.parametrize("M", ROWS)
+@pytest.mark.parametrize("M", ROWS + ("walk",))
 @pytest.mark.parametrize("kind", sorted(SHAPES))
 def test_against_the_two_launch_form_and_float64(device, kind, M, second_epilogue, capsys):
+    if M == "walk":       # two full rounds of this device's waves and 33 rows more: every wave walks two tiles or three
+        M = 32 * 8 * torch.cuda.get_device_properties(device).multi_processor_count * 2 + 33
     c = make_case(kind, M)
     Y, got = run_chain(device, kind, c, second_epilogue)
     Y2, two = run_two_launches(device, kind, c, second_epilogue)
