@@ -120,6 +120,9 @@ SIGNATURES = {
     "d3f_batch_norm_train": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "d3f_batch_norm_backward": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz,
                                      _vp]),
+    "d3f_ind_max_pool_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "d3f_ind_max_pool_backward": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "d3f_closest_pool_cat_backward": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "d3f_pose_errors": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_sanitize_descriptors": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "d3f_matching_summary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -554,6 +554,9 @@ extern "C" int d3f_affine_act(const float* x, int ldx, int M, int N, const float
 // batch normalisation in training mode with the same epilogue, and its backward (d3f_batch_norm_train, d3f_batch_norm_backward)
 #include "ph_batch_norm.h"
 
+// the backward of the two gathers above (d3f_ind_max_pool_backward, d3f_closest_pool_cat_backward)
+#include "ph_pool_backward.h"
+
 // ------------------------------------------------------------------------------------------------
 // (xyz, desc, score) -> one record f32[3 + C + 1] per point: the 144-byte payload (C = 32) that the testers write per
 // fragment (utils/tester.py:215-229 keeps points / features / scores together) and that the multi-GPU runner gathers once

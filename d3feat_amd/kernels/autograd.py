@@ -17,6 +17,21 @@ pass).  Backward: ops.batch_norm_backward -> gradients to x, gamma, beta and res
     unary_trainable(x, W)
 
 Forward: ops.gemm.  Backward: ops.unary_backward (gx = gy W^T on the contraction router, gW = x^T gy by ops.gemm_tn).
+
+    ind_max_pool_trainable(x, inds)                          closest_pool_cat_trainable(x, inds, skip)
+
+The two gathers at a level boundary.  Forward: ops.ind_max_pool / ops.closest_pool_cat.  Backward: ops.ind_max_pool_backward (from the
+stored output) / ops.closest_pool_cat_backward for x and the column view of the gradient for skip.  The transposed table is built at the
+first backward and kept on the context.
+
+    detection_head_trainable(features, neighbors, lens_dev, include_zero, stack_group)       -> (descriptors, scores)
+
+Forward: ops.detect_head.  Backward: ops.detect_head_backward; either incoming gradient may be None.
+
+    pair_loss_trainable(features, scores, points, anc_idx, pos_idx, **loss settings)         -> (loss scalar, PairGradients)
+
+ONE validation.loss_gradients call in the forward: the scalar is the sum over the pairs of status 0 of circle + det, the stored
+gradients are scaled by the incoming scalar in the backward, and the result object carries the five validation figures of the same call.
 """
 import torch
 
@@ -138,3 +153,114 @@ class _Unary(torch.autograd.Function):
 def unary_trainable(x, W):
     """ops.gemm(x, W) whose result carries gradients to x and W."""
     return _Unary.apply(x, W)
+
+
+class _MaxPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, inds):
+        xp = _plain(x)
+        y = ops.ind_max_pool(xp, inds)
+        ctx.inds, ctx.table = inds, None
+        ctx.counts = (_Count(x), _Count(inds))
+        ctx.save_for_backward(xp, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        x, y = ctx.saved_tensors
+        x, y = ops._tag(x, ctx.counts[0]), ops._tag(y, ctx.counts[1])
+        if ctx.table is None:
+            ctx.table = ops.neighbor_transpose_supports(ctx.inds, x.shape[0], getattr(y, "n_dev", None), getattr(x, "n_dev", None))
+        return ops.ind_max_pool_backward(x, ctx.inds, y, _as_rows(grad_y).detach(), transpose=ctx.table), None
+
+
+def ind_max_pool_trainable(x, inds):
+    """ops.ind_max_pool(x, inds) whose result carries the gradient to x (float32 rows)."""
+    return _MaxPool.apply(x, inds)
+
+
+class _UpsampleCat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, skip, inds):
+        ctx.inds, ctx.table = inds, None
+        ctx.shape = (int(x.shape[0]), int(x.shape[1]))
+        ctx.count = _Count(x)
+        return ops.closest_pool_cat(_plain(x), inds, None if skip is None else _plain(skip))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        need_x, need_skip = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g = ops._tag(_as_rows(grad_out).detach(), ctx.inds)
+        N1, C1 = ctx.shape
+        gx = None
+        if need_x:
+            gx = ops._tag(torch.empty((N1, C1), dtype=torch.float32, device=g.device), ctx.count)
+            if ctx.table is None:
+                ctx.table = ops.neighbor_transpose_supports(ops._tag(ctx.inds[:, :1], ctx.inds), N1, None, getattr(gx, "n_dev", None))
+            ops.closest_pool_cat_backward(g, ctx.inds, N1, C1, transpose=ctx.table, out=gx)
+        return gx, (g[:, C1:] if need_skip else None), None
+
+
+def closest_pool_cat_trainable(x, inds, skip=None):
+    """ops.closest_pool_cat(x, inds, skip) whose result carries gradients to x and skip."""
+    return _UpsampleCat.apply(x, skip, inds)
+
+
+class _Head(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, neighbors, lens_dev, include_zero, stack_group):
+        f = _plain(features)
+        ctx.geometry = (neighbors, lens_dev, include_zero, stack_group)
+        ctx.table = None
+        ctx.count = _Count(features)
+        ctx.set_materialize_grads(False)                             # (an unused output hands None, not zeros, to the backward)
+        ctx.save_for_backward(f)
+        desc, score = ops.detect_head(f, neighbors, lens_dev, include_zero, stack_group=stack_group)
+        return desc, score
+
+    @staticmethod
+    def backward(ctx, grad_desc, grad_score):
+        if not ctx.needs_input_grad[0] or (grad_desc is None and grad_score is None):
+            return (None,) * 5
+        neighbors, lens_dev, include_zero, stack_group = ctx.geometry
+        (f,) = ctx.saved_tensors
+        if ctx.table is None:
+            ctx.table = ops.neighbor_transpose(neighbors, lens_dev)
+        gd = None if grad_desc is None else _as_rows(grad_desc).detach()
+        gs = None if grad_score is None else grad_score.detach()
+        if gs is not None and gs.dim() == 2 and gs.shape[0] > 1 and gs.stride(0) < 1:
+            gs = gs.contiguous()                                     # (an expanded gradient)
+        gx = ops.detect_head_backward(ops._tag(f, ctx.count), neighbors, lens_dev, include_zero, gd, gs, stack_group=stack_group,
+                                      transpose=ctx.table)
+        return (gx,) + (None,) * 4
+
+
+def detection_head_trainable(features, neighbors, lens_dev, include_zero, stack_group=0):
+    """ops.detect_head -> (descriptors, scores) whose gradients (either may be missing) reach `features`."""
+    return _Head.apply(features, neighbors, lens_dev, include_zero, stack_group)
+
+
+class _PairLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, features, scores, result):
+        v = result.values
+        ok = (result.status == 0).to(torch.float32)
+        ctx.result = result
+        return ((v[:, 0 if result.loss == "circle_loss" else 1] + v[:, 2]) * ok).sum()     # (columns: validation.FIGURES)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        r = ctx.result
+        gf = r.features * grad_loss if ctx.needs_input_grad[0] else None
+        gs = (r.scores * grad_loss).reshape(-1, 1) if ctx.needs_input_grad[1] else None
+        return gf, gs, None
+
+
+def pair_loss_trainable(features, scores, points, anc_idx, pos_idx, **settings):
+    """-> (loss, result): validation.loss_gradients(features, scores, points, anc_idx, pos_idx, **settings) once; loss is the autograd
+    scalar circle + det summed over the pairs of status 0, result the PairGradients of that call (its figures are the validation's)."""
+    from .. import validation
+    result = validation.loss_gradients(_plain(features), _plain(scores), points, anc_idx, pos_idx, **settings)
+    return _PairLoss.apply(features, scores, result), result

@@ -4,15 +4,28 @@
 
 The nearest-upsample gather and the skip concatenation (D3Feat.py:55-63) are one kernel; the l2 normalisation
 (:65) and the whole soft detection module (:67-115) are one kernel after a per-cloud max reduction.
+
+With dropout_prob < 0.99 (training) the walk runs the trainable forms of the blocks (network_blocks.training_walk) and ends in
+kernels.autograd.detection_head_trainable: the two outputs carry gradients to every variable of the network.  The encoder skip
+F[l - 1] feeds the next encoder block and the decoder's concatenation; autograd adds the two gradients.
 """
+import contextlib
+
 import numpy as np
 import torch
 
 from .. import ops
+from ..kernels.autograd import detection_head_trainable
+from . import network_blocks
 from .network_blocks import assemble_CNN_blocks, get_block_ops, variable_scope
 
 
 def assemble_FCNN_blocks(inputs, config, dropout_prob):
+    with network_blocks.training_walk() if dropout_prob < 0.99 else contextlib.nullcontext():
+        return _assemble_FCNN_blocks(inputs, config, dropout_prob)
+
+
+def _assemble_FCNN_blocks(inputs, config, dropout_prob):
     F = assemble_CNN_blocks(inputs, config, dropout_prob)
     features = F[-1]
     layer = config.num_layers - 1
@@ -32,7 +45,7 @@ def assemble_FCNN_blocks(inputs, config, dropout_prob):
                 # ... kept lazy: the unary block that follows contracts [gathered | skip] directly (ops.UpsampleCat)
                 with variable_scope('nearest_upsample'):
                     if isinstance(features, ops.UpsampleCat):
-                        features = features.materialize()
+                        features = network_blocks._upsampled_train(features) if training else features.materialize()
                     features = ops.UpsampleCat(features, inputs['upsamples'][layer - 1], F[layer - 1])
             else:
                 features = get_block_ops(block)(layer, inputs, features, r, fdim, config, training)
@@ -45,8 +58,8 @@ def assemble_FCNN_blocks(inputs, config, dropout_prob):
             if block != 'nearest_upsample':
                 raise NotImplementedError('only nearest_upsample decoders are implemented')
     if isinstance(features, ops.UpsampleCat):
-        features = features.materialize()
-    return detection_head(features, inputs)
+        features = network_blocks._upsampled_train(features) if training else features.materialize()
+    return detection_head_training(features, inputs) if training else detection_head(features, inputs)
 
 
 def detection_head(features, inputs):
@@ -61,6 +74,15 @@ def detection_head(features, inputs):
     ib = inputs.get('in_batches')
     group = ib.group if isinstance(ib, ops.StackGroups) else 0
     return ops.detect_head(features, inputs['neighbors'][0], lens_dev, include_zero, stack_group=group)
+
+
+def detection_head_training(features, inputs):
+    """detection_head whose two outputs carry gradients to `features` (the backward is ops.detect_head_backward, with stack_group and
+    the include-zero vector taken from `inputs` as detection_head_backward takes them)."""
+    lens_dev = ops.as_lens(inputs['stack_lengths'], features.device)
+    ib = inputs.get('in_batches')
+    group = ib.group if isinstance(ib, ops.StackGroups) else 0
+    return detection_head_trainable(features, inputs['neighbors'][0], lens_dev, inputs.get('in_batches_padded'), group)
 
 
 def detection_head_backward(features, inputs, grad_features, grad_scores, transpose=None):

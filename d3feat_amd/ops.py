@@ -1525,6 +1525,95 @@ def kpconv_backward(query_points, support_points, neighbors_indices, features, K
     return gf, gW
 
 
+def _table(what, transpose, rows, items):
+    """(start i32[rows + 1], edges i32[>= items]) of a passed transposed table, checked."""
+    start = _typed(transpose[0], torch.int32, "transpose[0]", 1)
+    edges = _typed(transpose[1], torch.int32, "transpose[1]", 1)
+    if start.numel() != rows + 1 or edges.numel() < items or not (start.is_contiguous() and edges.is_contiguous()):
+        raise ValueError("%s: transpose must be (start i32[%d], edges i32[%d]) of the same indices" % (what, rows + 1, items))
+    return start, edges
+
+
+def ind_max_pool_backward(x, inds, y, grad_y, transpose=None, out=None):
+    """Backward of ind_max_pool -> gx f32[N1, C], the gradient with respect to x, from y (the STORED forward output) and grad_y f32[N2, C];
+    x, y, grad_y and out may be column views.  Ties split evenly, the shadow row's column minima included: the definition and the
+    summation orders are in include/d3feat_amd.h (d3f_ind_max_pool_backward).  transpose: (start, edges) of
+    neighbor_transpose_supports(inds, N1); built here when None.  Device-resident counts ride on the tags of x and inds; rows of out at
+    or beyond the count of x are left alone.  fp32 rows only.  Three launches, no read-back, capturable."""
+    lib = _lib.load()
+    x, ldx = _rows(_typed(x, torch.float32, "x"), "x")
+    idx, ldi = _rows(_typed(inds, torch.int32, "inds"), "inds")
+    y, ldy = _rows(_typed(y, torch.float32, "y"), "y")
+    g, ldg = _rows(_typed(grad_y, torch.float32, "grad_y"), "grad_y")
+    (N1, C), (N2, K) = x.shape, idx.shape
+    if C < 1:
+        raise ValueError("ind_max_pool_backward: x is %s" % (tuple(x.shape),))
+    if tuple(y.shape) != (N2, C) or tuple(g.shape) != (N2, C):
+        raise ValueError("ind_max_pool_backward: y is %s, grad_y %s, wanted %s" % (tuple(y.shape), tuple(g.shape), (N2, C)))
+    if N2 * K > (1 << 31) - 8192:
+        raise ValueError("ind_max_pool_backward: %d x %d neighbour slots (at most 2^31 - 8192)" % (N2, K))
+    if out is not None:
+        out, ldo = _rows(_typed(out, torch.float32, "out"), "out")
+        if tuple(out.shape) != (N1, C):
+            raise ValueError("ind_max_pool_backward: out is %s, x %s" % (tuple(out.shape), (N1, C)))
+    start = edges = None
+    if transpose is not None:
+        start, edges = _table("ind_max_pool_backward", transpose, N1, N2 * K)
+    n1_t = getattr(x, "n_dev", None)
+    n2_t = _row_count(inds, y, grad_y)
+    _on_device("ind_max_pool_backward", x=x, inds=idx, y=y, grad_y=g, out=out, start=start, edges=edges, n1_dev=n1_t, n2_dev=n2_t)
+    dev = x.device
+    if start is None:
+        start, edges = neighbor_transpose_supports(idx, N1, n2_t, n1_t)
+    if out is None:
+        out, ldo = torch.empty((N1, C), dtype=torch.float32, device=dev), C
+    nbytes = lib.d3f_ind_max_pool_backward_workspace_bytes(N1, N2, K, C)
+    ws = workspace(nbytes, dev)
+    with _timed("ind_max_pool_backward", dict(N1=N1, N2=N2, K=K, C=C), dev):
+        rc = lib.d3f_ind_max_pool_backward(x.data_ptr(), N1, ldx, C, idx.data_ptr(), N2, ldi, K, y.data_ptr(), ldy, g.data_ptr(), ldg,
+                                           start.data_ptr(), edges.data_ptr(), out.data_ptr(), ldo, _ptr(n1_t), _ptr(n2_t), 0,
+                                           ws.data_ptr(), nbytes, _stream(dev))
+    _lib.check(rc, "ind_max_pool_backward")
+    return _tag(out, x)
+
+
+def closest_pool_cat_backward(grad_out, inds, num_coarse, C1, transpose=None, out=None):
+    """Backward of closest_pool_cat with respect to x -> gx f32[num_coarse, C1]: the rows grad_out[n, :C1] added, in ascending n, into
+    the coarse row inds[n, 0] names; a shadow index carries nothing (include/d3feat_amd.h, d3f_closest_pool_cat_backward).  The skip's
+    gradient is the view grad_out[:, C1:].  transpose: (start, edges) of neighbor_transpose_supports(inds[:, :1], num_coarse); built
+    here when None.  The device-resident counts ride on the tags of inds / grad_out (fine rows) and of `out` (coarse rows).  One launch,
+    no read-back, capturable."""
+    lib = _lib.load()
+    g, ldg = _rows(_typed(grad_out, torch.float32, "grad_out"), "grad_out")
+    idx, ldi = _rows(_typed(inds, torch.int32, "inds"), "inds")
+    N1, C1 = int(num_coarse), int(C1)
+    N2 = idx.shape[0]
+    if N1 < 0 or C1 < 1 or g.shape[1] < C1:
+        raise ValueError("closest_pool_cat_backward: num_coarse = %d, C1 = %d, grad_out is %s" % (N1, C1, tuple(g.shape)))
+    if idx.shape[1] < 1 or g.shape[0] != N2:
+        raise ValueError("closest_pool_cat_backward: inds is %s, grad_out %s" % (tuple(idx.shape), tuple(g.shape)))
+    if out is not None:
+        out, ldo = _rows(_typed(out, torch.float32, "out"), "out")
+        if tuple(out.shape) != (N1, C1):
+            raise ValueError("closest_pool_cat_backward: out is %s, wanted %s" % (tuple(out.shape), (N1, C1)))
+    start = edges = None
+    if transpose is not None:
+        start, edges = _table("closest_pool_cat_backward", transpose, N1, N2)
+    n1_t = getattr(out, "n_dev", None) if out is not None else None
+    n2_t = _row_count(inds, grad_out)
+    _on_device("closest_pool_cat_backward", grad_out=g, inds=idx, out=out, start=start, edges=edges, n1_dev=n1_t, n2_dev=n2_t)
+    dev = g.device
+    if start is None:
+        start, edges = neighbor_transpose_supports(_tag(idx[:, :1], inds), N1, n2_t, n1_t)
+    if out is None:
+        out, ldo = torch.empty((N1, C1), dtype=torch.float32, device=dev), C1
+    with _timed("closest_pool_cat_backward", dict(N1=N1, N2=N2, C1=C1), dev):
+        rc = lib.d3f_closest_pool_cat_backward(g.data_ptr(), N2, ldg, C1, idx.data_ptr(), ldi, N1, start.data_ptr(), edges.data_ptr(),
+                                               out.data_ptr(), ldo, _ptr(n1_t), _ptr(n2_t), _stream(dev))
+    _lib.check(rc, "closest_pool_cat_backward")
+    return out
+
+
 class RawRecords:
     """A cloud still in its file encoding (utils.ply.read_ply_records / utils.results.read_kitti_records): raw bytes + record
     layout.  FragmentEngine.submit takes it wherever it takes a float32 [n,3] cloud and decodes it on the GPU, straight into

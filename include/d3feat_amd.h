@@ -1003,6 +1003,59 @@ int d3f_batch_norm_backward(const float* x, int ldx, const float* y, int ldy, co
                             const float* mean, const float* rstd, int leaky, float alpha, float* gx, int ldgx, float* ggamma,
                             float* gbeta, float* gres, int ldgr, const int* M_dev, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Backward of d3f_ind_max_pool (models/network_blocks.py:51-66): TF's gradient of gather -> reduce_max with the reduce_min behind the
+ * shadow row, under the equal-split tie rule of d3f_detect_head_backward.  fp32 rows only: feat_bf16 != 0 is D3F_ERR_ARG.
+ * x f32[n1, C] (ldx) the pooled layer's input, idx i32[n2, ld_idx] (K columns), y f32[n2, C] (ldy) the STORED forward output, gy f32[n2, C]
+ * (ldg) its gradient, gx f32[n1, C] (ldgx) the result; n1 = min(N1, *N1_dev), n2 = min(N2, *N2_dev) (either pointer may be NULL), N1 and
+ * N2 are capacities.  start / edges: the table d3f_neighbor_transpose_qs made of the same idx with Ns = N1.
+ * Forward: x' = concat(x, colmin), colmin[c] = min_j x[j,c] (the ordered minimum: -0 below +0); a slot whose index is outside [0, n1) is a
+ * SHADOW slot and gathers colmin; y[i,c] = max_k x'[idx[i,k], c].
+ * Backward.  Equality is equality of VALUES (tf.equal: -0 == +0); inputs are finite.
+ *   T[i,c]  = the number of the K slots of row i whose gathered value equals y[i,c]: a real index listed twice counts twice, every
+ *             shadow slot counts on its own, and counts when colmin[c] == y[i,c]
+ *   gs[i,c] = gy[i,c] / T[i,c]                       one fp32 division (T == 0, which a y of the forward never gives, takes gs = 0)
+ *   S[c]    = sum_i (tying shadow slots of (i,c)) * gs[i,c]        the products rounded in fp32, the sum in float64
+ *   M[c]    = #{j < n1 : x[j,c] == colmin[c]}
+ *   gx[j,c] = sum over the edges e = i K + k of row j's segment, in ascending e, of [x[j,c] == y[i,c]] gs[i,c]
+ *             + [x[j,c] == colmin[c]] float(S[c] / M[c])
+ * Summation orders.  The segment sum is ONE fp32 chain per entry in ascending e, started at zero, and the shadow share is added last.
+ * S: pooled rows are cut into slices of 256 rows, doubled until at most 128 slices cover the capacity N2; with LQ = min(16, the power of
+ * two >= ceil(C / 4)) and R = 256 / LQ, chain r of a slice adds the rows r, r + R, ... in ascending order from 0.0, the R chains are added
+ * by the tree chain[r] += chain[r + s], s = R/2 .. 1, and the slice partials in ascending slice order -- all in float64, the rule of
+ * d3f_batch_norm_train.  colmin and M are integer work (ordered minima and counts): any order gives the same result.  No float atomic;
+ * two calls give equal bits; a row of gx depends on its own segment and on the two column vectors only.
+ * Kernels: lanes run across columns, a quad of four columns per lane; one 16-byte access per quad when C % 4 == 0, every leading dimension
+ * is a multiple of 4 and x, y, gy, gx are 16-byte aligned, four guarded 4-byte accesses otherwise -- the same thread mapping and the
+ * same orders on both paths.  Three launches: column minima and their counts per slice of fine rows; per pooled row T, gs and the
+ * slice partials of S, whose last workgroup to finish folds colmin, M and S into the share; the segment gather.  All sizes are read on
+ * the device; no memset, no read-back; capturable.
+ * Every word of the first n1 rows (C columns) of gx is written; rows at or beyond n1 are left alone; a row nobody names gets exactly
+ * the shadow share or zero; n2 == 0 (or K == 0) writes zeros.  x rows at or beyond n1 and idx / y / gy rows at or beyond n2 are never
+ * read; no index outside [0, n1) forms an address; the table is range-checked, never trusted.  N1 == 0 is D3F_OK.
+ * D3F_ERR_ARG before anything touches the device: feat_bf16 != 0, a negative size, C < 1 or > 2^20, N2 * K > 2^31 - 8192, ld_idx < K,
+ * ldx / ldy / ldg / ldgx < C, a NULL x, gx or start, a NULL y or gy with N2 > 0, a NULL idx or edges with N2 * K > 0.
+ * workspace >= d3f_ind_max_pool_backward_workspace_bytes(N1, N2, K, C): gs (N2 rows of ceil(C / 4) quads), the slice partials, two
+ * column vectors and a ticket; its contents before the call do not matter; else D3F_ERR_WORKSPACE.  The function returns 0 for sizes
+ * the call refuses. */
+size_t d3f_ind_max_pool_backward_workspace_bytes(int N1, int N2, int K, int C);
+int d3f_ind_max_pool_backward(const void* x, int N1, int ldx, int C, const int* idx, int N2, int ld_idx, int K, const void* y, int ldy,
+                              const float* gy, int ldg, const int* start, const int* edges, float* gx, int ldgx, const int* N1_dev,
+                              const int* N2_dev, int feat_bf16, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of d3f_closest_pool_cat (models/network_blocks.py:69-83 + models/D3Feat.py:63) with respect to x: from g f32[n2, >= C1]
+ * (ldg), the gradient of out = [x'[idx[n,0]] | skip[n]], to gx f32[n1, C1] (ldgx):
+ *   gx[j,:] = sum of g[n, 0:C1] over the fine rows n < n2 with idx[n,0] == j, in ascending n, ONE fp32 chain per entry started at zero.
+ * A shadow index (outside [0, n1)) carries no gradient.  The gradient of skip is the column view g[:, C1:]: no kernel.
+ * idx i32[n2, ld_idx]: the first column is read.  start / edges: the table d3f_neighbor_transpose_qs made of that ONE column (K = 1,
+ * the same ld_idx, Ns = N1); an edge is used only when it is in range and idx[e, 0] == j.  n1 = min(N1, *N1_dev), n2 = min(N2, *N2_dev).
+ * One launch, the thread mapping and the two access paths of d3f_ind_max_pool_backward (16 bytes when C1 % 4 == 0, ldg and ldgx are
+ * multiples of 4 and g, gx are 16-byte aligned); no atomic, no memset, no read-back, capturable; two calls give equal bits.  Every word of
+ * the first n1 rows (C1 columns) of gx is written, rows nobody names get zeros (n2 == 0: all), rows at or beyond n1 are left alone.
+ * D3F_ERR_ARG before anything touches the device: a negative size, C1 < 1 or > 2^20, N2 > 2^31 - 8192, ldg < C1, ldgx < C1, ld_idx < 1,
+ * a NULL gx or start, a NULL g, idx or edges with N2 > 0.  N1 == 0 is D3F_OK. */
+int d3f_closest_pool_cat_backward(const float* g, int N2, int ldg, int C1, const int* idx, int ld_idx, int N1, const int* start,
+                                  const int* edges, float* gx, int ldgx, const int* N1_dev, const int* N2_dev, void* stream);
+
 /* The KITTI test metric of P * per_pair estimated transforms in two launches (utils/tester.py:326-344 of the reference: relative
  * translation error, relative rotation error, success under both thresholds, and the sums of its three AverageMeters).
  *   T_est f32[P * per_pair, 12], row-major [R | t]; gt f32[P, 12] in the SAME direction as T_est: source -> target, the direction of
