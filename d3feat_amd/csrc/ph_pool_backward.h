@@ -246,6 +246,8 @@ extern "C" int d3f_ind_max_pool_backward(const void* x_, int N1, int ldx, int C,
     const int S1 = d3f_slice_rows(N1), S2 = d3f_slice_rows(N2);
     const int sl1 = d3f_cdiv(N1, S1), sl2 = d3f_cdiv(N2 > 0 ? N2 : 1, S2);
     const int Cp = pb_quad_cols(C);
+    // (tests/test_gpu_pool_backward.py::test_column_minimum_held_as_zeros_of_both_signs reads colmin at the offset this order gives:
+    // a change of the order or of the alignment goes with a change there)
     D3fArena ar(workspace, workspace_bytes);
     unsigned* ticket = ar.take<unsigned>(1);
     unsigned* pmin = ar.take<unsigned>((size_t)sl1 * C);

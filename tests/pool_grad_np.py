@@ -92,15 +92,56 @@ def torch_closest_pool_cat(x, inds, skip=None):
 
 
 # ---- the shared cases ---------------------------------------------------------------------------------------------------------
-def pool_case(seed, N1, N2, K, C, quantised=True, ties=True, dtype=np.float32):
+def sliced_pool_case(seed, N1, N2, K, C, S=256, zero_column=None, dtype=np.float32):
+    """pool_case for more than one slice of S rows on either side (the device folds per-slice partials): quantised values, and in EVERY
+    slice of pooled rows, at its first rows p0, p0 + 1, p0 + 2 (a trailing slice shorter than 3 rows: as many as fit) --
+      p0             no valid neighbour (all K slots shadow: y = colmin, T = K per column, so the slice's shadow share is not zero)
+      p0 + 1         its only valid neighbour is fine row N1 - 2, the strict argmin of column 0 -- a row of the LAST slice of fine rows,
+                     so the minimum of column 0 is held there only -- beside K - 1 shadow slots
+      p0 + 2         names fine row 7 twice (K > 2)
+    column 1's minimum is held by one fine row of each of the first three slices (M = 3, or fewer slices: fewer); fine row 3 is named
+    in slot 0 by every sixth pooled row from row 5 on (at most 90 of them: the longest segment), fine rows 4 and S + 4 by none (both
+    hold a zero of zero_column).
+    zero_column: that column holds non-negative multiples of 1/8 whose zeros are +0 in the first slice of fine rows and -0 beyond."""
+    rng = np.random.default_rng(seed)
+    assert N1 >= 2 * S and N2 >= 8 and K >= 3
+    x = rng.integers(-16, 17, (N1, C)) / 8.0
+    inds = rng.integers(0, N1, (N2, K))
+    inds[rng.random((N2, K)) < 0.2] = N1
+    inds[rng.random((N2, K)) < 0.03] = N1 + 3
+    inds[rng.random((N2, K)) < 0.03] = -1
+    inds[(inds == 4) | (inds == 3) | (inds == S + 4)] = 8
+    inds[5:5 + 6 * 90:6, 0] = 3
+    for p0 in range(0, N2, S):
+        inds[p0, :] = N1
+        if p0 + 1 < N2:
+            inds[p0 + 1, :] = N1
+            inds[p0 + 1, 0] = N1 - 2
+        if p0 + 2 < N2:
+            inds[p0 + 2, 1:3] = 7
+    x[N1 - 2, 0] = x[:, 0].min() - 0.5
+    if C > 1:
+        x[[r for r in (2, S + 6, 2 * S + 9) if r < N1 - 2], 1] = x[:, 1].min() - 0.25
+    if zero_column is not None:
+        col = rng.integers(0, 17, N1) / 8.0
+        col[[1, 4, S - 1, S, S + 4, N1 - 1]] = 0.0
+        col[S:][col[S:] == 0] = -0.0
+        x[:, zero_column] = col
+    g = rng.normal(size=(N2, C))
+    return x.astype(dtype), inds.astype(np.int32), g.astype(dtype)
+
+
+def pool_case(seed, N1, N2, K, C, quantised=True, ties=True, dtype=np.float32, slice_rows=None, zero_column=None):
     """x [N1, C], inds i32[N2, K] with shadow entries (N1 and beyond, and negative), g [N2, C].  quantised: multiples of 1/8 in [-2, 2]
-    (many ties).  ties (N1 >= 12, N2 >= 8): the planted rows --
+    (many ties).  slice_rows / zero_column: sliced_pool_case above instead.  ties (N1 >= 12, N2 >= 8): the planted rows --
       pooled row 0   no valid neighbour (all K slots shadow: y = colmin, T = K per column)
       pooled row 1   its only valid neighbour is fine row 5, which is made the strict argmin of column 0, beside shadow slots when K > 1
                      (column 0 ties between the real slot and the K - 1 shadow slots)
       column 1       its minimum is held by the fine rows 2, 6 and 9 (M = 3)
       pooled row 2   names fine row 7 twice when K > 1
       fine row 3     named by every pooled row but rows 0 and 1 (slot 0); fine row 4 named by none."""
+    if slice_rows is not None:
+        return sliced_pool_case(seed, N1, N2, K, C, slice_rows, zero_column, dtype)
     rng = np.random.default_rng(seed)
     if quantised:
         x = rng.integers(-16, 17, (N1, C)) / 8.0

@@ -58,6 +58,33 @@ def test_max_pool_restatement_against_torch_float64_autograd():
     assert seen["T"] >= 3 and seen["shadow"] >= 2 and seen["M"] >= 3
 
 
+def test_sliced_case_against_torch_float64_autograd():
+    """pool_grad_np.sliced_pool_case (the case of the GPU test's runs beyond one slice of pooled rows) is what it claims to be, and on it
+    the restatement agrees with float64 torch autograd to 1e-12 -- the zeros of both signs included: torch's amin / amax compare
+    values, so +0 and -0 tie."""
+    S, N1, N2, K = 256, 3 * 256 + 25, 2 * 256 + 7, 7
+    for C, zc in ((3, None), (64, None), (4, 2)):
+        x, inds, g = pg.pool_case(70 + C, N1, N2, K, C, dtype=np.float64, slice_rows=S, zero_column=zc)
+        y = pg.max_pool_forward(x, inds)
+        want_y, want = _torch_pool_gradient(x, inds, g)
+        assert np.array_equal(y, want_y)
+        p = pg.max_pool_backward(x, inds, y, g, parts=True)
+        assert np.abs(p["gx"] - want).max() <= 1e-12 * np.abs(want).max()
+        shadow = (inds < 0) | (inds >= N1)
+        for a in range(0, N2, S):
+            assert shadow[a].all() and (p["shadow_ties"][a] == K).all() and (p["T"][a + 1, 0] == K) and (inds[a + 2] == 7).sum() >= 2
+            assert (p["T"][a:a + S] >= 2).any() and (inds[a + 1] == N1 - 2).sum() == 1
+            assert ((p["shadow_ties"][a:a + S] * p["gs"][a:a + S]).sum(0) != 0).any()
+        assert p["M"][0] == 1 and np.nonzero(x[:, 0] == p["colmin"][0])[0].tolist() == [N1 - 2] and p["M"][1] == 3
+        assert pg.longest_segment(inds, N1) <= 90 and not (inds == 4).any() and not (inds == S + 4).any()
+        if zc is not None:
+            zero = x[:, zc] == 0
+            assert p["colmin"][zc] == 0 and p["M"][zc] == zero.sum() and zero[[4, S + 4]].all()
+            assert not np.signbit(x[:S, zc][zero[:S]]).any() and np.signbit(x[S:, zc][zero[S:]]).all()
+            share = p["S"][zc] / p["M"][zc]
+            assert share != 0 and np.allclose(p["gx"][[4, S + 4], zc], share, rtol=1e-15)
+
+
 def test_upsample_restatement_against_torch_float64_autograd():
     for at, (N1, N2, K, C1, C2) in enumerate([(50, 300, 3, 4, 0), (50, 300, 1, 1, 32), (12, 40, 5, 7, 3)]):
         inds, g = pg.upsample_case(20 + at, N1, N2, K, C1, C2, dtype=np.float64)
