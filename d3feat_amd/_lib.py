@@ -23,6 +23,7 @@ MATCH_KMAX = 8192
 VALIDATION_NMAX = 1024
 SCENES_MAX = 256
 GRID_RESET_MAX = 8
+SGD_CHUNK = 4096                                # elements of a variable per workgroup of d3f_momentum_sgd
 VP_INDEX_RANGE, VP_COUNT_RANGE = 1, 2           # status of a pair of d3f_validation_pairs
 
 _vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
@@ -123,6 +124,9 @@ SIGNATURES = {
     "d3f_ind_max_pool_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "d3f_ind_max_pool_backward": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "d3f_closest_pool_cat_backward": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "d3f_momentum_sgd_plan": (_i, [_vp, _i, _vp, _i]),
+    "d3f_momentum_sgd_workspace_bytes": (_sz, [_i, _i]),
+    "d3f_momentum_sgd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "d3f_pose_errors": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "d3f_sanitize_descriptors": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "d3f_matching_summary": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),

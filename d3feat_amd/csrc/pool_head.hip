@@ -557,6 +557,9 @@ extern "C" int d3f_affine_act(const float* x, int ldx, int M, int N, const float
 // the backward of the two gathers above (d3f_ind_max_pool_backward, d3f_closest_pool_cat_backward)
 #include "ph_pool_backward.h"
 
+// the optimiser's step of every variable in one call (d3f_momentum_sgd)
+#include "ph_optimizer.h"
+
 // ------------------------------------------------------------------------------------------------
 // (xyz, desc, score) -> one record f32[3 + C + 1] per point: the 144-byte payload (C = 32) that the testers write per
 // fragment (utils/tester.py:215-229 keeps points / features / scores together) and that the multi-GPU runner gathers once

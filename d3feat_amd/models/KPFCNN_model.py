@@ -19,7 +19,9 @@ Training: with model.dropout_prob < 0.99 (the reference feeds 0.5, utils/trainer
 and the gradients of desc_loss + det_loss from ONE validation.loss_gradients call, and sets regularization_loss = weights_decay * the sum
 of 0.5 |v|^2 over the variables whose name contains `weights` (:189-190) and loss = desc_loss + det_loss + regularization_loss (:191),
 an autograd scalar.  backward() zeroes the .grad of variables.parameters() and calls loss.backward(); d3feat_amd/training.py holds the
-optimiser's update.  Under the skip rule (:172-186) the five figures are the skip tuple and carry no gradient.  Deformable blocks,
+optimiser's update.  With fold_regularization = True the regularisation term stays out of the graph (loss = desc_loss + det_loss): its
+gradient weights_decay * v is added by training.DeviceMomentumSGD's step, and regularization_loss is that optimiser's device scalar --
+the figure of the PREVIOUS step until step() has run on this pass's gradients.  Under the skip rule (:172-186) the five figures are the skip tuple and carry no gradient.  Deformable blocks,
 bf16 feature rows, graph replay and several GPUs are not built for training.
 """
 import numpy as np
@@ -50,6 +52,10 @@ class KernelPointFCNN:
         self._skip = None
         self.desc_loss = self.det_loss = self.accuracy = self.ave_d_pos = self.ave_d_neg = None
         self.regularization_loss = self.loss = None
+        # True: the regularisation term stays out of the autograd graph (loss = desc_loss + det_loss); its gradient and its value
+        # come from a training.DeviceMomentumSGD built with weights_decay (its attach(model) sets both attributes)
+        self.fold_regularization = False
+        self.regularization_scalar = None
         if isinstance(flat_inputs, (list, tuple)):
             self.run(flat_inputs)
 
@@ -121,18 +127,30 @@ class KernelPointFCNN:
                 self.out_features, self.out_scores, self.anchor_inputs['backup_points'], anc, pos, safe_radius=cfg.safe_radius,
                 keypts_num=cfg.keypts_num, det_loss_weight=cfg.det_loss_weight)
             self.desc_loss, self.det_loss, self.accuracy, self.ave_d_pos, self.ave_d_neg = self.validation.figures(0)
+        if self.fold_regularization:
+            # the optimiser's device scalar: float(weights_decay * sum 0.5 |v|^2) of the values the LAST step started from, so it is the
+            # previous step's figure until step() has run on this pass's gradients, and this pass's afterwards
+            opt = self.regularization_scalar
+            self.regularization_loss = opt.regularization_loss if opt is not None else None
+            self.loss = pair if isinstance(pair, torch.Tensor) else torch.zeros((), dtype=torch.float32, device=self.device)
+            return
         reg = [0.5 * (p * p).sum() for name, p in self.variables.parameters().items() if 'weights' in name]
         self.regularization_loss = float(cfg.weights_decay) * torch.stack(reg).sum()
         self.loss = pair + self.regularization_loss
 
-    def backward(self):
-        """The gradient of `loss` into the .grad of every leaf of variables.parameters() (zeroed first) -> that dict."""
+    def backward(self, keep_grads=False):
+        """The gradient of `loss` into the .grad of every leaf of variables.parameters() (zeroed first) -> that dict.
+        keep_grads: the .grad tensors stay where they are and autograd accumulates into them in place -- for gradient buffers that an
+        optimiser has installed and zeroes itself (training.DeviceMomentumSGD, persistent_grads); a leaf the backward does not reach
+        keeps its zeros."""
         if self.loss is None:
             raise RuntimeError('backward(): run() with dropout_prob < 0.99 first')
         params = self.variables.parameters()
-        for p in params.values():
-            p.grad = None
-        self.loss.backward()
+        if not keep_grads:
+            for p in params.values():
+                p.grad = None
+        if self.loss.requires_grad:                      # (folded regularisation under the skip rule: nothing carries a gradient)
+            self.loss.backward()
         for p in params.values():
             if p.grad is None:
                 p.grad = torch.zeros_like(p)

@@ -1882,3 +1882,50 @@ def unary_backward(x, W, grad_y, need_input=True, need_weights=True):
     if need_weights:
         gW = gemm_tn(x, grad_y)
     return gx, gW
+
+
+def momentum_sgd_plan(counts):
+    """The chunk table of momentum_sgd_step for variables of `counts` elements -> i32[nchunks, 2] on the HOST, (variable, first element)
+    per chunk of _lib.SGD_CHUNK elements: a variable's chunks are contiguous and in element order (d3f_momentum_sgd_plan).  Host only."""
+    lib = _lib.load()
+    counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    n = lib.d3f_momentum_sgd_plan(counts.ctypes.data, counts.size, None, 0)
+    if n < 0:
+        _lib.check(n, "momentum_sgd_plan")
+    table = np.zeros((n, 2), np.int32)
+    rc = lib.d3f_momentum_sgd_plan(counts.ctypes.data, counts.size, table.ctypes.data, n)
+    if rc != n:
+        _lib.check(min(rc, -3), "momentum_sgd_plan")
+    return table
+
+
+def momentum_sgd_workspace_bytes(num_variables, num_chunks):
+    return int(_lib.load().d3f_momentum_sgd_workspace_bytes(int(num_variables), int(num_chunks)))
+
+
+def momentum_sgd_step(desc, chunks, hyper, zero_grad=False, reg_loss=None, ws=None):
+    """One optimiser step of every variable in one call (include/d3feat_amd.h, d3f_momentum_sgd): desc i64[T, 4] on the device, one
+    descriptor per variable (the addresses of v, g -- 0: skipped -- and a, then count + (decay << 32)); chunks i32[nchunks, 2] on the
+    device (momentum_sgd_plan of the same counts); hyper f32[4] on the device, {lr, mom, clip, wd}; reg_loss f32[1] or None; ws: a byte
+    buffer of momentum_sgd_workspace_bytes(T, nchunks) that the caller owns (a captured call keeps its own), else the shared scratch.
+    Two launches, no read-back, capturable.  Nothing is returned: v, a (and g with zero_grad) are rewritten in place."""
+    lib = _lib.load()
+    _typed(desc, torch.int64, "desc", 2)
+    _typed(chunks, torch.int32, "chunks", 2)
+    _typed(hyper, torch.float32, "hyper", 1)
+    if desc.shape[1] != 4 or chunks.shape[1] != 2 or hyper.numel() != 4 or not (desc.is_contiguous() and chunks.is_contiguous() and hyper.is_contiguous()):
+        raise ValueError("momentum_sgd_step: desc is %s, chunks %s, hyper %s" % (tuple(desc.shape), tuple(chunks.shape), tuple(hyper.shape)))
+    if reg_loss is not None and _typed(reg_loss, torch.float32, "reg_loss").numel() != 1:
+        raise ValueError("momentum_sgd_step: reg_loss must hold one float")
+    _on_device("momentum_sgd_step", desc=desc, chunks=chunks, hyper=hyper, reg_loss=reg_loss, ws=ws)
+    dev = desc.device
+    T, nchunks = desc.shape[0], chunks.shape[0]
+    nbytes = lib.d3f_momentum_sgd_workspace_bytes(T, nchunks)
+    if ws is None:
+        ws = workspace(nbytes, dev)
+    elif ws.dtype != torch.uint8 or ws.numel() < nbytes:
+        raise ValueError("momentum_sgd_step: ws must be a uint8 buffer of at least %d bytes" % nbytes)
+    with _timed("momentum_sgd_step", dict(T=T, nchunks=nchunks), dev):
+        rc = lib.d3f_momentum_sgd(desc.data_ptr(), T, chunks.data_ptr(), nchunks, hyper.data_ptr(), 1 if zero_grad else 0, _ptr(reg_loss),
+                                  ws.data_ptr(), ws.numel(), _stream(dev))
+    _lib.check(rc, "momentum_sgd_step")

@@ -1056,6 +1056,47 @@ int d3f_ind_max_pool_backward(const void* x, int N1, int ldx, int C, const int* 
 int d3f_closest_pool_cat_backward(const float* g, int N2, int ldg, int C1, const int* idx, int ld_idx, int N1, const int* start,
                                   const int* edges, float* gx, int ldgx, const int* N1_dev, const int* N2_dev, void* stream);
 
+/* The optimiser's step of EVERY variable in one call (utils/trainer.py:119-156 of the reference: tf.train.MomentumOptimizer, no
+ * Nesterov, behind a per-variable tf.clip_by_norm; the gradient of the regularisation loss of KPFCNN_model.py:189-191 folded in).
+ * desc: T descriptors on the DEVICE, one per variable: v f32[count] the variable, g f32[count] its gradient, a f32[count] its `Momentum`
+ *   slot, and a decay flag.  A variable whose g (or v, or a) is NULL is skipped whole: v and a are left untouched, nothing goes into R.
+ * chunks: the table d3f_momentum_sgd_plan made of the same counts, on the device: i32[nchunks, 2] = (variable, first element); every
+ *   variable is cut into chunks of D3F_SGD_CHUNK elements, a variable's chunks are contiguous and in element order.  The kernels
+ *   range-check every entry against desc; an entry that does not fit is passed over.
+ * hyper: f32[4] on the DEVICE, {lr, mom, clip, wd}: read by the kernels, so a captured call follows a new learning rate.
+ * Per variable, fl(.) one float32 rounding, nothing contracted into a fused multiply-add:
+ *   g1 = g                      (decay == 0)        g1 = fl(g + fl(wd * v))      (decay != 0)
+ *   S  = sum over the variable of (double)g1 * (double)g1,  n = (float)sqrt(S)   (a correctly rounded float64 root, rounded once more)
+ *   s  = clip > 0 ? fl(clip / max(n, clip)) : 1          (n == 0 gives 1; a NaN n stays NaN)
+ *   g2 = fl(g1 * s),   a' = fl(fl(mom * a) + g2),   v' = fl(v - fl(lr * a'))
+ *   R  = sum over the decayed variables of 0.5 * (double)v * (double)v  of the OLD v;  *reg_loss_out = (float)((double)wd * R)
+ * zero_grad != 0: every word of g inside the counts is +0 afterwards (a gradient buffer that autograd accumulates into stays in place);
+ * else g is only read.  reg_loss_out may be NULL.  A non-finite gradient follows the arithmetic and stays inside its own variable.
+ * Summation orders, all float64 from 0.0.  Within a chunk, thread t of 256 adds the elements of its quads t, t + 256, ... (quad q =
+ * elements 4 q .. 4 q + 3 of the chunk) in ascending order; lane l of a wave takes acc += acc[l + s] for s = 32 .. 1; the four wave sums
+ * are added as (w0 + w2) + (w1 + w3).  A variable's chunk partials are added in chunk order, R's over the whole table in table order.
+ * A quad is one 16-byte access where v, g and a of the variable are all 16-byte aligned, four 4-byte accesses otherwise and in a
+ * variable's tail: the same orders and the same bits on both paths.
+ * Two launches whatever T is (partials; totals + update).  No float atomic, no memset, no read-back, capturable; two calls on equal
+ * inputs give equal bits; no word beyond count of any tensor is written.  T == 0 launches nothing and returns D3F_OK.
+ * D3F_ERR_ARG before anything touches the device: T or nchunks negative, a NULL hyper, a NULL desc with T > 0, a NULL chunks with T > 0
+ * and nchunks > 0.  workspace >= d3f_momentum_sgd_workspace_bytes(T, nchunks): 16 bytes per chunk, every word of it written before it is
+ * read; else D3F_ERR_WORKSPACE.  The size function returns 0 for negative sizes.
+ * d3f_momentum_sgd_plan (host only): counts i32[T] -> the number of chunks, and the first chunks_cap of them into chunks_out when it is
+ * not NULL; D3F_ERR_ARG for a negative T, count or chunks_cap, a NULL counts with T > 0, more than 2^30 chunks. */
+#define D3F_SGD_CHUNK 4096
+typedef struct d3f_sgd_var {
+    float* v;
+    float* g;
+    float* a;
+    int count;
+    int decay;
+} d3f_sgd_var;
+int d3f_momentum_sgd_plan(const int* counts, int T, int* chunks_out, int chunks_cap);
+size_t d3f_momentum_sgd_workspace_bytes(int T, int nchunks);
+int d3f_momentum_sgd(const void* desc, int T, const int* chunks, int nchunks, const float* hyper, int zero_grad, float* reg_loss_out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* The KITTI test metric of P * per_pair estimated transforms in two launches (utils/tester.py:326-344 of the reference: relative
  * translation error, relative rotation error, success under both thresholds, and the sums of its three AverageMeters).
  *   T_est f32[P * per_pair, 12], row-major [R | t]; gt f32[P, 12] in the SAME direction as T_est: source -> target, the direction of
