@@ -21,6 +21,7 @@ PAIRS_KMAX = 1024
 REPEAT_COUNTS_MAX = 16
 MATCH_KMAX = 8192
 VALIDATION_NMAX = 1024
+TRAINING_KEYPTS_MAX = 1024
 SCENES_MAX = 256
 GRID_RESET_MAX = 8
 SGD_CHUNK = 4096                                # elements of a variable per workgroup of d3f_momentum_sgd
@@ -133,6 +134,10 @@ SIGNATURES = {
     "d3f_registration_recall": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "d3f_icp_pairs_workspace_bytes": (_sz, [_i, _i]),
     "d3f_icp_pairs": (_i, [_vp, _sz, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i] + [_vp] * 9 + [_sz, _vp]),
+    "d3f_training_draw": (_i, [C.c_uint64, C.c_uint64, _i, _i, C.c_uint64, _vp]),
+    "d3f_training_pairs_workspace_bytes": (_sz, [_i, _i, _i]),
+    "d3f_training_pairs": (_i, [_vp, _sz, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _i, _i, C.c_uint64, _vp, _i, C.c_uint64, _i, _f, _i, _f, _f,
+                                _f] + [_vp] * 4 + [_i] + [_vp] * 6 + [_sz, _vp]),
     "d3f_gemm_pack_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_pack_f32t": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "d3f_gemm_f32t": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp, _sz,

@@ -1058,3 +1058,6 @@ extern "C" int d3f_batch_radius_neighbors(const float* queries, int Nq, const fl
 
 // ---- point-to-point ICP of every pair to convergence (nb_icp.h) -------------------------------------------------------------------
 #include "nb_icp.h"
+
+// ---- training pairs: correspondences, sample and augmentation of every pair in one call (nb_training_pairs.h) ---------------------
+#include "nb_training_pairs.h"

@@ -64,6 +64,15 @@ __device__ __forceinline__ float rc_d2(float qx, float qy, float qz, float x, fl
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
+// the mixing function of every counter-based draw of this library (splitmix64's finaliser): d3f_ransac_draw (registration.hip) and
+// d3f_training_draw (nb_training_pairs.h) are built on it
+__host__ __device__ __forceinline__ unsigned long long rg_splitmix(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
 // The winner among the validated hypotheses of a pair.  better(a, b): larger count, then smaller sumd2, then earlier place in the list
 // (= earlier iteration)
 struct RcBest { int c; unsigned long long s; int v; };

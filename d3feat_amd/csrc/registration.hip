@@ -179,12 +179,7 @@ extern "C" int d3f_mutual_matches(const int* ab, int Na, const int* ba, int Nb, 
 // ---------------------------------------------------------------------------------------------------------------------
 // RANSAC hypotheses: one thread per iteration
 // ---------------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ unsigned long long rg_splitmix(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+// rg_splitmix: rc_shared.h -- shared with the training-pair draws of radius_neighbors.hip (nb_training_pairs.h)
 // draw d of iteration it: uniform integer in [0, n)  (counter based: a pure function of (seed, it, d))
 __host__ __device__ __forceinline__ int rg_draw(unsigned long long seed, unsigned long long it, int d, int n) {
     const unsigned long long r = rg_splitmix(seed ^ rg_splitmix(it * 64ull + (unsigned long long)d));

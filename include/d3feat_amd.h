@@ -1254,6 +1254,83 @@ int d3f_icp_pairs(const void* grid, size_t grid_bytes, int N_tgt, const float* s
                   double* sumd2, double* fitness, double* rmse, int* iterations, int* converged, int* nearest, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* Training pairs: the correspondences, the sample and the augmentation of P pairs in one call (what the reference's generators do per
+ * pair on the host: datasets/KITTI.py:35-48, 182-206, 319-337; datasets/ThreeDMatch.py:24-45, 222-229, 266-273).  No read-back, no
+ * host decision, every length read on the device: capturable.
+ *   points f32[N, 3]: 2 P stacked clouds, lens_dev i32[2 P]; cloud 2 p is the anchor and cloud 2 p + 1 the positive of pair p.  A
+ *   length below 0 counts as 0, one that runs past N is cut there; n = the sum.  Rows from n on are neither read nor written.
+ * THE DRAWS.  Counter based and stateless: with mix = the finaliser of splitmix64 (the function under d3f_ransac_draw),
+ *   key  = mix(mix(seed ^ mix(step)) ^ (pair << 8 | stream)),   draw(seed, step, pair, stream, counter) = mix(key ^ counter),
+ * 64 bits; d3f_training_draw is the host copy (D3F_ERR_ARG: out NULL, pair < 0, stream outside 0 .. 255).  pair = pair0 + p: a caller
+ * that splits a list of pairs over several calls passes the number of the first one, and P pairs in one call give the bits of P calls.
+ * u24(r) = (r >> 40) 2^-24, a float in [0, 1); integers in [0, m) are (r >> 11) mod m.  The streams and their counters:
+ *   D3F_TP_STREAM_NOISE + side     3 i + c        coordinate c of row i of the cloud (side 0: anchor, 1: positive)
+ *   D3F_TP_STREAM_ROTATION + side  2 d, 2 d + 1   angle and axis of rotation d of the cloud
+ *   D3F_TP_STREAM_SCALE            0              the scale of the PAIR
+ *   D3F_TP_STREAM_SHIFT + side     c              coordinate c of the shift of the cloud
+ *   D3F_TP_STREAM_SAMPLE           i              entry i of the sample
+ * step: *step_dev, a u64 on the device, read by the first kernel; the call's last kernel stores step + 1 there, so a replayed graph
+ * draws afresh every time with no host write.  use_host_step != 0: host_step is used instead (step_dev, when not NULL, still receives
+ * host_step + 1).  Equal (seed, step) give equal bits.
+ * THE MATCHES, radius form (grid != NULL: built by d3f_neighbor_grid_build over these points and lengths, B = 2 P, with a radius >=
+ * `radius`; trans f32[P, 16]: row-major 4 x 4, source to target, three rows read).  The anchor row (x, y, z) is moved to
+ *   q[r] = ((T[r,0] x + T[r,1] y) + T[r,2] z) + T[r,3], fp32, every operation rounded on its own (no FMA),
+ * and every row j of the positive with d2 = (dx dx + dy dy) + dz dz < radius radius STRICTLY (dx = q - s; fp32, no FMA: the metric of
+ * every search of this library) is a match (i, j).  The matches are ordered by i ascending and inside a row by (d2, j) ascending:
+ * get_matching_indices' list, FLANN returning a radius result by distance (equal distances: the smaller index here; Open3D's own bits
+ * are not pinned, it is not available to the tests).  M = their number (all pairs of a call together: below 2^31).  The list is never
+ * stored: match number t is the candidate of rank t - start[i] of the row i with start[i] <= t < start[i + 1].
+ * The sample, radius form: keypts_num DISTINCT match numbers by Floyd's algorithm -- S empty; for i = 0 .. keypts_num - 1 with
+ * j = M - keypts_num + i: t = draw(SAMPLE, i) mod (j + 1); entry i = t if t is not in S, else j; S gains entry i.  (Every subset is
+ * equally likely; M == keypts_num returns every match.)  anc_idx[p, i] = the match's i, pos_idx[p, i] = its j + the anchor's length:
+ * indices into the pair's own rows, the convention of d3f_loss_gradients.  status_dev[p]: D3F_TP_FEW_MATCHES when M < min_matches
+ * (the reference drops such a pair; its 1024 is an argument here), D3F_TP_BELOW_KEYPTS when M < keypts_num.
+ * List form (grid == NULL; keypts_pairs i32[L, 2], pair_start_dev i32[P + 1]: pair p owns rows pair_start[p] .. pair_start[p + 1] of
+ * the list, the reference's precomputed keypts): entry i is row draw(SAMPLE, i) mod len of the pair's list, WITH replacement, the
+ * second column shifted by the anchor's length.  No search, trans and radius are not read.  D3F_TP_BELOW_KEYPTS for an empty list,
+ * D3F_TP_LIST_RANGE for offsets outside 0 .. L.  The list's values are not checked (d3f_loss_gradients does).
+ * A pair with a status other than 0 gets n_dev[p] = 0 and NO index is written for it (d3f_loss_gradients then skips it); otherwise
+ * n_dev[p] = keypts_num.  matches_dev[p] = M (list form: the list's length).  row0_dev i32[P + 1]: the first row of every pair, and n.
+ * THE ROW PASS.  params f32[2 P, 16] per cloud: [0..8] R row-major, [9] scale, [10..12] shift, [13] the first angle, [14] the first
+ * axis, [15] augment_rotation.
+ *   R: identity for augment_rotation 0; for 1 one draw, for 3 the product (R_0 R_1) R_2 of three draws with axes 0, 1, 2, each entry
+ *      (a0 b0 + a1 b1) + a2 b2 in fp32 without FMA.  A draw: theta = ((r >> 11) 2^-53 2) pi in float64, c = (float)cos(theta),
+ *      s = (float)sin(theta), axis = (r' >> 11) mod 3 for augment_rotation 1; the matrix is the reference's own (ThreeDMatch.py:24-45,
+ *      as it stands): [[c, -s, -s], [s, c, -s], [s, s, c]] with column and row `axis` cleared and R[axis, axis] = 1.
+ *   scale = scale_min + (scale_max - scale_min) u24, one per pair; shift[c] = -shift_range + (2 shift_range) u24, one per cloud; fp32,
+ *      each operation rounded on its own.
+ *   out_points row = ((p + u noise) @ R) scale + shift:  a[c] = p[c] + u24(NOISE, 3 i + c) augment_noise  (u uniform, not Gaussian: the
+ *      reference's rand);  o[j] = ((a[0] R[0,j] + a[1] R[1,j]) + a[2] R[2,j]) scale + shift[j];  fp32, no FMA.  The rows of a pair with
+ *      a status are augmented all the same.
+ *   backup row: radius form: the moved anchor rows and the positive's rows as they are (the pair in one frame); list form: the input.
+ * Launches: parameters and offsets; rows (backup, augmentation, the matches of every anchor row); radius form: the one-launch scan,
+ * the sample per pair, one thread per sample entry for its (i, j); list form: the sample per pair.  Five or three, whatever P is.
+ * No float atomic, no memset, fixed orders; nothing is written beyond n rows, P entries or keypts_num indices of a row.
+ * workspace >= d3f_training_pairs_workspace_bytes(N, P, keypts_num) (8 bytes per row, 4 per sample entry, the offsets), else
+ * D3F_ERR_WORKSPACE; so is a grid_bytes below d3f_neighbor_grid_bytes(N, 2 P).  The size function returns 0 for sizes the call refuses.
+ * D3F_ERR_ARG before anything touches the device: N < 0, P < 1, 2 P > D3F_MAX_BATCH, keypts_num outside 1 .. D3F_TRAINING_KEYPTS_MAX
+ * (the sample is drawn in LDS), ld_idx < keypts_num, pair0 < 0, L < 0, radius form: a radius that is not positive and finite, trans
+ * NULL; list form: keypts_pairs or pair_start_dev NULL; augment_rotation not 0 / 1 / 3, a NaN parameter, step_dev NULL without
+ * use_host_step, any other NULL pointer (points, out_points and backup may be NULL when N == 0).
+ * Asynchronous on `stream`, no allocation, no synchronisation. */
+#define D3F_TRAINING_KEYPTS_MAX 1024   /* largest keypts_num of d3f_training_pairs (= D3F_VALIDATION_NMAX, what the loss takes) */
+#define D3F_TP_STREAM_NOISE 0
+#define D3F_TP_STREAM_ROTATION 2
+#define D3F_TP_STREAM_SCALE 4
+#define D3F_TP_STREAM_SHIFT 6
+#define D3F_TP_STREAM_SAMPLE 8
+#define D3F_TP_FEW_MATCHES 1
+#define D3F_TP_BELOW_KEYPTS 2
+#define D3F_TP_LIST_RANGE 4
+int d3f_training_draw(uint64_t seed, uint64_t step, int pair, int stream, uint64_t counter, uint64_t* out);
+size_t d3f_training_pairs_workspace_bytes(int N, int P, int keypts_num);
+int d3f_training_pairs(const void* grid, size_t grid_bytes, const float* points, int N, const int* lens_dev, int P, const float* trans,
+                       const int* keypts_pairs, int L, const int* pair_start_dev, float radius, int keypts_num, int min_matches,
+                       uint64_t seed, uint64_t* step_dev, int use_host_step, uint64_t host_step, int pair0, float augment_noise,
+                       int augment_rotation, float scale_min, float scale_max, float shift_range, float* out_points, float* backup,
+                       int* anc_idx, int* pos_idx, int ld_idx, int* n_dev, int* row0_dev, int* matches_dev, int* status_dev,
+                       float* params, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
